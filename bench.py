@@ -9,18 +9,30 @@ triangles, materials) is resident in HBM before the timed region.  N GPUs shard 
 frame's samples (strong scaling: total work per frame is fixed).
 
 --bvh rebuilt (default) traverses the CRT_BVH_REBUILT 4-wide SAH BVH (same hit rule as the
-reference); at N=1 the same frame is then also rendered through the reference's own BVH and the
+reference); with --full at N=1 the same frame is then also rendered through the reference's own BVH and the
 image parity (per-channel RMS of the resolved colour, north-star bar 1e-4; bit-identical pixel
 fraction) is reported in the JSON line together with that frame's kernel time.  --bvh reference
 times the bit-exact reference-BVH path itself.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets the scene up, warms up, times the K frames and prints the line with the headline figures (metric,
+value, ms_per_step, the timed frames' kernel times).  --full adds everything that takes runs of its own: the end-to-end
+frame on a fresh renderer, the work-counting launch behind `algorithmic` and `roofline`, the parity frames (the
+reference-BVH frame at N=1, the statistical parity frames at N>1) and the CPU baseline; --no-count, --no-parity and
+--no-cpu-baseline leave single ones out of a --full run.  Without --full those fields are null.
+
+--dump-outputs DIR: after the timed frames rank 0 writes what the last timed frame left with the caller, the fp32
+linear sums (`linear.npy`, H x W x 3) and the resolved RGBA8 frame (`rgba8.npy`, as float32), at most 64 MB in all: an
+array that does not fit is written as its pixels at a fixed, seeded sample of positions (rows of a (pixels, channels)
+array, ascending pixel index).  The same arguments give the same scene, camera, seed and sample on every run.
 
 `--gpus N > 1` without a launcher environment starts `torch.distributed.run --nproc-per-node N` itself, as a child
 process, before anything imports torch or touches a GPU, relays rank 0's JSON line and exits with the child's code; a
 launcher whose WORLD_SIZE differs from --gpus is an error (exit 2).  At N > 1 the line carries each rank's render and
-collective times, the roofline of rank 0's share and a statistical parity field against the 1-GPU frame.
+collective times and, with --full, the roofline of rank 0's share and a statistical parity field against the 1-GPU frame
+(SURVEY §8e).
 
 rank 0 prints ONE JSON line (last line of stdout); progress goes to stderr.
 """
@@ -30,7 +42,6 @@ import argparse
 import importlib
 import json
 import os
-import socket
 import subprocess
 import sys
 import time
@@ -95,8 +106,15 @@ def parse(argv=None):
     ap.add_argument("--spp", type=int, default=2000)
     ap.add_argument("--bounces", type=int, default=20)
     ap.add_argument("--seed", type=int, default=41)
-    ap.add_argument("--no-count", action="store_true", help="skip the work-counting launch (roofline -> null)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the end-to-end frame, the work-counting "
+                         "launch (algorithmic, roofline), the parity frames and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed frame's outputs to DIR/linear.npy and DIR/rgba8.npy (float32, "
+                         "at most 64 MB in all; a larger array as a fixed, seeded sample of its pixels)")
+    ap.add_argument("--no-count", action="store_true",
+                    help="--full: skip the work-counting launch (algorithmic and roofline -> null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="target CPU-baseline sample duration")
     ap.add_argument("--cpu-single-seconds", type=float, default=8.0,
                     help="cpu_baseline: also time one thread on a band of the frame for about this long (0 = skip)")
@@ -133,7 +151,7 @@ def parse(argv=None):
     ap.add_argument("--bvh-width", type=int, default=4, help="rebuilt BVH: 4 (variant 4) or 2 (threaded)")
     ap.add_argument("--leaf-size", type=int, default=4)
     ap.add_argument("--traversal-cost", type=float, default=2.0)
-    ap.add_argument("--no-parity", action="store_true", help="skip the reference-BVH parity frame")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the parity frames")
     ap.add_argument("--print-workload-key", action="store_true",
                     help="print the key of profiles/roofline_counters.json for these arguments and exit (tools/pmc.sh)")
     ap.add_argument("--spatial-splits", action="store_true",
@@ -159,6 +177,8 @@ def parse(argv=None):
         ap.error("--bvh-width must be 2 or 4")
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.share is not None:
         g, n = args.share
         if not 0 <= g < n or args.gpus != 1 or args.shard != "spp":
@@ -171,18 +191,15 @@ def launched_by_torchrun() -> bool:
         k in os.environ for k in ("MASTER_ADDR", "MASTER_PORT", "RANK", "WORLD_SIZE"))
 
 
-def free_port() -> int:
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def spawn_ranks(args, argv) -> int:
     """`--gpus N > 1` from a plain `python bench.py`: run the N ranks under torch.distributed.run as a CHILD process
     (this process has not imported torch, let alone touched a GPU), pass their progress through, print rank 0's JSON
     line last and return the child's exit code (1 if it succeeded without a line)."""
+    # the c10d rendezvous on port 0: the launcher's store binds a free port itself and hands that store to the ranks,
+    # so no port is picked here and released again for somebody else to take before the launcher listens on it
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-           "--master-addr=127.0.0.1", f"--master-port={free_port()}", str(Path(__file__).resolve()), *argv]
+           "--rdzv-backend=c10d", "--rdzv-endpoint=127.0.0.1:0", f"--rdzv-id=bench-{os.getpid()}",
+           "--local-addr=127.0.0.1", str(Path(__file__).resolve()), *argv]
     log(f"[launch] --gpus {args.gpus} without a launcher: {' '.join(cmd)}")
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, bufsize=1)
     line = None
@@ -204,6 +221,35 @@ def spawn_ranks(args, argv) -> int:
         log("[launch] the ranks exited 0 without a JSON line")
         rc = 1
     return rc
+
+
+def scene_files(name: str):
+    """crt_amd.assets.scene_files(name), also where this user may not write the repository tree.
+
+    The bunny proxies are generated (seeded, the same bytes wherever they are written) into assets/generated/ the first
+    time a scene needs them.  If that folder cannot be made or written, they go to a per-user cache folder instead:
+    $XDG_CACHE_HOME or ~/.cache, else the temporary directory."""
+    from crt_amd import assets
+    try:
+        return assets.scene_files(name)
+    except OSError as e:
+        first = e
+    import functools
+    import tempfile
+    cache = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    for d in (Path(cache) / "crt_amd" / "generated", Path(tempfile.gettempdir()) / f"crt_amd_generated_{os.getuid()}"):
+        saved = assets.bunny_proxy, assets.million_proxy
+        # SCENES calls the generators by their module names: hand them the other folder for this one call
+        assets.bunny_proxy, assets.million_proxy = (functools.partial(f, d) for f in saved)
+        try:
+            files = assets.scene_files(name)
+            log(f"[scene] {first}: generated assets are in {d}")
+            return files
+        except OSError:
+            continue
+        finally:
+            assets.bunny_proxy, assets.million_proxy = saved
+    raise first
 
 
 def cgroup_cpu_quota():
@@ -232,7 +278,6 @@ def cpu_baseline(args, cam_floats, log_fn):
     sys.path.insert(0, str(REPO / "oracle"))
     import objload
     import pyoracle
-    from crt_amd import assets
     try:
         affinity = len(os.sched_getaffinity(0))
     except AttributeError:
@@ -242,7 +287,7 @@ def cpu_baseline(args, cam_floats, log_fn):
     # 16-CPU quota; more threads than the quota only time-slice the same 16 CPUs)
     ncpu = max(1, min(affinity, int(quota))) if quota else affinity
     threads = args.cpu_threads if args.cpu_threads > 0 else ncpu
-    sc = pyoracle.OracleScene(objload.load_scene(assets.scene_files(args.scene)))
+    sc = pyoracle.OracleScene(objload.load_scene(scene_files(args.scene)))
     w, h = args.width, args.height
     t = time.perf_counter()
     _, _, c1 = sc.render(cam_floats, w, h, 1, args.bounces, seed=args.seed, nthreads=threads)
@@ -399,6 +444,33 @@ def main(argv=None):
     return run(args)
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: all arrays together stay below 64 MB, .npy headers included
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir, frames, budget: int = DUMP_BUDGET_BYTES):
+    """Write each (name, H x W x C array) as out_dir/<name>.npy in float32.  An array gets what is left of the budget,
+    less up to a quarter of it for every array still to come (the headline frame's 44.2 MB of linear sums fit whole);
+    one that does not fit is written as a (pixels, C) array of its pixels at sorted positions drawn without replacement
+    by a generator seeded with DUMP_SAMPLE_SEED, so the same frame size and budget always pick the same pixels."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    left = int(budget)
+    for i, (name, a) in enumerate(frames):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        cap = left - sum(min(4 * b.size, left // 4) for _, b in frames[i + 1:])
+        if a.nbytes > cap:
+            px = a.reshape(-1, a.shape[-1])
+            keep = max(1, cap // (4 * px.shape[1]))
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], size=keep, replace=False))
+            a = np.ascontiguousarray(px[idx])
+            log(f"[dump] {name}: {keep} of {px.shape[0]} pixels (seed {DUMP_SAMPLE_SEED})")
+        np.save(out_dir / f"{name}.npy", a)
+        left -= a.nbytes
+    log(f"[dump] {budget - left} bytes in {out_dir}")
+
+
 def shard_spp_of(args) -> int:
     g, n = args.share
     base, rem = divmod(args.spp, n)
@@ -411,10 +483,13 @@ def run(args) -> int:
 
     crt = importlib.import_module(args.rig)
     rehearsal = args.rig != "crt_amd"
-    from crt_amd import assets
     from crt_amd.dist import ShardedFrameRenderer, dist_env, gather_frame_timings
 
     rank, local, world = dist_env()
+    # what takes runs of its own is --full's; a plain run times the frames and reports them
+    do_count = args.full and not args.no_count
+    do_parity = args.full and not args.no_parity
+    do_cpu = args.full and not args.no_cpu_baseline
     on_gpu = getattr(crt, "DEVICE_TYPE", "cuda") == "cuda"
     if on_gpu:
         ngpu = torch.cuda.device_count()
@@ -461,9 +536,9 @@ def run(args) -> int:
         return [int(v) for v in t.tolist()]
 
     W, H = args.width, args.height
-    files = assets.scene_files(args.scene) if rank == 0 else None
+    files = scene_files(args.scene) if rank == 0 else None
     barrier()
-    files = assets.scene_files(args.scene)
+    files = scene_files(args.scene)
     t = time.perf_counter()
     hs = crt.HostScene(files, build_device=None if args.host_build else local)
     t_load = time.perf_counter() - t
@@ -477,7 +552,7 @@ def run(args) -> int:
         bvh_desc = (f"rebuilt {args.bvh_width}-wide SAH, leaf<={args.leaf_size}, C_trav={args.traversal_cost:g}"
                     + (", spatial splits" if args.spatial_splits else ""))
     t_scene = time.perf_counter() - t
-    if ref_scene is None:   # the reference-BVH scene of the parity check, outside the timed set-up
+    if ref_scene is None and do_parity and world == 1:   # the parity check's reference-BVH scene, after the timed set-up
         ref_scene = hs.upload(local)
     st = scene.stats()
     counts = hs.counts()
@@ -550,7 +625,9 @@ def run(args) -> int:
     assert len(frame_t) == args.steps, f"{len(frame_t)} frame timings for {args.steps} timed frames"
     # the reduced N-rank frame (rank 0 holds it) before any later launch reuses the framebuffer: the statistical parity
     # field compares it with the 1-GPU frame
-    lin_frame = fr.linear() if rank == 0 and world > 1 and not args.no_parity else None
+    lin_frame = fr.linear() if rank == 0 and world > 1 and do_parity else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("linear", fr.linear()), ("rgba8", r.rgba8())])
     kernel_ms = [f[0] for f in frame_t]
     kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
     kernel_ms_max = allreduce_max(max(kernel_ms))
@@ -580,31 +657,33 @@ def run(args) -> int:
     # WindowManager.h:87): the scene's load + BVH builds + upload measured above, plus a fresh renderer (its own
     # curand_init, no cached state), one frame with the collective and the resolve, and the RGBA8 D2H readback on
     # rank 0, max over ranks
-    barrier()
-    sync()
-    t = time.perf_counter()
-    r_e2e = make_renderer()
-    fr_e2e = make_frame(r_e2e)
-    fr_e2e.render()
-    if rank == 0:
-        r_e2e.rgba8()
-    sync()
-    t_frame_e2e = allreduce_max(time.perf_counter() - t)
-    t_rb = time.perf_counter()
-    if rank == 0:
-        r_e2e.rgba8()
-    t_readback = time.perf_counter() - t_rb
-    del fr_e2e, r_e2e
-    end_to_end = {"end_to_end_s": round(t_scene + t_frame_e2e, 4),
-                  "scene_load_build_upload_s": round(t_scene, 4),
-                  "fresh_renderer_frame_readback_s": round(t_frame_e2e, 4),
-                  "rgba8_readback_ms": round(t_readback * 1e3, 3),
-                  "runtime_init_s": round(t_runtime, 4),
-                  "note": "scene: OBJ load + mesh BVH build + rebuilt-tree build + upload (after the HIP runtime's "
-                          "start-up, runtime_init_s); then a new renderer "
-                          "(curand_init by the jump kernel, not the cache) + one frame + collective + resolve + "
-                          "RGBA8 D2H to host (rank 0); max over ranks"}
-    log_r(f"[e2e] {end_to_end}")
+    end_to_end = None
+    if args.full:
+        barrier()
+        sync()
+        t = time.perf_counter()
+        r_e2e = make_renderer()
+        fr_e2e = make_frame(r_e2e)
+        fr_e2e.render()
+        if rank == 0:
+            r_e2e.rgba8()
+        sync()
+        t_frame_e2e = allreduce_max(time.perf_counter() - t)
+        t_rb = time.perf_counter()
+        if rank == 0:
+            r_e2e.rgba8()
+        t_readback = time.perf_counter() - t_rb
+        del fr_e2e, r_e2e
+        end_to_end = {"end_to_end_s": round(t_scene + t_frame_e2e, 4),
+                      "scene_load_build_upload_s": round(t_scene, 4),
+                      "fresh_renderer_frame_readback_s": round(t_frame_e2e, 4),
+                      "rgba8_readback_ms": round(t_readback * 1e3, 3),
+                      "runtime_init_s": round(t_runtime, 4),
+                      "note": "scene: OBJ load + mesh BVH build + rebuilt-tree build + upload (after the HIP runtime's "
+                              "start-up, runtime_init_s); then a new renderer "
+                              "(curand_init by the jump kernel, not the cache) + one frame + collective + resolve + "
+                              "RGBA8 D2H to host (rank 0); max over ranks"}
+        log_r(f"[e2e] {end_to_end}")
 
     if args.save_ppm and rank == 0:
         img = r.rgba8()
@@ -615,7 +694,7 @@ def run(args) -> int:
     # exact work counts for the same launch (deterministic: same seed, same shard)
     roofline = algorithmic = None
     work = None
-    if not args.no_count:
+    if do_count:
         r.init_rand(args.seed, fr.subseq)
         r.render(scene, fr.spp, args.bounces, count_work=True)
         r.synchronize()
@@ -648,7 +727,9 @@ def run(args) -> int:
                        "note": "32*box + 36*tri + 20*sphere + 16*ray + 60*pixel bytes; 24*box + 54*tri + 30*sphere "
                                "+ 100*ray f32 ops (DESIGN.md §5); the %.1f MB scene is L2/Infinity-Cache resident"
                                % (st["device_bytes"] / 1e6)}
-    ec, ec_rule = roofline_counters(workload_key(args, fr.spp), kname, workload_key(args, args.spp))
+    ec = ec_rule = None
+    if args.full:
+        ec, ec_rule = roofline_counters(workload_key(args, fr.spp), kname, workload_key(args, args.spp))
     if ec is not None:
         # the counters are the main render kernel's alone, so they are divided by its own time (HIP events around that
         # launch only), not by the whole render's, which includes the cost probe and the tile sort
@@ -660,12 +741,12 @@ def run(args) -> int:
                         if fr.spp != args.spp else "the whole frame",
                         kernel_ms_note=f"HIP events around the main render launch, average of the {len(hist)} timed "
                                        "frames (probe and tile sort excluded)")
-    else:
+    elif args.full:
         log_r(f"[roofline] no committed counter summary for {workload_key(args, fr.spp)} / {kname}: roofline null")
 
     # parity of the timed configuration against the reference's own BVH on the same frame (N=1)
     parity = None
-    if world == 1 and args.bvh == "rebuilt" and not args.no_parity:
+    if world == 1 and args.bvh == "rebuilt" and do_parity:
         import numpy as np
         r.init_rand(args.seed, fr.subseq)
         r.render(scene, fr.spp, args.bounces)
@@ -698,7 +779,7 @@ def run(args) -> int:
         log_r(f"[parity] N={world} vs the 1-GPU frame: {parity}")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and do_cpu:
         cpu = cpu_baseline(args, crt.camera_floats(cam), log)
 
     ms_per_step = elapsed / args.steps * 1e3
@@ -724,8 +805,11 @@ def run(args) -> int:
             "render_phases_ms_last_frame": {k: round(v, 3) for k, v in phases.items()},
             "render_phases_ms_avg": {k: round(v, 3) for k, v in phases_avg.items()},
             "roofline": roofline, "algorithmic": algorithmic, "cpu_baseline": cpu, "parity": parity,
-            "setup": setup, "end_to_end": end_to_end, "end_to_end_s": end_to_end["end_to_end_s"],
+            "setup": setup, "end_to_end": end_to_end, "end_to_end_s": end_to_end and end_to_end["end_to_end_s"],
+            "full": args.full,
         }
+        if args.dump_outputs:
+            out["outputs"] = str(Path(args.dump_outputs))
         if dist_t is not None:
             # N > 1 (or a one-rank process group): each rank's render and the time its stream spent in the collective
             out.update(render_ms_per_rank=dist_t["render_ms_per_rank"], reduce_ms=dist_t["reduce_ms"],

@@ -7,7 +7,6 @@ one after another in this process and summed on the host: with 2 ranks bit for b
 to within one rounding of the sum order.  The resolved RGBA8 is writeColor of the reduced sums.
 """
 import os
-import socket
 import subprocess
 import sys
 from pathlib import Path
@@ -24,18 +23,13 @@ REPO = Path(__file__).resolve().parents[1]
 W, H, SPP = 160, 90, 24
 
 
-def _port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _run(tmp_path, world, reduce_op, spp=SPP, mode="spp", backend="gloo"):
     out = str(tmp_path / f"frame_{world}_{reduce_op}_{mode}_{backend}")
+    # rendezvous on port 0, as bench.py's own launch: the launcher's store binds a free port itself, so none is picked
+    # here and released again for another process to take first
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-           "--master-addr=127.0.0.1", f"--master-port={_port()}", str(REPO / "tests" / "helpers" / "dist_frame_worker.py"),
+           "--rdzv-backend=c10d", "--rdzv-endpoint=127.0.0.1:0", f"--rdzv-id=frame-{os.getpid()}",
+           "--local-addr=127.0.0.1", str(REPO / "tests" / "helpers" / "dist_frame_worker.py"),
            out, str(W), str(H), str(spp), reduce_op, mode, backend]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(os.environ, OMP_NUM_THREADS="2"))
     assert p.returncode == 0, p.stderr[-4000:]
@@ -105,7 +99,7 @@ def test_bench_gpus_2_launches_two_ranks_with_statistical_parity():
     env["OMP_NUM_THREADS"] = "2"
     p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
                         "--width", "320", "--height", "180", "--spp", "64", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, env=env)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, p.stderr[-4000:]
     out = json.loads(p.stdout.strip().splitlines()[-1])
     assert out["n_gpus"] == 2 and "rehearsal" not in out

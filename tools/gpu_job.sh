@@ -24,16 +24,16 @@ case $MODE in
 check)
   timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $R/$OUT/pytest_gpu.log 2>&1
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $R/$OUT/smoke.log 2>&1
-  timeout -k 10 400 python3 bench.py > $R/$OUT/bench.log 2>&1
+  timeout -k 10 400 python3 bench.py --full > $R/$OUT/bench.log 2>&1
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof -o bench -- \
-      python3 $R/bench.py --no-cpu-baseline --no-parity > $R/$OUT/bench_prof.log 2>&1
+      python3 $R/bench.py --full --no-cpu-baseline --no-parity > $R/$OUT/bench_prof.log 2>&1
   ;;
 bench)
-  timeout -k 10 600 python3 bench.py "$@" > $R/$OUT/bench.log 2>&1
+  timeout -k 10 600 python3 bench.py --full "$@" > $R/$OUT/bench.log 2>&1
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof -o bench -- \
-      python3 $R/bench.py --no-cpu-baseline --no-parity "$@" > $R/$OUT/bench_prof.log 2>&1
+      python3 $R/bench.py --full --no-cpu-baseline --no-parity "$@" > $R/$OUT/bench_prof.log 2>&1
   ;;
 ab)
   LIBB=$1; N=${2:-2}; shift 2
