@@ -208,7 +208,14 @@ typedef struct crt_scene_options {
 int  crt_scene_export(const crt_scene_desc* desc, const crt_scene_options* opts, float* nodes, float* prims,
                       int32_t* rank_code, int64_t info[10]);
 int  crt_scene_create(const crt_scene_desc* desc, int device, crt_scene** out);
-/* crt_scene_create with options (NULL = defaults = CRT_BVH_REFERENCE). */
+/* crt_scene_create with options (NULL = defaults = CRT_BVH_REFERENCE).
+ * A scene needs at least one object; there is no sky-only scene.  n_objects == 0 is CRT_ERR_INVALID_ARGUMENT: "scene
+ * has no BVH nodes" when n_scene_nodes is 0 as well, "scene leaf object out of range" when scene_nodes still holds a
+ * leaf (every leaf must name an object below n_objects).  Any number of spheres is accepted.  CRT_BVH_REBUILT, width 4: up to 8
+ * spheres are tested once per ray behind the reference's own box test for them; with more, the spheres of radius
+ * below 1 go into the tree's leaves and those of radius >= 1 stay per ray, of which there may then be at most 8
+ * (more: CRT_ERR_INVALID_ARGUMENT; width 2 takes any number).  Only per ray is a sphere's reference box replayed,
+ * which a large sphere needs: its f32 roots can land outside its own box. */
 int  crt_scene_create_ex(const crt_scene_desc* desc, int device, const crt_scene_options* opts, crt_scene** out);
 int  crt_scene_get_stats(const crt_scene* scene, crt_scene_stats* out);
 void crt_scene_destroy(crt_scene* scene);

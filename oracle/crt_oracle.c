@@ -133,7 +133,10 @@ static int box_hit(const Box* b, const Ray* r, Iv rt) {                         
 }
 
 /* --------------------------------------------------------------- HitInfo */
-typedef struct { V3 p, n; uint32_t mat; float t; int front; } Hit;   /* HitInfo.cuh:6-17 */
+typedef struct {
+    V3 p, n; uint32_t mat; float t; int front;                        /* HitInfo.cuh:6-17 */
+    int obj, prim;   /* oracle only (oracle_trace_rays): mesh index or -1 - sphere index, triangle after the build permutation */
+} Hit;
 static inline void set_face_normal(Hit* h, const Ray* r, V3 outward) {
     h->front = dot3(r->d, outward) < 0;
     h->n = h->front ? outward : vneg(outward);
@@ -308,6 +311,7 @@ typedef struct {
     uint32_t* idx;          /* m_Indices + indexOffset (permuted in place by the builder) */
     int32_t* fmat;          /* m_FaceMaterialIds + faceMatOffset (permuted) */
     uint32_t n_verts, n_idx, matid_off;
+    int id;                 /* index in Scene::meshes (oracle_trace_rays) */
     Box box;
     Node* bvh;
     int n_nodes;
@@ -429,6 +433,7 @@ static int tri_hit(const Mesh* m, const Ray* r, V3 v0, V3 v1, V3 v2, Iv rt, Hit*
     rec->t = t;
     rec->p = ray_at(r, t);
     rec->mat = (uint32_t)(m->fmat[base / 3] + (int32_t)m->matid_off);
+    rec->obj = m->id; rec->prim = base / 3;
     V3 n = unitv(cross3(e1, e2));
     set_face_normal(rec, r, n);
     return 1;
@@ -464,9 +469,9 @@ static int mesh_hit(const Mesh* m, const Ray* r, Iv rt, Hit* rec, Counters* cn) 
 
 /* ---------------------------------------------------------------- Sphere */
 /* Core/Sphere.cuh:6-53 */
-typedef struct { V3 c; float r, r2; uint32_t mat; Box box; } Sphere;
+typedef struct { V3 c; float r, r2; uint32_t mat; Box box; int id; } Sphere;
 static Sphere make_sphere(V3 c, float rad, int mat) {                                        /* :20-25 */
-    Sphere s; s.c = c; s.r = rad; s.r2 = rad * rad; s.mat = (uint32_t)mat;
+    Sphere s; s.c = c; s.r = rad; s.r2 = rad * rad; s.mat = (uint32_t)mat; s.id = 0;
     V3 rv = v3(rad, rad, rad);
     s.box = box_from_points(vsub(c, rv), vadd(c, rv));
     return s;
@@ -487,6 +492,7 @@ static int sphere_hit(const Sphere* sp, const Ray* r, Iv rt, Hit* rec) {        
     rec->t = root;
     rec->p = ray_at(r, rec->t);
     rec->mat = sp->mat;
+    rec->obj = -1 - sp->id; rec->prim = 0;
     V3 on = vdiv(vsub(rec->p, sp->c), sp->r);
     set_face_normal(rec, r, on);
     return 1;
@@ -501,7 +507,7 @@ typedef struct {
     uint32_t* idx;
     int32_t* fmat;
     int n_spheres;
-    Sphere spheres[2];
+    Sphere* spheres;
     int n_obj;
     Obj objs[500];
     int n_mat;
@@ -683,13 +689,15 @@ EXPORT void oracle_rng_draw(uint32_t* state6, int n, uint32_t* out_u32, float* o
 /* mesh_info: per mesh 6 u32: vertexOffset, vertexCount, indexOffset, indexCount, faceMatOffset, matIDOffset
  * (SceneManager.h:125-195).  matdata: per material 9 floats: type, albedo3, emission3, roughness, ior
  * (Material.cuh:16-47).  Returns 0 on success. */
-EXPORT int oracle_scene_create(int n_meshes, const float* positions, unsigned long long n_vert_total,
-                               const uint32_t* indices, unsigned long long n_idx_total,
-                               const int32_t* facemat, unsigned long long n_face_total,
-                               const uint32_t* mesh_info, int n_mat, const float* matdata, void** out) {
+/* The part of createRandomWorld (CUDAKernels.h:56-84) both entry points share: materials and meshes. */
+static int scene_base(int n_meshes, const float* positions, unsigned long long n_vert_total,
+                      const uint32_t* indices, unsigned long long n_idx_total,
+                      const int32_t* facemat, unsigned long long n_face_total,
+                      const uint32_t* mesh_info, int n_mat, const float* matdata, Scene** out) {
     build_seq_tables();
     Scene* sc = (Scene*)calloc(1, sizeof(Scene));
     if (!sc) return -1;
+    *out = sc;
     sc->n_meshes = n_meshes;
     sc->meshes = (Mesh*)calloc((size_t)(n_meshes > 0 ? n_meshes : 1), sizeof(Mesh));
     sc->verts = (float*)malloc(sizeof(float) * 3 * (n_vert_total ? n_vert_total : 1));
@@ -698,7 +706,6 @@ EXPORT int oracle_scene_create(int n_meshes, const float* positions, unsigned lo
     memcpy(sc->verts, positions, sizeof(float) * 3 * n_vert_total);
     memcpy(sc->idx, indices, sizeof(uint32_t) * n_idx_total);
     memcpy(sc->fmat, facemat, sizeof(int32_t) * n_face_total);
-    /* createRandomWorld (CUDAKernels.h:56-84) */
     for (int i = 0; i < n_mat && sc->n_mat < 500; i++) {            /* createMaterialsKernel :28-54 */
         const float* d = matdata + 9 * i;
         Mat m; memset(&m, 0, sizeof m);
@@ -718,10 +725,28 @@ EXPORT int oracle_scene_create(int n_meshes, const float* positions, unsigned lo
         m->n_idx = mi[3];
         m->fmat = sc->fmat + mi[4];
         m->matid_off = mi[5];
+        m->id = i;
         int rc = mesh_build(m);
         if (rc) return rc;
+    }
+    return 0;
+}
+
+EXPORT void oracle_scene_destroy(void* p);
+
+EXPORT int oracle_scene_create(int n_meshes, const float* positions, unsigned long long n_vert_total,
+                               const uint32_t* indices, unsigned long long n_idx_total,
+                               const int32_t* facemat, unsigned long long n_face_total,
+                               const uint32_t* mesh_info, int n_mat, const float* matdata, void** out) {
+    Scene* sc = NULL;
+    int rc = scene_base(n_meshes, positions, n_vert_total, indices, n_idx_total, facemat, n_face_total, mesh_info,
+                        n_mat, matdata, &sc);
+    if (rc) { oracle_scene_destroy(sc); return rc; }
+    /* createRandomWorld (CUDAKernels.h:56-84) */
+    for (int i = 0; i < n_meshes; i++) {
         sc->objs[sc->n_obj].is_mesh = 1; sc->objs[sc->n_obj].index = i; sc->n_obj++;
     }
+    sc->spheres = (Sphere*)calloc(2, sizeof(Sphere));
     Mat g; memset(&g, 0, sizeof g); g.type = MT_LAMBERTIAN; g.albedo = v3(0.5f, 0.5f, 0.5f);
     int gi = sc->n_mat; sc->mats[sc->n_mat++] = g;
     sc->spheres[0] = make_sphere(v3(0, -1000, 0), 999, gi);
@@ -729,17 +754,79 @@ EXPORT int oracle_scene_create(int n_meshes, const float* positions, unsigned lo
     Mat mt; memset(&mt, 0, sizeof mt); mt.type = MT_METAL; mt.albedo = v3((float)0.7, (float)0.6, (float)0.5); mt.roughness = 0.0f;
     int mti = sc->n_mat; sc->mats[sc->n_mat++] = mt;
     sc->spheres[1] = make_sphere(v3((float)0.2, (float)0.2, 0), 0.05f, mti);
+    sc->spheres[1].id = 1;
     sc->objs[sc->n_obj].is_mesh = 0; sc->objs[sc->n_obj].index = 1; sc->n_obj++;
     sc->n_spheres = 2;
     build_scene_bvh(sc);
     *out = sc;
     return 0;
 }
+
+/* oracle_scene_create with the caller's world instead of createRandomWorld's two spheres: n_spheres spheres of
+ * 5 floats (centre3, radius, material index as a float), n_sphere_mat more material rows appended after the
+ * meshes' (same 9-float rows), and the HittableList order as n_obj pairs (kind, index), kind 0 = mesh, 1 = sphere
+ * (crt_object_kind).  Returns -3 for an empty or oversized object list or an index out of range. */
+EXPORT int oracle_scene_create_ex(int n_meshes, const float* positions, unsigned long long n_vert_total,
+                                  const uint32_t* indices, unsigned long long n_idx_total,
+                                  const int32_t* facemat, unsigned long long n_face_total,
+                                  const uint32_t* mesh_info, int n_mat, const float* matdata,
+                                  int n_spheres, const float* spheres, int n_sphere_mat, const float* sphere_matdata,
+                                  int n_obj, const int32_t* order, void** out) {
+    if (n_obj < 1 || n_obj > 500 || n_spheres < 0 || n_mat + n_sphere_mat > 500) return -3;
+    for (int i = 0; i < n_obj; i++) {
+        int kind = order[2 * i], index = order[2 * i + 1];
+        if ((kind != 0 && kind != 1) || index < 0 || index >= (kind == 0 ? n_meshes : n_spheres)) return -3;
+    }
+    Scene* sc = NULL;
+    int rc = scene_base(n_meshes, positions, n_vert_total, indices, n_idx_total, facemat, n_face_total, mesh_info,
+                        n_mat, matdata, &sc);
+    if (rc) { oracle_scene_destroy(sc); return rc; }
+    for (int i = 0; i < n_sphere_mat; i++) {
+        const float* d = sphere_matdata + 9 * i;
+        Mat m; memset(&m, 0, sizeof m);
+        m.type = (int)d[0];
+        m.albedo = v3(d[1], d[2], d[3]);
+        m.emission = v3(d[4], d[5], d[6]);
+        m.roughness = d[7] < 1.f ? d[7] : 1.f;
+        m.ior = d[8];
+        sc->mats[sc->n_mat++] = m;
+    }
+    sc->spheres = (Sphere*)calloc((size_t)(n_spheres > 0 ? n_spheres : 1), sizeof(Sphere));
+    for (int i = 0; i < n_spheres; i++) {
+        const float* q = spheres + 5 * i;
+        sc->spheres[i] = make_sphere(v3(q[0], q[1], q[2]), q[3], (int)q[4]);
+        sc->spheres[i].id = i;
+    }
+    sc->n_spheres = n_spheres;
+    for (int i = 0; i < n_obj; i++) { sc->objs[i].is_mesh = order[2 * i] == 0; sc->objs[i].index = order[2 * i + 1]; }
+    sc->n_obj = n_obj;
+    build_scene_bvh(sc);
+    *out = sc;
+    return 0;
+}
+
+/* scene_hit over [0.001, inf) for n rays (o, d: 3 floats each), the closest-hit query of rayColor
+ * (CUDAKernels.h:123).  t_out: t, or -1 on a miss.  prim_out: 2 ints per ray, (mesh index, triangle after the
+ * mesh build's permutation) or (-1 - sphere index, 0); untouched on a miss. */
+EXPORT void oracle_trace_rays(const void* scene, const float* o, const float* d, int n, float* t_out,
+                              int32_t* prim_out) {
+    const Scene* sc = (const Scene*)scene;
+    Counters cn; memset(&cn, 0, sizeof cn);
+    for (int i = 0; i < n; i++) {
+        Ray r; r.o = v3(o[3 * i], o[3 * i + 1], o[3 * i + 2]); r.d = v3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+        Hit rec;
+        if (scene_hit(sc, &r, iv(0.001f, INFINITY), &rec, &cn)) {
+            t_out[i] = rec.t; prim_out[2 * i] = rec.obj; prim_out[2 * i + 1] = rec.prim;
+        } else {
+            t_out[i] = -1.f;
+        }
+    }
+}
 EXPORT void oracle_scene_destroy(void* p) {
     Scene* sc = (Scene*)p;
     if (!sc) return;
     for (int i = 0; i < sc->n_meshes; i++) free(sc->meshes[i].bvh);
-    free(sc->meshes); free(sc->verts); free(sc->idx); free(sc->fmat); free(sc->snodes); free(sc);
+    free(sc->meshes); free(sc->verts); free(sc->idx); free(sc->fmat); free(sc->snodes); free(sc->spheres); free(sc);
 }
 /* Node dump: per node 6 floats box + 5 ints (left,right,obj_index,obj_count,is_leaf). which=-1: scene BVH. */
 EXPORT int oracle_scene_nodes(void* p, int which, float* boxes, int32_t* ints) {

@@ -34,6 +34,10 @@ def lib():
         P, u64, i32, f32p = C.c_void_p, C.c_ulonglong, C.c_int, C.c_void_p
         L.oracle_scene_create.argtypes = [i32, P, u64, P, u64, P, u64, P, i32, P, C.POINTER(C.c_void_p)]
         L.oracle_scene_create.restype = i32
+        L.oracle_scene_create_ex.argtypes = [i32, P, u64, P, u64, P, u64, P, i32, P, i32, P, i32, P, i32, P,
+                                             C.POINTER(C.c_void_p)]
+        L.oracle_scene_create_ex.restype = i32
+        L.oracle_trace_rays.argtypes = [P, P, P, i32, P, P]
         L.oracle_scene_destroy.argtypes = [P]
         L.oracle_scene_nodes.argtypes = [P, i32, P, P]
         L.oracle_scene_nodes.restype = i32
@@ -60,9 +64,14 @@ def _p(a: np.ndarray):
 
 
 class OracleScene:
-    """Reference createRandomWorld + BVH builds over a loaded scene (objload.LoadedScene)."""
+    """Reference createRandomWorld + BVH builds over a loaded scene (objload.LoadedScene).
 
-    def __init__(self, loaded):
+    spheres=None: createRandomWorld's own two spheres after the meshes (oracle_scene_create).  Otherwise the
+    caller's world (oracle_scene_create_ex): spheres = (array [n, 5] of centre3, radius, material index,
+    array [m, 9] of material rows appended after the loaded ones), order = the HittableList as (kind, index)
+    pairs, kind 0 = mesh, 1 = sphere (default: meshes, then spheres)."""
+
+    def __init__(self, loaded, spheres=None, order=None):
         L = lib()
         self._keep = [np.ascontiguousarray(loaded.positions, np.float32),
                       np.ascontiguousarray(loaded.indices, np.uint32),
@@ -71,12 +80,36 @@ class OracleScene:
                       np.ascontiguousarray(loaded.matdata, np.float32)]
         pos, idx, fm, info, mats = self._keep
         h = C.c_void_p()
-        rc = L.oracle_scene_create(len(info), _p(pos), len(pos), _p(idx), len(idx), _p(fm), len(fm),
-                                   _p(info), len(mats), _p(mats), C.byref(h))
+        if spheres is None and order is None:
+            rc = L.oracle_scene_create(len(info), _p(pos), len(pos), _p(idx), len(idx), _p(fm), len(fm),
+                                       _p(info), len(mats), _p(mats), C.byref(h))
+            what = "oracle_scene_create"
+        else:
+            sph, smat = spheres if spheres is not None else (np.zeros((0, 5)), np.zeros((0, 9)))
+            sph = np.ascontiguousarray(sph, np.float32).reshape(-1, 5)
+            smat = np.ascontiguousarray(smat, np.float32).reshape(-1, 9)
+            if order is None:
+                order = [(0, i) for i in range(len(info))] + [(1, i) for i in range(len(sph))]
+            order = np.ascontiguousarray(order, np.int32).reshape(-1, 2)
+            rc = L.oracle_scene_create_ex(len(info), _p(pos), len(pos), _p(idx), len(idx), _p(fm), len(fm),
+                                          _p(info), len(mats), _p(mats), len(sph), _p(sph), len(smat), _p(smat),
+                                          len(order), _p(order), C.byref(h))
+            what = "oracle_scene_create_ex"
         if rc != 0:
-            raise RuntimeError(f"oracle_scene_create failed rc={rc}")
+            raise RuntimeError(f"{what} failed rc={rc}")
         self.h = h
         self.n_meshes = len(info)
+
+    def trace(self, o, d):
+        """scene_hit over [0.001, inf) per ray: (t [n] or -1, prim [n, 2] = (mesh, permuted triangle) or
+        (-1 - sphere, 0))."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        assert o.shape == d.shape
+        t = np.zeros(len(o), np.float32)
+        prim = np.zeros((len(o), 2), np.int32)
+        lib().oracle_trace_rays(self.h, _p(o), _p(d), len(o), _p(t), _p(prim))
+        return t, prim
 
     def __del__(self):
         if getattr(self, "h", None):

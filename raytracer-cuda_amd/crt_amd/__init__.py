@@ -127,20 +127,32 @@ class HostScene:
 
     def export(self, bvh: str = "reference", **options) -> dict:
         """The device arrays crt_scene_create_ex would upload (host only, crt_scene_export)."""
-        o = scene_options(bvh, **options)
-        d = self.desc()
-        info = (C.c_int64 * 10)()
-        check(_lib.hip().crt_scene_export(C.byref(d), C.byref(o), None, None, None, info), "crt_scene_export")
-        nodes = np.zeros((info[0], 4), np.float32)
-        prims = np.zeros((info[1], 4), np.float32)
-        rank_code = np.zeros(info[2], np.int32)
-        check(_lib.hip().crt_scene_export(C.byref(d), C.byref(o), _p(nodes), _p(prims), _p(rank_code), info),
-              "crt_scene_export")
-        keys = ("node_float4s", "prim_float4s", "ranks", "nodes_per_layout", "layouts", "width", "stack_bound",
-                "excluded", "sphere_first", "n_ray_spheres")
-        out = dict(zip(keys, (int(v) for v in info)))
-        out.update(nodes=nodes, prims=prims, rank_code=rank_code)
-        return out
+        return export_desc(self.desc(), bvh, **options)
+
+
+def export_desc(d: SceneDesc, bvh: str = "reference", **options) -> dict:
+    """crt_scene_export of any scene description (HostScene.desc() or a caller's own)."""
+    o = scene_options(bvh, **options)
+    info = (C.c_int64 * 10)()
+    check(_lib.hip().crt_scene_export(C.byref(d), C.byref(o), None, None, None, info), "crt_scene_export")
+    nodes = np.zeros((info[0], 4), np.float32)
+    prims = np.zeros((info[1], 4), np.float32)
+    rank_code = np.zeros(info[2], np.int32)
+    check(_lib.hip().crt_scene_export(C.byref(d), C.byref(o), _p(nodes), _p(prims), _p(rank_code), info),
+          "crt_scene_export")
+    keys = ("node_float4s", "prim_float4s", "ranks", "nodes_per_layout", "layouts", "width", "stack_bound",
+            "excluded", "sphere_first", "n_ray_spheres")
+    out = dict(zip(keys, (int(v) for v in info)))
+    out.update(nodes=nodes, prims=prims, rank_code=rank_code)
+    return out
+
+
+def create_scene(d: SceneDesc, device: int = 0, bvh: str = "reference", **options) -> "Scene":
+    """crt_scene_create_ex of any scene description (the caller keeps the arrays alive during the call)."""
+    o = scene_options(bvh, **options)
+    h = C.c_void_p()
+    check(_lib.hip().crt_scene_create_ex(C.byref(d), int(device), C.byref(o), C.byref(h)), "crt_scene_create_ex")
+    return Scene(h, device)
 
 
 def scene_options(bvh: str = "reference", leaf_size: int = 0, layouts: int = 0, traversal_cost: float = 0.0,

@@ -2753,6 +2753,13 @@ struct Rebuilt {
     int sphere_first = 0, n_ray_spheres = 0;   // width 4: spheres kept out of the tree (tested per ray)
     std::vector<float4> chain;                 // their reference scene-level leaf boxes (2 float4 per box)
     static constexpr int kMaxRaySpheres = 8;
+    // With more than kMaxRaySpheres spheres the small ones go into the tree's leaves, but a sphere of at least this
+    // radius stays per ray: only there is its reference scene-level box replayed (ray_spheres).  The f32 roots of
+    // Sphere::hit err by about ulp(r^2) / |oc . d|; for the radius-999 ground sphere that puts a spurious root of a
+    // ray leaving the surface above t = 0.001 while the reference's box test has already rejected the ray
+    // (tests/golden/ground_sphere_rays.json), and a leaf's padded box is too wide to reject it.  Below radius 1 the
+    // same needs a ray within 3e-5 rad of the tangent plane that also starts within 0.001 |d| of the box face.
+    static constexpr float kRaySphereRadius = 1.0f;
 
     // gpu_device >= 0: the binned-SAH tree is built on that GPU (crtx_build_sah_gpu, crt_bvh_build.hip)
     long spatial_splits = 0;   // SBVH: nodes cut by a plane, and primitive references in the leaves
@@ -2770,13 +2777,23 @@ struct Rebuilt {
         std::vector<int> ray_sph;
         std::vector<crt_sah::TriVerts> verts;
         if (spatial && width != 4) { err = "spatial splits need width 4"; return false; }
-        int n_sph = 0;
-        for (int p = 0; p < n; ++p) n_sph += (F.rank_code[F.rank_of[p]] & SPHERE_BIT) != 0;
-        const bool spheres_per_ray = width == 4 && n_sph <= kMaxRaySpheres;
+        int n_sph = 0, n_large = 0;
+        for (int p = 0; p < n; ++p)
+            if (F.rank_code[F.rank_of[p]] & SPHERE_BIT) {
+                ++n_sph;
+                n_large += F.reachable[p] && !(std::fabs(F.prims[3 * (size_t)p].w) < kRaySphereRadius);
+            }
+        const bool all_per_ray = width == 4 && n_sph <= kMaxRaySpheres;
+        if (width == 4 && !all_per_ray && n_large > kMaxRaySpheres) {
+            err = "more than 8 spheres of radius >= 1 among more than 8 spheres: large spheres are tested per ray, "
+                  "at most 8 of them (width 2 takes any number)";
+            return false;
+        }
         for (int p = 0; p < n; ++p) {
             const bool sphere = (F.rank_code[F.rank_of[p]] & SPHERE_BIT) != 0;
             if (!F.reachable[p]) { excluded += !sphere; continue; }
             const float4 f0 = F.prims[3 * p], f1 = F.prims[3 * p + 1], f2 = F.prims[3 * p + 2];
+            const bool spheres_per_ray = all_per_ray || (width == 4 && !(std::fabs(f0.w) < kRaySphereRadius));
             if (sphere && spheres_per_ray) {
                 // a per-ray sphere's hit point becomes a ray origin too: the same 2^60 bound as the tree's boxes
                 // (wide_boxes: |o| * 2^64 must stay finite)

@@ -6,11 +6,18 @@
   the brute-force closest hit (t, then the higher reference rank) for random rays — i.e. the padded
   boxes never cull a hit and the rank rule reproduces the reference's tie-breaking.
 """
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 
 import crt_amd
 from crt_amd import assets
+
+sys.path.insert(0, str(Path(__file__).resolve().parent / "helpers"))
+from bvh_emulation import (_best, _check_threaded, _check_wide, _i, _is_sphere, _prim_box, _prim_ranks,  # noqa: E402
+                           _prim_t, _sphere_all, _trace_wide)
 
 F32 = np.float32
 
@@ -23,18 +30,6 @@ def host_scene():
 @pytest.fixture(scope="module")
 def ref_export(host_scene):
     return host_scene.export("reference")
-
-
-def _i(a):
-    return np.asarray(a, np.float32).view(np.int32)
-
-
-def _prim_ranks(prims):
-    return _i(prims.reshape(-1, 3, 4)[:, 2, 2])
-
-
-def _is_sphere(prims):
-    return _i(prims.reshape(-1, 3, 4)[:, 2, 3]) == 1
 
 
 def test_reference_export_ranks(ref_export):
@@ -74,195 +69,6 @@ def test_rebuilt_structure(host_scene, ref_export, opts):
         _check_wide(e, prims)
     else:
         _check_threaded(e, prims)
-
-
-def _prim_box(rec):
-    if _i(rec[2, 3]) == 1:
-        c, r = rec[0, :3], abs(rec[0, 3])
-        return c - r, c + r
-    v0 = rec[0, :3]
-    e1 = np.array([rec[0, 3], rec[1, 0], rec[1, 1]], np.float32)
-    e2 = np.array([rec[1, 2], rec[1, 3], rec[2, 0]], np.float32)
-    pts = np.stack([v0, v0 + e1, v0 + e2])
-    return pts.min(0), pts.max(0)
-
-
-def _check_wide(e, prims):
-    nodes = e["nodes"].reshape(-1, 8, 4)
-    n = len(nodes)
-    assert n == e["nodes_per_layout"]
-    seen = np.zeros(len(prims), np.int32)
-    parent_of = {0: None}
-    for i in range(n):
-        q = nodes[i]
-        fc, meta, lf, counts = _i(q[6])
-        n_int, n_slots = meta & 0xFF, meta >> 8
-        assert 0 <= n_int <= n_slots <= 4
-        off = 0
-        for s in range(4):
-            lo = np.array([q[0, s], q[2, s], q[4, s]])
-            hi = np.array([q[1, s], q[3, s], q[5, s]])
-            c = (counts >> (8 * s)) & 0xFF
-            if s >= n_slots:
-                assert (lo == 1e30).all() and (hi == 1e30).all() and c == 0
-            elif s < n_int:
-                assert c == 0
-                child = fc + s
-                assert 0 < child < n and child not in parent_of
-                parent_of[child] = (i, lo, hi)
-            else:
-                assert c > 0
-                for p in range(lf + off, lf + off + c):
-                    seen[p] += 1
-                    plo, phi = _prim_box(prims[p])
-                    assert (plo > lo).all() and (phi < hi).all(), "leaf box must strictly enclose (padding)"
-                off += c
-    rs = slice(e["sphere_first"], e["sphere_first"] + e["n_ray_spheres"])
-    assert _is_sphere(e["prims"])[rs].all(), "per-ray list holds spheres only"
-    seen[rs] += 1
-    assert (seen == 1).all(), "every primitive in exactly one leaf or the per-ray sphere list"
-    assert len(parent_of) == n
-    # child node boxes inside their parent's slot box
-    for child, pr in parent_of.items():
-        if pr is None:
-            continue
-        _, lo, hi = pr
-        q = nodes[child]
-        meta = _i(q[6])[1]
-        for s in range(meta >> 8):
-            assert q[0, s] >= lo[0] and q[2, s] >= lo[1] and q[4, s] >= lo[2]
-            assert q[1, s] <= hi[0] and q[3, s] <= hi[1] and q[5, s] <= hi[2]
-    # stack bound = max over root paths of the branching nodes (one entry per node), recomputed independently
-    bound = np.zeros(n, np.int64)
-    for i in range(n - 1, -1, -1):
-        fc, meta = _i(nodes[i, 6])[:2]
-        m = meta & 0xFF
-        bound[i] = (max(bound[fc + s] for s in range(m)) if m else 0) + (1 if m >= 2 else 0)
-    assert e["stack_bound"] == bound[0] + 1
-
-
-def _check_threaded(e, prims):
-    nodes = e["nodes"].reshape(e["layouts"], -1, 2, 4)
-    seen = np.zeros(len(prims), np.int32)
-    for lay in range(e["layouts"]):
-        L = nodes[lay]
-        cnt = np.zeros(len(prims), np.int32)
-        for i in range(len(L)):
-            a, b = _i(L[i, 1, 2:])
-            if b == -1:
-                assert i < a <= len(L)
-            elif b >= 1 << 30:
-                cnt[b - (1 << 30)] += 1
-            else:
-                cnt[b:b + a] += 1
-        assert (cnt == 1).all()
-        seen += cnt
-    assert (seen == e["layouts"]).all()
-
-
-# ---------------------------------------------------------------- traversal semantics
-def _mt_all(prims, o, d, tmax):
-    """Möller–Trumbore over all triangle records, float32 with the kernel's operation order."""
-    f0, f1, f2 = prims[:, 0], prims[:, 1], prims[:, 2]
-    v0 = f0[:, :3]
-    e1 = np.stack([f0[:, 3], f1[:, 0], f1[:, 1]], 1)
-    e2 = np.stack([f1[:, 2], f1[:, 3], f2[:, 0]], 1)
-
-    def cross(u, v):
-        return np.stack([u[..., 1] * v[..., 2] - u[..., 2] * v[..., 1], u[..., 2] * v[..., 0] - u[..., 0] * v[..., 2],
-                         u[..., 0] * v[..., 1] - u[..., 1] * v[..., 0]], -1)
-
-    def dot(u, v):
-        return (u[..., 0] * v[..., 0] + u[..., 1] * v[..., 1]) + u[..., 2] * v[..., 2]
-
-    with np.errstate(all="ignore"):
-        dd = np.broadcast_to(d, e2.shape)
-        h = cross(dd, e2)
-        det = dot(e1, h)
-        ok = ~(np.abs(det) < F32(1e-8))
-        f = F32(1) / det
-        s = o - v0
-        u = f * dot(s, h)
-        ok &= ~((u < 0) | (u > 1))
-        q = cross(s, e1)
-        v = f * dot(dd, q)
-        ok &= ~((v < 0) | ((u + v) > 1))
-        t = f * dot(e2, q)
-        ok &= ~((t < F32(0.001)) | (t > tmax))
-    return np.where(ok, t, -1).astype(np.float32)
-
-
-def _sphere_all(prims, o, d, tmax):
-    f0, f1 = prims[:, 0], prims[:, 1]
-    with np.errstate(all="ignore"):
-        oc = o - f0[:, :3]
-        qa = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
-        hb = (oc[:, 0] * d[0] + oc[:, 1] * d[1]) + oc[:, 2] * d[2]
-        qc = ((oc[:, 0] * oc[:, 0] + oc[:, 1] * oc[:, 1]) + oc[:, 2] * oc[:, 2]) - f1[:, 0]
-        disc = hb * hb - qa * qc
-        sq = np.sqrt(np.maximum(disc, 0)).astype(np.float32)
-        r1 = (-hb - sq) / qa
-        r2 = (-hb + sq) / qa
-        bad1 = (r1 < F32(0.001)) | (r1 > tmax)
-        bad2 = (r2 < F32(0.001)) | (r2 > tmax)
-        t = np.where(bad1, np.where(bad2, -1, r2), r1)
-    return np.where(disc < 0, -1, t).astype(np.float32)
-
-
-def _prim_t(prims, o, d, tmax):
-    sph = _i(prims[:, 2, 3]) == 1
-    t = _mt_all(prims, o, d, tmax)
-    if sph.any():
-        t[sph] = _sphere_all(prims[sph], o, d, tmax)
-    return t
-
-
-def _best(t, ranks, closest=np.float32(np.inf), hit=-1):
-    ok = t >= 0
-    if not ok.any():
-        return closest, hit
-    tm = t[ok].min()
-    r = ranks[ok][t[ok] == tm].max()
-    if tm < closest or (tm == closest and r > hit):
-        return tm, int(r)
-    return closest, hit
-
-
-def _trace_wide(e, prims, ranks, o, d):
-    nodes = e["nodes"].reshape(-1, 8, 4)
-    with np.errstate(all="ignore"):
-        inv = (F32(1) / d).astype(np.float32)
-    closest, hit = np.float32(np.inf), -1
-    rs = slice(e["sphere_first"], e["sphere_first"] + e["n_ray_spheres"])
-    if e["n_ray_spheres"]:
-        closest, hit = _best(_prim_t(prims[rs], o, d, np.float32(np.inf)), ranks[rs])
-    stack, node, steps = [], 0, 0
-    while node >= 0:
-        steps += 1
-        q = nodes[node]
-        with np.errstate(all="ignore"):
-            a = [(q[2 * k] - o[k]) * inv[k] for k in range(3)]
-            b = [(q[2 * k + 1] - o[k]) * inv[k] for k in range(3)]
-        t0 = np.fmax(np.fmax(np.fmin(a[0], b[0]), np.fmin(a[1], b[1])), np.fmax(np.fmin(a[2], b[2]), F32(0.001)))
-        t1 = np.fmin(np.fmin(np.fmax(a[0], b[0]), np.fmax(a[1], b[1])), np.fmin(np.fmax(a[2], b[2]), closest))
-        hitm = t0 < t1
-        fc, meta, lf, counts = _i(q[6])
-        n_int = meta & 0xFF
-        entry = closest
-        off = 0
-        for s in range(4):
-            c = (counts >> (8 * s)) & 0xFF
-            if s >= n_int and c and hitm[s]:
-                rng = slice(lf + off, lf + off + c)
-                closest, hit = _best(_prim_t(prims[rng], o, d, entry), ranks[rng], closest, hit)
-            off += c
-        kids = sorted((t0[s], s) for s in range(n_int) if hitm[s])
-        if kids:
-            node = fc + kids[0][1]
-            stack.extend(fc + s for _, s in reversed(kids[1:]))
-        else:
-            node = stack.pop() if stack else -1
-    return closest, hit
 
 
 def test_wide_export_spheres_per_ray(host_scene):
