@@ -232,6 +232,60 @@ int  crt_scene_compare(crt_renderer* r, const crt_scene* a, const crt_scene* b, 
 int  crt_scene_compare_dump(crt_renderer* r, const crt_scene* a, const crt_scene* b, int spp, int max_bounces,
                             uint64_t out[5], float* dump, int max_dump);
 
+/* ---- ray queries (no reference counterpart: the reference traces only the rays its render kernel generates) ----
+ * A batch of caller-supplied rays against a device scene: closest hit or occlusion (DESIGN.md "Ray queries").
+ * Closest hit = the reference's own query, scene.hit(ray, Interval(0.001f, INFINITY)) (CUDAKernels.h:123), with the
+ * render kernels' hit rule (closest t, ties to the higher reference DFS rank); it is reported only when t <= tmax.  The
+ * traversal always runs over [0.001, inf): tmax filters the result, it never changes which boxes or primitives the
+ * traversal accepts.  Occlusion = "the closest-hit query reports a hit".
+ * Preconditions per ray: every component of origin and dir finite, dir not all-zero (zero components of either sign
+ * are fine), |origin| < 2^59, tmax not NaN.  The host-pointer entries check them before anything is launched; for the
+ * device-pointer entry they are the caller's duty. */
+typedef struct crt_ray { float origin[3]; float tmax; float dir[3]; float reserved; } crt_ray;   /* dir: not normalised; t is in units of dir */
+/* object: index into desc.meshes, or -1 - index into desc.spheres; primitive: triangle of the mesh after the build
+ * permutation (indices[index_offset + 3 * primitive ..]), 0 for a sphere; material: the index shade() uses (triangle:
+ * face_materials[face_offset + primitive] + material_id_offset; sphere: its material), as is even when out of range;
+ * normal: the outward geometric unit normal, not flipped (triangle: the shading record's unit(cross(e1, e2)), Mesh.cuh:
+ * 303-304; sphere: (1 / r) * (P - c), P = o + t * d, Sphere.cuh:44); front_face = dot(dir, normal) < 0 (HitInfo.cuh:16).
+ * A miss: t = -1.f, every other field 0. */
+typedef struct crt_hit { float t; int32_t object, primitive, material; float normal[3]; int32_t front_face; } crt_hit;
+typedef struct crt_trace_options {
+    int32_t mode;        /* 0 = automatic (4-wide scenes: 2 from 2^20 rays per call, else 1; the records are the same);
+                            1 = one ray per lane (trace / trace4); 2 = wave-cooperative stream kernel (4-wide scenes only).
+                            Over 4-wide nodes mode 1 keeps a fixed 64-entry stack per lane, three entries per level:
+                            a tree with 3 * stack_bound > 64 is CRT_ERR_UNSUPPORTED in mode 1, and mode 0 takes 2 */
+    int32_t grid_waves;  /* 0 = automatic; > 0: testing only, caps the persistent grid so few rays still refill lanes */
+    int32_t stack_lds;   /* 0 = default; 1..16 as crt_renderer_set_stack_lds (1 forces the HBM overflow path); the stream
+                            kernel keeps at most 12 entries in LDS (one-wave workgroups at 6 per SIMD), so 13..16 act as 12 */
+    int32_t refill_threshold; /* 0 = default; idle lanes (1..64) that trigger a refill pass */
+} crt_trace_options;
+typedef struct crt_trace_stats {
+    float kernel_ms;               /* HIP events */
+    uint64_t rays, box_tests, tri_tests, sphere_tests; /* only when counting was requested */
+    uint64_t step_lane_slots, step_active_lanes;  /* traversal steps x 64, and lanes with a node in them: lane fill */
+} crt_trace_stats;
+#define CRT_TRACE_COUNT_WORK 1u   /* crt_scene_trace_device flags bit 0 */
+
+/* Host only, no GPU: CRT_OK, or CRT_ERR_INVALID_ARGUMENT with *first_bad (optional) = the first ray that breaks a
+ * precondition (crt_last_error names it too). */
+int crt_trace_validate_rays(const crt_ray* rays, int64_t n, int64_t* first_bad);
+/* Host only like crt_scene_export: the per-rank identity table, n_ranks x 3 ints (object, primitive, material), the
+ * same for every bvh mode of one description.  out == NULL: only *n_ranks is set. */
+int crt_scene_export_identity(const crt_scene_desc* desc, const crt_scene_options* opts, int32_t* out, int64_t* n_ranks);
+/* Host pointers, synchronous; n up to 2^31 - 1 (traced in chunks through staging buffers the scene owns).  n == 0:
+ * CRT_OK, nothing launched.  A device error (e.g. a traversal-stack entry dropped below the tree's bound) is
+ * CRT_ERR_HIP.  A scene handle serves one trace call at a time. */
+int crt_scene_trace(const crt_scene* scene, const crt_ray* rays, int64_t n, const crt_trace_options* opts, crt_hit* hits_out);
+int crt_scene_occluded(const crt_scene* scene, const crt_ray* rays, int64_t n, const crt_trace_options* opts, uint8_t* out);
+/* Device pointers on the scene's device, 16-B aligned; enqueued on `stream`, asynchronous.  d_hits / d_occluded: either
+ * may be NULL, not both (only d_occluded: the occlusion query, whose lanes retire at the first accepted hit).  Device
+ * errors of the launch are reported by crt_scene_trace_last_stats. */
+int crt_scene_trace_device(const crt_scene* scene, const crt_ray* d_rays, int64_t n, const crt_trace_options* opts,
+                           crt_hit* d_hits, uint8_t* d_occluded, unsigned flags, void* stream);
+/* Of the last trace on this scene; synchronises with it.  The work counts are 0 unless it counted (the host entries
+ * never count; mode 1 over a 4-wide scene counts rays only). */
+int crt_scene_trace_last_stats(const crt_scene* scene, crt_trace_stats* out);
+
 /* ---- renderer (CUDARenderer) ---- */
 int  crt_renderer_create(int width, int height, int device, crt_renderer** out);
 void crt_renderer_destroy(crt_renderer* r);

@@ -130,6 +130,22 @@ class HostScene:
         return export_desc(self.desc(), bvh, **options)
 
 
+    def identity(self, bvh: str = "reference", **options) -> np.ndarray:
+        """The per-rank identity table of the ray queries, int32 [ranks, 3] = (object, primitive, material) (host only,
+        crt_scene_export_identity); the same for every bvh mode."""
+        return identity_desc(self.desc(), bvh, **options)
+
+
+def identity_desc(d: SceneDesc, bvh: str = "reference", **options) -> np.ndarray:
+    """crt_scene_export_identity of any scene description."""
+    o = scene_options(bvh, **options)
+    n = C.c_int64(0)
+    check(_lib.hip().crt_scene_export_identity(C.byref(d), C.byref(o), None, C.byref(n)), "crt_scene_export_identity")
+    out = np.zeros((n.value, 3), np.int32)
+    check(_lib.hip().crt_scene_export_identity(C.byref(d), C.byref(o), _p(out), C.byref(n)), "crt_scene_export_identity")
+    return out
+
+
 def export_desc(d: SceneDesc, bvh: str = "reference", **options) -> dict:
     """crt_scene_export of any scene description (HostScene.desc() or a caller's own)."""
     o = scene_options(bvh, **options)
@@ -181,6 +197,48 @@ def _nodes_to_np(ptr, n):
     return rec["b"].copy(), rec["i"].copy()
 
 
+# crt_hit as a numpy record (two 16-B rows)
+HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<i4"), ("primitive", "<i4"), ("material", "<i4"),
+                      ("normal", "<f4", 3), ("front_face", "<i4")])
+
+
+def pack_rays(rays_or_o, d=None, tmax=None) -> np.ndarray:
+    """crt_ray rows, float32 [n, 8] = (o.xyz, tmax, d.xyz, 0), from an [n, 8] array or from origins [n, 3], directions
+    [n, 3] and tmax (None = inf, a scalar or [n])."""
+    if d is None:
+        r = np.ascontiguousarray(rays_or_o, np.float32)
+        if r.ndim != 2 or r.shape[1] != 8:
+            raise ValueError("rays must have shape [n, 8]")
+        return r
+    o = np.asarray(rays_or_o, np.float32).reshape(-1, 3)
+    d = np.asarray(d, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions differ in shape")
+    r = np.zeros((len(o), 8), np.float32)
+    r[:, :3], r[:, 4:7] = o, d
+    r[:, 3] = np.inf if tmax is None else np.asarray(tmax, np.float32)
+    return r
+
+
+def validate_rays(rays) -> int:
+    """Index of the first ray that breaks a precondition of the ray queries, or -1 (crt_trace_validate_rays; no GPU)."""
+    r = pack_rays(rays)
+    bad = C.c_int64(-1)
+    rc = _lib.hip().crt_trace_validate_rays(_p(r), len(r), C.byref(bad))
+    if rc not in (0, -1):
+        check(rc, "crt_trace_validate_rays")
+    return int(bad.value) if rc else -1
+
+
+def _is_torch(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch"     # no torch import for numpy callers
+
+
+def _hit_fields(f32, i32) -> dict:
+    return {"t": f32[:, 0], "object": i32[:, 1], "primitive": i32[:, 2], "material": i32[:, 3],
+            "normal": f32[:, 4:7], "front_face": i32[:, 7]}
+
+
 class Scene:
     """Device scene handle (crt_scene)."""
 
@@ -199,6 +257,92 @@ class Scene:
             self.h = None
 
     __del__ = close
+
+    # ---- ray queries (crt_hip.h "ray queries", DESIGN.md "Ray queries")
+    @staticmethod
+    def _trace_options(mode, grid_waves, stack_lds, refill_threshold):
+        o = _lib.TraceOptions()
+        o.mode, o.grid_waves, o.stack_lds, o.refill_threshold = int(mode), int(grid_waves), int(stack_lds), int(refill_threshold)
+        return o
+
+    def _trace_torch(self, rays, o, want_hits, count_work):
+        import torch
+        if (rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous()
+                or not rays.is_cuda or rays.device.index != self.device):
+            raise ValueError("rays must be a contiguous float32 [n, 8] tensor on the scene's device")
+        n = rays.shape[0]
+        hits = torch.empty((n, 8), dtype=torch.float32, device=rays.device) if want_hits else None
+        occ = None if want_hits else torch.empty((n,), dtype=torch.uint8, device=rays.device)
+        stream = torch.cuda.current_stream(rays.device).cuda_stream
+        check(_lib.hip().crt_scene_trace_device(self.h, rays.data_ptr(), n, C.byref(o),
+                                                hits.data_ptr() if want_hits else None,
+                                                None if want_hits else occ.data_ptr(),
+                                                _lib.TRACE_COUNT_WORK if count_work else 0, stream),
+              "crt_scene_trace_device")
+        return hits if want_hits else occ
+
+    def trace(self, rays_or_o, d=None, tmax=None, *, mode=0, grid_waves=0, stack_lds=0, refill_threshold=0,
+              count_work=False) -> dict:
+        """Closest hit of every ray over [0.001, inf), reported when t <= tmax: a dict of arrays t, object, primitive,
+        material, normal [n, 3], front_face (a miss: t = -1, the rest 0; see crt_hit in crt_hip.h).
+
+        numpy: rays float32 [n, 8] (pack_rays), or origins, directions and tmax; the rays are checked on the host
+        (CrtError names the first bad one) and the result is numpy.  torch: a contiguous float32 [n, 8] tensor on the
+        scene's device; the query is enqueued on torch's current stream without a host copy and the dict holds views
+        of ONE [n, 8] tensor of crt_hit rows, float32 columns (t, normal) of the tensor itself ("f32") and int32
+        columns (object, primitive, material, front_face) of its int32 view ("i32").  The caller keeps the
+        preconditions.  count_work fills trace_stats()' work counts (numpy rays then go through the device entry too).
+
+        A torch query (and a numpy one with count_work) is asynchronous: a device error of its kernel, such as a
+        traversal-stack entry dropped below the tree's bound, is raised by the next trace_stats() call, not here.
+        The numpy path without count_work waits for the kernel and raises such an error itself."""
+        o = self._trace_options(mode, grid_waves, stack_lds, refill_threshold)
+        if _is_torch(rays_or_o):
+            if d is not None or tmax is not None:
+                raise ValueError("a torch query takes one [n, 8] tensor of crt_ray rows")
+            f32 = self._trace_torch(rays_or_o, o, True, count_work)
+            i32 = f32.view(__import__("torch").int32)
+            return dict(_hit_fields(f32, i32), f32=f32, i32=i32)
+        r = pack_rays(rays_or_o, d, tmax)
+        if count_work:
+            import torch
+            self._check_rays(r)
+            f32 = self._trace_torch(torch.from_numpy(r).to(f"cuda:{self.device}"), o, True, True).cpu().numpy()
+        else:
+            f32 = np.zeros((len(r), 8), np.float32)
+            check(_lib.hip().crt_scene_trace(self.h, _p(r), len(r), C.byref(o), _p(f32)), "crt_scene_trace")
+        return {k: v.copy() for k, v in _hit_fields(f32, f32.view(np.int32)).items()}
+
+    def occluded(self, rays_or_o, d=None, tmax=None, *, mode=0, grid_waves=0, stack_lds=0, refill_threshold=0,
+                 count_work=False):
+        """uint8 [n]: 1 where trace() with the same rays reports a hit (the 4-wide stream kernel retires a lane at its
+        first accepted hit with t <= tmax).  numpy in, numpy out; a torch tensor in, a torch tensor out (see trace,
+        also for where a device error of an asynchronous query is raised: trace_stats())."""
+        o = self._trace_options(mode, grid_waves, stack_lds, refill_threshold)
+        if _is_torch(rays_or_o):
+            if d is not None or tmax is not None:
+                raise ValueError("a torch query takes one [n, 8] tensor of crt_ray rows")
+            return self._trace_torch(rays_or_o, o, False, count_work)
+        r = pack_rays(rays_or_o, d, tmax)
+        if count_work:
+            import torch
+            self._check_rays(r)
+            return self._trace_torch(torch.from_numpy(r).to(f"cuda:{self.device}"), o, False, True).cpu().numpy()
+        out = np.zeros(len(r), np.uint8)
+        check(_lib.hip().crt_scene_occluded(self.h, _p(r), len(r), C.byref(o), _p(out)), "crt_scene_occluded")
+        return out
+
+    @staticmethod
+    def _check_rays(r):
+        check(_lib.hip().crt_trace_validate_rays(_p(r), len(r), None), "crt_trace_validate_rays")
+
+    def trace_stats(self) -> dict:
+        """Of the last ray query on this scene (crt_scene_trace_last_stats; waits for it): kernel_ms, and for a
+        count_work query rays, box_tests, tri_tests, sphere_tests, step_lane_slots, step_active_lanes (lane fill =
+        step_active_lanes / step_lane_slots)."""
+        s = _lib.TraceStats()
+        check(_lib.hip().crt_scene_trace_last_stats(self.h, C.byref(s)), "crt_scene_trace_last_stats")
+        return {k: (float if k == "kernel_ms" else int)(getattr(s, k)) for k, _ in _lib.TraceStats._fields_}
 
 
 def load_scene(obj_files, device: int = 0, **upload_options):

@@ -94,6 +94,27 @@ class WorkCounters(C.Structure):
                 ("sphere_tests", C.c_uint64), ("paths", C.c_uint64)]
 
 
+class Ray(C.Structure):              # crt_hip.h crt_ray: two 16-B rows
+    _fields_ = [("origin", C.c_float * 3), ("tmax", C.c_float), ("dir", C.c_float * 3), ("reserved", C.c_float)]
+
+
+class Hit(C.Structure):              # crt_hip.h crt_hit: two 16-B rows
+    _fields_ = [("t", C.c_float), ("object", C.c_int32), ("primitive", C.c_int32), ("material", C.c_int32),
+                ("normal", C.c_float * 3), ("front_face", C.c_int32)]
+
+
+class TraceOptions(C.Structure):     # crt_hip.h crt_trace_options
+    _fields_ = [("mode", C.c_int32), ("grid_waves", C.c_int32), ("stack_lds", C.c_int32),
+                ("refill_threshold", C.c_int32)]
+
+
+class TraceStats(C.Structure):       # crt_hip.h crt_trace_stats
+    _fields_ = [("kernel_ms", C.c_float), ("rays", C.c_uint64), ("box_tests", C.c_uint64), ("tri_tests", C.c_uint64),
+                ("sphere_tests", C.c_uint64), ("step_lane_slots", C.c_uint64), ("step_active_lanes", C.c_uint64)]
+
+
+TRACE_COUNT_WORK = 1     # crt_scene_trace_device flags
+
 # exported symbol lists (checked by tests against include/*.h)
 HIP_SYMBOLS = [
     "crt_abi_version", "crt_build_flags", "crt_last_error", "crt_device_count", "crt_scene_create", "crt_scene_create_ex", "crt_scene_get_stats", "crt_scene_compare", "crt_scene_compare_dump", "crt_scene_export",
@@ -112,6 +133,8 @@ HIP_SYMBOLS = [
     "crt_renderer_set_top_levels",
     "crt_selftest_math", "crt_selftest_rng", "crt_selftest_geometry", "crt_selftest_scan", "crt_selftest_rcp",
     "crt_selftest_uv_div", "crt_selftest_sqrt",
+    "crt_trace_validate_rays", "crt_scene_export_identity", "crt_scene_trace", "crt_scene_occluded",
+    "crt_scene_trace_device", "crt_scene_trace_last_stats",
 ]
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
@@ -192,6 +215,12 @@ def hip():
             "crt_selftest_rcp": ([C.c_uint32, C.c_uint32, P, P], i32),
             "crt_selftest_uv_div": ([i32, P], i32),
             "crt_selftest_sqrt": ([C.c_uint32, C.c_uint32, P, P], i32),
+            "crt_trace_validate_rays": ([P, C.c_int64, P], i32),
+            "crt_scene_export_identity": ([P, P, P, P], i32),
+            "crt_scene_trace": ([P, P, C.c_int64, P, P], i32),
+            "crt_scene_occluded": ([P, P, C.c_int64, P, P], i32),
+            "crt_scene_trace_device": ([P, P, C.c_int64, P, P, P, C.c_uint, P], i32),
+            "crt_scene_trace_last_stats": ([P, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):

@@ -2601,6 +2601,7 @@ struct Flattener {
     std::vector<int> rank_of;        // per prim
     std::vector<char> reachable;     // per prim
     std::vector<int> rank_code;      // per rank: prim code
+    std::vector<int> sphere_of;      // per sphere prim, in prim order after the triangles: its index in D->spheres
     int max_depth = 0;
     std::string err;
 
@@ -2683,6 +2684,7 @@ struct Flattener {
             prims.push_back(make_float4(0.f, i2f(S.material), 0.f, i2f(1)));                  // word 11 = 1: sphere
             rank_of.push_back(-1);
             reachable.push_back(0);
+            sphere_of.push_back(O.index);
             visit_prim(p, SPHERE_BIT | p, thin);
             push_node(N.bmin, N.bmax, 0, SPHERE_BIT | p);
         } else {
@@ -3074,12 +3076,16 @@ struct crt_scene {
     int bvh = CRT_BVH_REFERENCE, layouts = 1;
     int width = 2;                 // 2: threaded layouts (variants 0-3); 4: 4-wide nodes (variant 4)
     int stack_cap = 0;             // width 4: traversal-stack entries a ray can need
+    int stack_bound = 0;           // width 4: the tree's own bound (stack_cap without the testing override)
     long spatial_splits = 0, references = 0;   // rebuilt tree: SBVH cuts, leaf references
     int sphere_first = 0, n_ray_spheres = 0;   // width 4: spheres tested per ray, prims [first, first + n)
     float sph2[2][12] = {};                    // width 4 with exactly two per-ray spheres: their kernel-argument copy
     int tree_spheres = 1;                      // width 4: some leaf holds a sphere
     long excluded = 0;
+    int4* d_ident = nullptr;       // ray queries: per rank (object, primitive, material, 0), see identity_table
+    struct TraceScratch* trace = nullptr;   // ray queries: scratch of the handle, allocated on first use (crt_trace.h)
 };
+void crtx_free_trace_scratch(crt_scene* S);
 
 constexpr int ERR_WORD = 15;      // d_counters word of the device error flags (RenderParams::err)
 
@@ -3310,6 +3316,45 @@ static std::vector<float4> shading_records(const std::vector<int>& rank_code, co
     return out;
 }
 
+// Per-rank identity of the ray queries' hit record: (object, primitive, material, 0) of the primitive with reference
+// DFS rank r.  Built from the Flattener alone, so it is the same table for every bvh mode of one description.
+// object = mesh index, or -1 - index in D->spheres; primitive = triangle within its mesh after the build permutation
+// (0 for a sphere); material = the record's material word (the index shade() uses, out of range or not).
+static std::vector<int32_t> identity_table(const Flattener& F) {
+    const size_t n_tri = F.prims.size() / 3 - F.sphere_of.size();
+    std::vector<int32_t> out(4 * F.rank_code.size(), 0);
+    for (size_t r = 0; r < F.rank_code.size(); ++r) {
+        const bool sphere = (F.rank_code[r] & SPHERE_BIT) != 0;
+        const size_t p = (size_t)(F.rank_code[r] & ~SPHERE_BIT);
+        int32_t* o = out.data() + 4 * r;
+        if (sphere) {
+            o[0] = -1 - F.sphere_of[p - n_tri];
+            o[1] = 0;
+            o[2] = i2i_host(F.prims[3 * p + 1].y);
+        } else {
+            const size_t m = (size_t)(std::upper_bound(F.mesh_prim_base.begin(), F.mesh_prim_base.end(), (int)p) -
+                                      F.mesh_prim_base.begin()) - 1;
+            o[0] = (int32_t)m;
+            o[1] = (int32_t)(p - (size_t)F.mesh_prim_base[m]);
+            o[2] = i2i_host(F.prims[3 * p + 2].y);
+        }
+    }
+    return out;
+}
+
+int crt_scene_export_identity(const crt_scene_desc* D, const crt_scene_options* opts, int32_t* out, int64_t* n_ranks) {
+    if (!D || !n_ranks) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
+    crt_scene_options o;
+    Flattener F{D};
+    Rebuilt RB;
+    if (int rc = build_scene_arrays(D, opts, o, F, RB, 0)) return rc;
+    const std::vector<int32_t> id = identity_table(F);
+    *n_ranks = (int64_t)F.rank_code.size();
+    if (out)
+        for (size_t r = 0; r < F.rank_code.size(); ++r) std::memcpy(out + 3 * r, id.data() + 4 * r, 3 * sizeof(int32_t));
+    return CRT_OK;
+}
+
 int crt_scene_create_ex(const crt_scene_desc* D, int device, const crt_scene_options* opts, crt_scene** out) {
     if (!D || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
@@ -3340,6 +3385,7 @@ int crt_scene_create_ex(const crt_scene_desc* D, int device, const crt_scene_opt
     S->excluded = rebuilt ? RB.excluded : 0;
     S->width = rebuilt ? RB.width : 2;
     S->stack_cap = rebuilt ? (o.stack_cap > 0 ? o.stack_cap : RB.stack_bound) : 0;
+    S->stack_bound = rebuilt ? RB.stack_bound : 0;
     S->sphere_first = rebuilt ? RB.sphere_first : 0;
     S->spatial_splits = rebuilt ? RB.spatial_splits : 0;
     S->references = rebuilt ? RB.references : 0;
@@ -3379,12 +3425,16 @@ int crt_scene_create_ex(const crt_scene_desc* D, int device, const crt_scene_opt
     tr.lap("node swizzle");
     const std::vector<float4> shade = shading_records(rc, rebuilt ? RB.prims : F.prims, D);
     tr.lap("shading records");
+    const std::vector<int32_t> ident = identity_table(F);
     hipError_t e;
     if ((e = up(&S->d_nodes, S->width == 4 ? swizzled : (rebuilt ? RB.nodes : F.nodes))) != hipSuccess ||
         (e = up(&S->d_prims, rebuilt ? RB.prims : F.prims)) != hipSuccess ||
         (e = up(&S->d_mats, mats)) != hipSuccess ||
         (e = up(&S->d_chain, rebuilt ? RB.chain : std::vector<float4>())) != hipSuccess ||
-        (e = up(&S->d_shade, shade)) != hipSuccess) {
+        (e = up(&S->d_shade, shade)) != hipSuccess ||
+        (e = hipMalloc((void**)&S->d_ident, std::max<size_t>(ident.size(), 4) * sizeof(int32_t))) != hipSuccess ||
+        (!ident.empty() && (e = hipMemcpy(S->d_ident, ident.data(), ident.size() * sizeof(int32_t),
+                                          hipMemcpyHostToDevice)) != hipSuccess)) {
         crt_scene_destroy(S);
         return set_error(CRT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
     }
@@ -3419,6 +3469,8 @@ void crt_scene_destroy(crt_scene* S) {
     if (S->d_mats) (void)hipFree(S->d_mats);
     if (S->d_shade) (void)hipFree(S->d_shade);
     if (S->d_chain) (void)hipFree(S->d_chain);
+    if (S->d_ident) (void)hipFree(S->d_ident);
+    crtx_free_trace_scratch(S);
     delete S;
 }
 
@@ -4446,3 +4498,8 @@ int crt_selftest_rng(unsigned long long seed, const unsigned long long* subseq, 
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ ray queries
+// Batch closest-hit / occlusion queries over a device scene: the kernels and their C ABI, in this translation unit
+// because they instantiate the traversal's device functions above (traverse_step4, trace, trace4, ray_spheres).
+#include "crt_trace.h"

@@ -1,0 +1,465 @@
+// crt_trace.h — batch ray queries (closest hit, occlusion) over a device scene: kernels + C ABI.
+//
+// Textually part of crt_hip.hip (included at its end): the kernels instantiate that file's traversal functions
+// unchanged -- traverse_step4 / top_steps / ray_spheres for 4-wide scenes, trace / trace4 per lane -- so a query sees
+// exactly the boxes, primitives and hit rule the render kernels see.  Nothing here is used by a render kernel.
+//
+//   crt_trace_kernel<ANY, COUNT>   4-wide scenes, the hot path: variant 7's persistent loop with the pixel replaced by
+//                                  a ray index and no shading state.  One wave per workgroup; a lane without a node is
+//                                  idle; a refill pass finishes the idle lanes' rays (per-ray spheres, record store)
+//                                  and hands them the next indices of one global counter.  All global loads of rays
+//                                  and stores of results sit in the pass, never in the step loop (the
+//                                  removed wavefront variant 5 paid a vmcnt wait per node load for them).
+//   crt_trace_lane_kernel<COUNT>   every scene: one ray per lane through trace<> (threaded) or trace4 (4-wide), the
+//                                  bit-exact baseline the stream kernel is measured against; no early exit.
+#pragma once
+
+struct TraceParams {
+    RenderParams P;                        // the scene's arrays, stack split, per-ray spheres, error word
+    const float4* __restrict__ rays;       // 2 rows per ray: (o.xyz, tmax) (d.xyz, -)
+    float4* __restrict__ hits;             // 2 rows per ray, or null
+    unsigned char* __restrict__ occ;       // 1 byte per ray, or null
+    const int4* __restrict__ ident;        // per rank: (object, primitive, material, 0)
+    uint32_t n;                            // rays of this launch (< 2^31)
+    uint32_t* __restrict__ next;           // stream kernel: the next unreserved ray index
+    uint32_t block;                        // stream kernel: indices a wave reserves per atomicAdd (a multiple of 64)
+    unsigned long long* __restrict__ stats;// COUNT: rays, boxes, triangles, spheres, step lane slots, active lanes
+    int refill_threshold;                  // stream kernel: idle lanes that trigger a refill pass
+    int width;                             // lane kernel: 2 = threaded nodes, 4 = 4-wide nodes
+};
+
+// The hit record (crt_hit) and / or the occlusion byte of ray i.  (t, rank) is the traversal's closest hit over
+// [0.001, inf); tmax filters it.  Identity from the rank's identity row, the normal from its shading record's first
+// row (triangle: the stored unit normal; sphere: (1 / r) * (P - c), Sphere.cuh:44, as shade_rec computes it).
+__device__ __forceinline__ void trace_store(const TraceParams& T, uint32_t i, V3 o, V3 d, float tmax, float t, int hit) {
+    const bool ok = hit >= 0 && t <= tmax;
+    if (T.hits) {
+        float4 a = make_float4(-1.f, 0.f, 0.f, 0.f), b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok) {
+            const int4 id = T.ident[hit];
+            const float4* R = T.P.shade + 3u * (uint32_t)hit;
+            const float4 r0 = R[0];
+            V3 nrm = v3(r0.x, r0.y, r0.z);
+            if (__float_as_uint(r0.w) & SHADE_SPHERE) {
+                const float ir = R[2].x;
+                const V3 hp = o + t * d;                    // Ray::pointAtDistance
+                nrm = ir * (hp - nrm);
+            }
+            const bool front = dot(d, nrm) < 0;             // HitInfo::setFaceNormal
+            a = make_float4(t, __int_as_float(id.x), __int_as_float(id.y), __int_as_float(id.z));
+            b = make_float4(nrm.x, nrm.y, nrm.z, __int_as_float(front ? 1 : 0));
+        }
+        T.hits[2 * (size_t)i] = a;
+        T.hits[2 * (size_t)i + 1] = b;
+    }
+    if (T.occ) T.occ[i] = ok ? (unsigned char)1 : (unsigned char)0;
+}
+
+__device__ __forceinline__ void trace_add_stats(const TraceParams& T, int lane, uint64_t rays, const TraceCounts& cnt,
+                                                uint64_t active) {
+    const uint64_t v[6] = {rays, cnt.boxes, cnt.tris, cnt.spheres, cnt.step_slots, active};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const uint64_t s = wave_sum_u64(v[k]);
+        if (lane == 0 && s) atomicAdd(&T.stats[k], (unsigned long long)s);
+    }
+}
+
+template <bool ANY, bool COUNT>
+__global__ __launch_bounds__(64, 6) void crt_trace_kernel(TraceParams T) {
+    const RenderParams& P = T.P;
+    constexpr int SD = CRT_STACK6;           // LDS stack entries per lane at 6 one-wave workgroups per SIMD
+    constexpr int TOPN = TOP_NODES;
+    __shared__ WaveLdsWide L;
+    __shared__ uint32_t stk[SD * 64];
+    __shared__ __attribute__((aligned(16))) float sph_lds[32];   // the two per-ray spheres, as crt_render_kernel stages them
+    __shared__ float4 top_lds[TOPN > 0 ? 8 * TOPN : 1];
+    if (threadIdx.x < 32) {
+        const int k = threadIdx.x & 15;
+        const int src = k < 4 ? k : k < 9 ? k + 1 : k == 9 ? 10 : k == 10 ? 4 : -1;
+        sph_lds[threadIdx.x] = src < 0 ? 0.f : P.sph2[threadIdx.x >> 4][src];
+    }
+    if (TOPN > 0 && threadIdx.x < 8u * TOPN) {
+        const uint32_t m = threadIdx.x >> 3, k = threadIdx.x & 7;
+        int n = 0;
+        if (m > 0) {
+            const float4 rm = node_row(P.nodes, node_base(0), 6);
+            n = (int)(m - 1) < (__float_as_int(rm.y) & 0xff) ? __float_as_int(rm.x) + (int)(m - 1) : -1;
+        }
+        if (n >= 0 && n < P.n_nodes) top_lds[threadIdx.x] = node_row(P.nodes, node_base(n), k);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x;
+    // the overflow stack region is indexed by grid lane, not by ray: (stack_cap - stack_lds) x grid lanes entries
+    const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane, n_gl = (size_t)gridDim.x * 64;
+    const float INF = __builtin_inff();
+    const uint64_t below = (1ull << lane) - 1ull;
+    const uint32_t NONE = 0xffffffffu;
+    TraceCounts cnt{};
+    uint64_t n_rays = 0, n_active = 0;       // COUNT only
+    // lane state: the ray, its traversal and its index; nothing else lives across the loop
+    V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f), inv = v3(0.f, 0.f, 0.f);
+    float tmax = INF, closest = INF;
+    uint32_t rows = 0, idx = NONE;
+    int node = -1, sp = 0, hit = -1;
+    // wave-uniform: first index of the reserved block, indices handed out.  Variant 7 reserves 64 pixels per
+    // atomicAdd; a ray is ~4 node steps where a pixel is whole paths, and at 64 rays per atomicAdd the one counter's
+    // address bounds the kernel (about 12 ns per atomic: 0.7 ms for 3.7 M rays whatever the grid, profiles/ray_query),
+    // so the host sizes the block with the query (trace_enqueue)
+    uint32_t pool = 0, used = T.block;
+    bool exhausted = false;
+    L.owner_at[lane] = 0;
+    for (;;) {
+        const bool idle = idx != NONE && node < 0;             // holds a finished ray
+        const int n_idle = __popcll(wave_ballot(idle));
+        const int n_have = __popcll(wave_ballot(idx != NONE));
+        if (n_idle >= T.refill_threshold || n_idle == n_have) {
+            if (idle) {
+                // the per-ray spheres against the traversal's closest hit, as finish_ray tests them (an occlusion
+                // lane that retired on a hit within tmax is occluded whatever they add)
+                if (!(ANY && hit >= 0 && closest <= tmax)) {
+                    if (COUNT) cnt.spheres += P.n_ray_spheres;
+                    ray_spheres<true>(P.prims, P.sphere_chain, P.n_chain, P.sphere_first, P.n_ray_spheres, o, d,
+                                      sphere_inv(d, inv), closest, hit, sph_lds);
+                }
+                trace_store(T, idx, o, d, tmax, closest, hit);
+                idx = NONE;
+            }
+            while (!exhausted) {                 // lanes without a ray take the next indices
+                const uint64_t need = wave_ballot(idx == NONE);
+                if (need == 0) break;
+                if (used >= T.block) {
+                    uint32_t b = 0;
+                    if (lane == 0) b = atomicAdd(T.next, T.block);
+                    pool = __builtin_amdgcn_readfirstlane(b);
+                    used = 0;
+                    if (pool >= T.n) { exhausted = true; break; }
+                }
+                const uint32_t take = min((uint32_t)__popcll(need), T.block - used);
+                const uint32_t rank = (uint32_t)__popcll(need & below);
+                if (idx == NONE && rank < take && pool + used + rank < T.n) {
+                    idx = pool + used + rank;
+                    const float4 r0 = T.rays[2 * (size_t)idx], r1 = T.rays[2 * (size_t)idx + 1];
+                    o = v3(r0.x, r0.y, r0.z);
+                    tmax = r0.w;
+                    d = v3(r1.x, r1.y, r1.z);
+                    if (COUNT) ++n_rays;
+                    node = 0;
+                    sp = 0;
+                    closest = INF;
+                    hit = -1;
+                    inv = box_inv(recip3_exact(d));   // the traversal's 1/d (wide_boxes)
+                    rows = ray_rows(inv);
+                    L.ray0[lane] = make_float4(o.x, o.y, o.z, d.x);
+                    if (TOPN > 0) top_steps<COUNT, TOPN>(P, top_lds, o, inv, rows, node, sp, cnt, stk, gl, n_gl);
+                }
+                used += take;
+            }
+            if (!wave_ballot(idx != NONE)) break;     // the counter is past the end and every lane is done
+        }
+        if (COUNT) n_active += node >= 0;
+        traverse_step4<COUNT>(P, o, d, inv, rows, node, sp, closest, hit, cnt, L, stk, lane, gl, n_gl);
+        // occlusion: the closest t is no larger than any accepted t, so the first accepted hit within tmax decides;
+        // the lane drops its stack and waits for the pass
+        if (ANY && node >= 0 && hit >= 0 && closest <= tmax) {
+            node = -1;
+            sp = 0;
+        }
+    }
+    if (COUNT) trace_add_stats(T, lane, n_rays, cnt, n_active);
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(256) void crt_trace_lane_kernel(TraceParams T) {
+    const RenderParams& P = T.P;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    TraceCounts cnt{};
+    if (i < T.n) {
+        const float4 r0 = T.rays[2 * (size_t)i], r1 = T.rays[2 * (size_t)i + 1];
+        const V3 o = v3(r0.x, r0.y, r0.z), d = v3(r1.x, r1.y, r1.z);
+        float t;
+        const int hit = T.width == 4 ? trace4(P.nodes, P.prims, P.sphere_chain, P.n_chain, P.sphere_first,
+                                              P.n_ray_spheres, o, d, t)
+                                     : trace<COUNT>(P.nodes, P.prims, P.n_nodes,
+                                                    layout_base(d, P.n_layouts, P.n_nodes), o, d, t, cnt);
+        trace_store(T, i, o, d, r0.w, t, hit);
+    }
+    if (COUNT) trace_add_stats(T, threadIdx.x & 63, i < T.n ? 1u : 0u, cnt, 0);
+}
+
+// ------------------------------------------------------------------ host side
+constexpr int TRACE_ERR_WORD = 6;            // d_stats word of the device error flags (RenderParams::err)
+constexpr int TRACE_STAT_WORDS = 8;
+constexpr int64_t TRACE_LAUNCH_RAYS = (int64_t)1 << 30;   // rays per launch (the ray counter is 32-bit)
+constexpr int64_t TRACE_STAGE_RAYS = (int64_t)1 << 20;    // rays per chunk of the host-pointer entries
+constexpr int64_t TRACE_STREAM_MIN_RAYS = (int64_t)1 << 20;   // automatic mode: queries from this size take the stream kernel
+constexpr int TRACE4_STACK = 64;             // trace4's per-lane stack (int stack[64] in crt_hip.hip)
+
+struct TraceScratch {
+    uint32_t* d_next = nullptr;
+    unsigned long long* d_stats = nullptr;
+    uint32_t* d_ovf = nullptr;               // stack entries beyond the LDS part, per grid lane
+    size_t ovf_bytes = 0;
+    float4* d_rays = nullptr;                // staging of the host-pointer entries
+    float4* d_hits = nullptr;
+    unsigned char* d_occ = nullptr;
+    int64_t stage_rays = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool traced = false;
+    int n_cus = 0, wg_per_cu = 0;
+};
+
+void crtx_free_trace_scratch(crt_scene* S) {
+    TraceScratch* X = S->trace;
+    if (!X) return;
+    if (X->d_next) (void)hipFree(X->d_next);
+    if (X->d_stats) (void)hipFree(X->d_stats);
+    if (X->d_ovf) (void)hipFree(X->d_ovf);
+    if (X->d_rays) (void)hipFree(X->d_rays);
+    if (X->d_hits) (void)hipFree(X->d_hits);
+    if (X->d_occ) (void)hipFree(X->d_occ);
+    if (X->ev0) (void)hipEventDestroy(X->ev0);
+    if (X->ev1) (void)hipEventDestroy(X->ev1);
+    delete X;
+    S->trace = nullptr;
+}
+
+namespace {
+
+int trace_scratch(crt_scene* S, TraceScratch** out) {
+    if (!S->trace) {
+        TraceScratch* X = new (std::nothrow) TraceScratch;
+        if (!X) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+        S->trace = X;   // whatever is allocated below is freed with the handle
+        HIP_TRY(hipMalloc((void**)&X->d_next, 4));
+        HIP_TRY(hipMalloc((void**)&X->d_stats, TRACE_STAT_WORDS * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(X->d_stats, 0, TRACE_STAT_WORDS * sizeof(unsigned long long)));
+        HIP_TRY(hipEventCreate(&X->ev0));
+        HIP_TRY(hipEventCreate(&X->ev1));
+        HIP_TRY(hipDeviceGetAttribute(&X->n_cus, hipDeviceAttributeMultiprocessorCount, S->device));
+        // the persistent grid fills the device once: CUs x the stream kernel's resident workgroups per CU
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, crt_trace_kernel<false, false>, 64, 0) != hipSuccess || nb <= 0)
+            nb = 4 * 6;
+        X->wg_per_cu = nb;
+    }
+    *out = S->trace;
+    return CRT_OK;
+}
+
+// One query over device pointers, enqueued on st.
+int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trace_options* opts, crt_hit* d_hits,
+                  uint8_t* d_occ, unsigned flags, hipStream_t st) {
+    crt_trace_options o{};
+    if (opts) o = *opts;
+    if (o.mode < 0 || o.mode > 2) return set_error(CRT_ERR_INVALID_ARGUMENT, "trace mode must be 0, 1 or 2");
+    if (o.grid_waves < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "grid_waves must be >= 0");
+    if (o.stack_lds < 0 || o.stack_lds > 16) return set_error(CRT_ERR_INVALID_ARGUMENT, "stack_lds must be 0..16");
+    if (o.refill_threshold < 0 || o.refill_threshold > 64)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "refill_threshold must be 0..64");
+    if (o.mode == 2 && S->width != 4)
+        return set_error(CRT_ERR_UNSUPPORTED, "the stream kernel (mode 2) needs a 4-wide rebuilt scene");
+    // The lane kernel over 4-wide nodes is trace4, whose per-lane stack holds TRACE4_STACK entries and takes up to
+    // three per branching ancestor (the stream kernel's encoding takes one): it drops what does not fit without a
+    // report, so a tree whose bound could overflow it never goes through it.
+    const bool lane_ok = S->width != 4 || 3 * (int64_t)S->stack_bound <= TRACE4_STACK;
+    if (o.mode == 1 && !lane_ok)
+        return set_error(CRT_ERR_UNSUPPORTED, "mode 1: the tree's stack bound exceeds the lane kernel's 64-entry stack "
+                                              "(3 entries per level); use mode 0 or 2");
+    // automatic: the stream kernel for large queries over 4-wide nodes (3.7 M rays: 1.08x the lane kernel's rate on
+    // primary rays, 1.3x on bounce rays), the lane kernel below that (200 k rays: the persistent grid's ramp and tail
+    // cost more than its lane fill gains, 0.10 ms against 0.07 ms; nothing was measured in between); the records are
+    // the same either way
+    const int mode = o.mode ? o.mode : (S->width == 4 && (n >= TRACE_STREAM_MIN_RAYS || !lane_ok) ? 2 : 1);
+    if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "ray and hit arrays must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(S->device));
+    TraceScratch* X = nullptr;
+    if (int rc = trace_scratch(S, &X)) return rc;
+    const bool cnt = (flags & CRT_TRACE_COUNT_WORK) != 0;
+
+    TraceParams T{};
+    RenderParams& P = T.P;
+    P.nodes = S->d_nodes; P.prims = S->d_prims; P.mats = S->d_mats; P.shade = S->d_shade;
+    P.n_nodes = S->n_nodes; P.n_mats = S->n_mats; P.n_prims = S->n_prims; P.n_layouts = S->layouts;
+    P.err = reinterpret_cast<unsigned*>(X->d_stats + TRACE_ERR_WORD);
+    P.top_levels = CRT_TOP_LEVELS;
+    P.stack_cap = S->stack_cap;
+    P.sphere_first = S->sphere_first;
+    P.n_ray_spheres = S->n_ray_spheres;
+    P.sphere_chain = S->d_chain;
+    P.n_chain = S->n_chain;
+    P.tree_spheres = S->tree_spheres;
+    std::memcpy(P.sph2, S->sph2, sizeof P.sph2);
+    T.ident = S->d_ident;
+    T.next = X->d_next;
+    T.stats = X->d_stats;
+    T.refill_threshold = o.refill_threshold ? o.refill_threshold : 44;   // the 4-wide render variants' threshold
+    T.width = S->width;
+    // the stream kernel's stack split: CRT_STACK6 entries per lane in LDS at the most, the rest per grid lane in HBM
+    P.stack_lds = std::min(o.stack_lds ? o.stack_lds : CRT_STACK6, CRT_STACK6);
+    if (S->stack_cap > 0) P.stack_lds = std::min(P.stack_lds, S->stack_cap);
+    const int64_t full_grid = (int64_t)X->n_cus * X->wg_per_cu;
+    if (mode == 2 && S->stack_cap > P.stack_lds) {
+        const size_t need = (size_t)(S->stack_cap - P.stack_lds) * (size_t)full_grid * 64 * 4;
+        if (need >= ((size_t)1 << 32))
+            return set_error(CRT_ERR_INVALID_ARGUMENT, "traversal-stack overflow region would exceed 4 GiB");
+        if (need > X->ovf_bytes) {
+            HIP_TRY(hipStreamSynchronize(st));
+            if (X->d_ovf) (void)hipFree(X->d_ovf);
+            X->d_ovf = nullptr;
+            X->ovf_bytes = 0;
+            HIP_TRY(hipMalloc((void**)&X->d_ovf, need));
+            X->ovf_bytes = need;
+        }
+        P.ovf = X->d_ovf;
+    }
+    // the counts and the error word of this query (crt_scene_trace_last_stats)
+    HIP_TRY(hipMemsetAsync(X->d_stats, 0, TRACE_STAT_WORDS * sizeof(unsigned long long), st));
+    const bool any = d_hits == nullptr;   // only the occlusion byte is wanted: lanes retire at the first accepted hit
+    for (int64_t at = 0; at < n; at += TRACE_LAUNCH_RAYS) {
+        const int64_t m = std::min(n - at, TRACE_LAUNCH_RAYS);
+        T.rays = reinterpret_cast<const float4*>(d_rays + at);
+        T.hits = d_hits ? reinterpret_cast<float4*>(d_hits + at) : nullptr;
+        T.occ = d_occ ? d_occ + at : nullptr;
+        T.n = (uint32_t)m;
+        if (mode == 2) {
+            int64_t waves = std::min(full_grid, (m + 63) / 64);
+            if (o.grid_waves > 0) waves = std::min<int64_t>(waves, o.grid_waves);
+            const dim3 grid((unsigned)std::max<int64_t>(waves, 1)), block(64);
+            // indices per reservation: 64 x k, k = the refills a lane gets from an even share of the query, at most 8
+            // (measured on 3.7 M primary / bounce rays over the full grid: 128 -> 0.59 / 0.49 ms, 256 -> 0.45 / 0.36,
+            // 512 -> 0.38 / 0.34, 1024 -> 0.38 / 0.39, 2048 -> 0.44 / 0.53: larger blocks leave the last waves a tail)
+            T.block = 64u * (uint32_t)std::min<int64_t>(8, std::max<int64_t>(1, m / (64 * std::max<int64_t>(waves, 1))));
+            HIP_TRY(hipMemsetAsync(X->d_next, 0, 4, st));
+            if (at == 0) HIP_TRY(hipEventRecord(X->ev0, st));   // kernel_ms: from the first kernel, after the counter's reset
+            if (any) {
+                if (cnt) hipLaunchKernelGGL((crt_trace_kernel<true, true>), grid, block, 0, st, T);
+                else hipLaunchKernelGGL((crt_trace_kernel<true, false>), grid, block, 0, st, T);
+            } else {
+                if (cnt) hipLaunchKernelGGL((crt_trace_kernel<false, true>), grid, block, 0, st, T);
+                else hipLaunchKernelGGL((crt_trace_kernel<false, false>), grid, block, 0, st, T);
+            }
+        } else {
+            const dim3 grid((unsigned)((m + 255) / 256)), block(256);
+            if (at == 0) HIP_TRY(hipEventRecord(X->ev0, st));
+            if (cnt) hipLaunchKernelGGL((crt_trace_lane_kernel<true>), grid, block, 0, st, T);
+            else hipLaunchKernelGGL((crt_trace_lane_kernel<false>), grid, block, 0, st, T);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(X->ev1, st));
+    X->traced = true;
+    return CRT_OK;
+}
+
+int trace_take_error(TraceScratch* X) {
+    unsigned long long word = 0;
+    HIP_TRY(hipMemcpy(&word, X->d_stats + TRACE_ERR_WORD, sizeof word, hipMemcpyDeviceToHost));
+    if (!word) return CRT_OK;
+    HIP_TRY(hipMemset(X->d_stats + TRACE_ERR_WORD, 0, sizeof word));
+    std::string m = "trace kernel reported an internal error:";
+    if (word & 1u) m += " primitive index out of range;";
+    if (word & 2u) m += " traversal stack deeper than the scene's stack bound (entries dropped);";
+    if (word & 4u) m += " leaf-round pair outside its owner's span (checked build);";
+    return set_error(CRT_ERR_HIP, m + " the results are invalid");
+}
+
+// The host-pointer entries: validate, then chunks through the handle's staging buffers on the null stream.
+int trace_host(const crt_scene* Sc, const crt_ray* rays, int64_t n, const crt_trace_options* opts, crt_hit* hits,
+               uint8_t* occ) {
+    if (!Sc || n < 0 || (n > 0 && (!rays || (!hits && !occ)))) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument or n < 0");
+    if (n > 0x7fffffffll) return set_error(CRT_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 rays");
+    if (n == 0) return CRT_OK;
+    if (int rc = crt_trace_validate_rays(rays, n, nullptr)) return rc;
+    crt_scene* S = const_cast<crt_scene*>(Sc);   // the scratch belongs to the handle (handles are not thread-safe)
+    HIP_TRY(hipSetDevice(S->device));
+    TraceScratch* X = nullptr;
+    if (int rc = trace_scratch(S, &X)) return rc;
+    const int64_t chunk = std::min(n, TRACE_STAGE_RAYS);
+    if (chunk > X->stage_rays) {
+        HIP_TRY(hipDeviceSynchronize());
+        if (X->d_rays) (void)hipFree(X->d_rays);
+        if (X->d_hits) (void)hipFree(X->d_hits);
+        if (X->d_occ) (void)hipFree(X->d_occ);
+        X->d_rays = X->d_hits = nullptr;
+        X->d_occ = nullptr;
+        X->stage_rays = 0;
+        HIP_TRY(hipMalloc((void**)&X->d_rays, (size_t)chunk * sizeof(crt_ray)));
+        HIP_TRY(hipMalloc((void**)&X->d_hits, (size_t)chunk * sizeof(crt_hit)));
+        HIP_TRY(hipMalloc((void**)&X->d_occ, (size_t)chunk));
+        X->stage_rays = chunk;
+    }
+    for (int64_t at = 0; at < n; at += chunk) {
+        const int64_t m = std::min(n - at, chunk);
+        HIP_TRY(hipMemcpy(X->d_rays, rays + at, (size_t)m * sizeof(crt_ray), hipMemcpyHostToDevice));
+        if (int rc = trace_enqueue(S, reinterpret_cast<const crt_ray*>(X->d_rays), m, opts,
+                                   hits ? reinterpret_cast<crt_hit*>(X->d_hits) : nullptr, occ ? X->d_occ : nullptr, 0,
+                                   nullptr))
+            return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        if (hits) HIP_TRY(hipMemcpy(hits + at, X->d_hits, (size_t)m * sizeof(crt_hit), hipMemcpyDeviceToHost));
+        if (occ) HIP_TRY(hipMemcpy(occ + at, X->d_occ, (size_t)m, hipMemcpyDeviceToHost));
+        if (int rc = trace_take_error(X)) return rc;
+    }
+    return CRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crt_trace_validate_rays(const crt_ray* rays, int64_t n, int64_t* first_bad) {
+    if (n < 0 || (n > 0 && !rays)) return set_error(CRT_ERR_INVALID_ARGUMENT, "null rays or n < 0");
+    for (int64_t i = 0; i < n; ++i) {
+        const crt_ray& r = rays[i];
+        const char* why = nullptr;
+        for (int a = 0; a < 3 && !why; ++a) {
+            if (!std::isfinite(r.origin[a])) why = "origin is not finite";
+            else if (!(std::fabs(r.origin[a]) < 0x1p59f)) why = "|origin| is 2^59 or more";
+            else if (!std::isfinite(r.dir[a])) why = "direction is not finite";
+        }
+        if (!why && r.dir[0] == 0.f && r.dir[1] == 0.f && r.dir[2] == 0.f) why = "direction is all zero";
+        if (!why && r.tmax != r.tmax) why = "tmax is NaN";
+        if (why) {
+            if (first_bad) *first_bad = i;
+            return set_error(CRT_ERR_INVALID_ARGUMENT, "ray " + std::to_string(i) + ": " + why);
+        }
+    }
+    return CRT_OK;
+}
+
+int crt_scene_trace(const crt_scene* S, const crt_ray* rays, int64_t n, const crt_trace_options* opts, crt_hit* hits_out) {
+    if (n > 0 && !hits_out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null hits_out");
+    return trace_host(S, rays, n, opts, hits_out, nullptr);
+}
+
+int crt_scene_occluded(const crt_scene* S, const crt_ray* rays, int64_t n, const crt_trace_options* opts, uint8_t* out) {
+    if (n > 0 && !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null out");
+    return trace_host(S, rays, n, opts, nullptr, out);
+}
+
+int crt_scene_trace_device(const crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trace_options* opts,
+                           crt_hit* d_hits, uint8_t* d_occluded, unsigned flags, void* stream) {
+    if (!S || n < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "null scene or n < 0");
+    if (n == 0) return CRT_OK;
+    if (!d_rays || (!d_hits && !d_occluded)) return set_error(CRT_ERR_INVALID_ARGUMENT, "null rays, or neither hits nor occluded");
+    return trace_enqueue(const_cast<crt_scene*>(S), d_rays, n, opts, d_hits, d_occluded, flags, (hipStream_t)stream);
+}
+
+int crt_scene_trace_last_stats(const crt_scene* S, crt_trace_stats* out) {
+    if (!S || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
+    *out = crt_trace_stats{};
+    TraceScratch* X = S->trace;
+    if (!X || !X->traced) return set_error(CRT_ERR_INVALID_ARGUMENT, "no trace on this scene yet");
+    HIP_TRY(hipSetDevice(S->device));
+    HIP_TRY(hipEventSynchronize(X->ev1));
+    HIP_TRY(hipEventElapsedTime(&out->kernel_ms, X->ev0, X->ev1));
+    unsigned long long w[TRACE_STAT_WORDS];
+    HIP_TRY(hipMemcpy(w, X->d_stats, sizeof w, hipMemcpyDeviceToHost));
+    out->rays = w[0]; out->box_tests = w[1]; out->tri_tests = w[2]; out->sphere_tests = w[3];
+    out->step_lane_slots = w[4]; out->step_active_lanes = w[5];
+    return trace_take_error(X);
+}
+
+}  // extern "C"

@@ -3,7 +3,12 @@
 // write it as PNG or binary PPM by extension (rows flipped like WindowManager::drawFrame's flipVertically).
 //
 //   crt_render [-w W] [-h H] [-spp N] [-seed S] [-o out.ppm] [-pos x y z] [-fov deg] [-bvh reference|rebuilt]
-//              [-leaf N] [-sbvh] model.obj...       (-sbvh: rebuilt tree with spatial splits)
+//              [-leaf N] [-sbvh] [-aov depth|normal|object] model.obj...   (-sbvh: rebuilt tree with spatial splits)
+//
+// -aov: instead of a frame, one ray per pixel through the pixel centre (CRT::RayQuery::centreRays: Camera::getRay with
+// u = (x + 0.5) / W, v = (y + 0.5) / H, lens offset 0) and an RGBA8 image of the closest hit, rows as for frames:
+// depth = grey 1 / (1 + t); normal = 0.5 * n + 0.5; object = a fixed 8-colour palette by object & 7; a miss is black.
+// A channel c in [0, 1] is stored as the byte (int)(255 * c + 0.5).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -14,7 +19,31 @@
 #include "crt/CUDARenderer.h"
 #include "crt/Camera.h"
 #include "crt/ImageIO.h"
+#include "crt/RayQuery.h"
 #include "crt/SceneManager.h"
+
+static uint8_t aovByte(float c) { return (uint8_t)(int)(255.0f * c + 0.5f); }
+
+// The -aov image of `hits` (row 0 = the bottom row, like CUDARenderer's frames).
+static std::vector<uint8_t> aovImage(const std::string& aov, const std::vector<crt_hit>& hits) {
+    static const uint8_t palette[8][3] = {{230, 25, 75}, {60, 180, 75}, {255, 225, 25}, {0, 130, 200},
+                                          {245, 130, 48}, {145, 30, 180}, {70, 240, 240}, {240, 50, 230}};
+    std::vector<uint8_t> img(hits.size() * 4, 0);
+    for (size_t i = 0; i < hits.size(); ++i) {
+        const crt_hit& h = hits[i];
+        uint8_t* px = img.data() + 4 * i;
+        px[3] = 255;
+        if (h.t < 0.f) continue;                                  // a miss: black
+        if (aov == "depth") {
+            px[0] = px[1] = px[2] = aovByte(1.0f / (1.0f + h.t));
+        } else if (aov == "normal") {
+            for (int c = 0; c < 3; ++c) px[c] = aovByte(0.5f * h.normal[c] + 0.5f);
+        } else {
+            for (int c = 0; c < 3; ++c) px[c] = palette[h.object & 7][c];
+        }
+    }
+    return img;
+}
 
 int main(int argc, char** argv) {
     try {
@@ -24,6 +53,7 @@ int main(int argc, char** argv) {
         float fov = 80.0f, aperture = 0.000001f;
         float pos[3] = {0.f, 0.f, 0.3f};
         std::string out = "frame.png";
+        std::string aov;
         std::vector<std::string> files;
         crt_scene_options opts{};
         for (int i = 1; i < argc; ++i) {
@@ -39,6 +69,14 @@ int main(int argc, char** argv) {
             else if (a == "-bvh") { need(1); std::string m = argv[++i]; opts.bvh = m == "rebuilt" ? CRT_BVH_REBUILT : CRT_BVH_REFERENCE; }
             else if (a == "-leaf") { need(1); opts.leaf_size = std::atoi(argv[++i]); }
             else if (a == "-sbvh") { opts.bvh = CRT_BVH_REBUILT; opts.spatial_splits = 1; }
+            else if (a == "-aov") {
+                need(1);
+                aov = argv[++i];
+                if (aov != "depth" && aov != "normal" && aov != "object") {
+                    std::fprintf(stderr, "-aov takes depth, normal or object\n");
+                    return 2;
+                }
+            }
             else files.push_back(a);
         }
         const float ASPECT_RATIO = 16.0f / 9.0f;                 // EntryPoint.cu:16-20
@@ -52,8 +90,24 @@ int main(int argc, char** argv) {
         SceneManager scene(W, H);
         scene.setModelFiles(files);
         scene.setSceneOptions(opts);
-        CUDARenderer renderer(W, H);
         auto t0 = std::chrono::steady_clock::now();
+        if (!aov.empty()) {                                       // a query needs the scene only: no renderer, no RNG state
+            scene.initializeScene(config);
+            auto t1 = std::chrono::steady_clock::now();
+            const CRT::RayQuery query(scene.getWorld());
+            const std::vector<crt_hit> hits = query.trace(CRT::RayQuery::centreRays(camera.toDesc(), W, H));
+            auto t2 = std::chrono::steady_clock::now();
+            const std::vector<uint8_t> img = aovImage(aov, hits);
+            CRT::writeImage(out, img.data(), W, H, true);
+            size_t n_hit = 0;
+            for (const crt_hit& h : hits) n_hit += h.t >= 0.f;
+            std::printf("{\"width\": %d, \"height\": %d, \"aov\": \"%s\", \"rays\": %zu, \"hits\": %zu, \"setup_s\": %.4f, "
+                        "\"query_s\": %.4f, \"kernel_ms\": %.3f, \"out\": \"%s\"}\n",
+                        W, H, aov.c_str(), hits.size(), n_hit, std::chrono::duration<double>(t1 - t0).count(),
+                        std::chrono::duration<double>(t2 - t1).count(), query.lastStats().kernel_ms, out.c_str());
+            return EXIT_SUCCESS;
+        }
+        CUDARenderer renderer(W, H);
         renderer.initialize(config, seed);
         scene.initializeScene(config, renderer.getRandState());
         auto t1 = std::chrono::steady_clock::now();
