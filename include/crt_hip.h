@@ -442,6 +442,10 @@ int crt_selftest_rcp(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* mis
  * fast square root (v_rsq_f32 + one FMA correction step, crt_device.h::sqrt_rsq) differs from the correctly rounded
  * sqrtf; first_bad = lowest such. */
 int crt_selftest_sqrt(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* mismatches, uint32_t* first_bad);
+/* Vec3::unit as the shading pass runs it, one call for all lanes of a wave: in = n x 3 floats, 64 consecutive vectors
+ * share a wave (and with it the wave-uniform choice between the fast and the IEEE square root and reciprocal);
+ * out[3*i..] = (1 / sqrt(x*x + y*y + z*z)) * v, every operation correctly rounded f32. */
+int crt_selftest_unit(const float* in, int n, float* out);
 /* Exhaustive check of next_ray's image-coordinate division for one frame dimension (width or height): counts the
  * floats a in [2^-33, dim] (every value x + U can take) for which uv_div(a, dim, RN(1/dim)) differs from IEEE a / dim.
  * crt_renderer_create runs the same check and uses uv_div only when both dimensions have none. */

@@ -132,7 +132,7 @@ HIP_SYMBOLS = [
     "crt_build_mesh_bvh", "crt_renderer_set_schedule", "crt_renderer_set_critical_tiles", "crt_renderer_set_pixel_shard",
     "crt_renderer_set_top_levels",
     "crt_selftest_math", "crt_selftest_rng", "crt_selftest_geometry", "crt_selftest_scan", "crt_selftest_rcp",
-    "crt_selftest_uv_div", "crt_selftest_sqrt",
+    "crt_selftest_uv_div", "crt_selftest_sqrt", "crt_selftest_unit",
     "crt_trace_validate_rays", "crt_scene_export_identity", "crt_scene_trace", "crt_scene_occluded",
     "crt_scene_trace_device", "crt_scene_trace_last_stats",
 ]
@@ -215,6 +215,7 @@ def hip():
             "crt_selftest_rcp": ([C.c_uint32, C.c_uint32, P, P], i32),
             "crt_selftest_uv_div": ([i32, P], i32),
             "crt_selftest_sqrt": ([C.c_uint32, C.c_uint32, P, P], i32),
+            "crt_selftest_unit": ([P, i32, P], i32),
             "crt_trace_validate_rays": ([P, C.c_int64, P], i32),
             "crt_scene_export_identity": ([P, P, P, P], i32),
             "crt_scene_trace": ([P, P, C.c_int64, P, P], i32),

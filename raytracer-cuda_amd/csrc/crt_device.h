@@ -151,7 +151,10 @@ __device__ __forceinline__ float uniform(Rng& s) { return __builtin_fmaf((float)
 // multiply fewer than the literal restatement, the same bits.
 __device__ __forceinline__ float rand_pm1(Rng& s) { return __builtin_fmaf(uniform(s), 2.0f, -1.0f); }
 
-__device__ __forceinline__ V3 rand_unit_vector(Rng& s) {   // Utility.cuh:45-53, :73-76
+// Utility::randomUnitVector in its two halves: the rejection loop (randomInUnitSphere, Utility.cuh:45-53) and the
+// normalisation (:73-76).  shade_rec normalises the sphere point together with the other materials' vectors, one
+// unit() for the whole pass.
+__device__ __forceinline__ V3 rand_in_unit_sphere(Rng& s) {
     V3 p;
     for (;;) {
         float a = rand_pm1(s);
@@ -161,7 +164,7 @@ __device__ __forceinline__ V3 rand_unit_vector(Rng& s) {   // Utility.cuh:45-53,
         if (len2(p) >= 1) continue;
         break;
     }
-    return unit(p);
+    return p;
 }
 
 // Material.cuh:132-137 with pow(float,int) restated as exponentiation by squaring.  r0 = ((1 - ref_idx) /
@@ -176,8 +179,8 @@ __device__ __forceinline__ float schlick_r0(float cosine, float r0) {
     return r0 + (1 - r0) * r;
 }
 
-__device__ __forceinline__ V3 sky(V3 d) {   // CRTUtility.cuh:34-38
-    V3 ud = unit(d);
+// CRTUtility.cuh:34-38 from the already normalised direction (shade_rec's shared unit())
+__device__ __forceinline__ V3 sky_unit(V3 ud) {
     float t = 0.5f * (ud.y + 1.0f);
     return (1.0f - t) * v3(1.0f, 1.0f, 1.0f) + t * v3(0.5f, 0.7f, 1.0f);
 }

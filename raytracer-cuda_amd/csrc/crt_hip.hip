@@ -1290,7 +1290,26 @@ struct PathState {
 #ifdef CRT_PROFILE_LOOPS
     uint32_t k1, k2, kr;   // this pass: unit-sphere candidates, unit-disk candidates, Russian-roulette draws
 #endif
+#ifdef CRT_PROFILE_SITES
+    uint32_t site;         // this pass: SITE_* bits of the blocks the lane took
+#endif
 };
+#ifdef CRT_PROFILE_SITES
+// Profiling build only (tools/build_profile_lib.sh sites -DCRT_PROFILE_SITES, tools/pass_site_count.py): which lanes
+// of a regeneration pass take the blocks that used to be issued once per lane set.  A lane marks the blocks it takes;
+// variant 8 ballots the marks per pass.  CAM_ENTRY: came into next_ray without a path and starts a sample; CAM_KILLED:
+// ended by the bounce limit or roulette inside next_ray and starts a sample (with the camera block ahead of those
+// tests this was a second trip of next_ray's loop and a second camera block).  UNIT_*: the lane needs a vector
+// normalised: the unit-sphere point (Lambert and metal), the direction for glass, the direction for the sky; REFL is
+// metal's second normalisation, which stays in its branch.
+constexpr uint32_t SITE_CAM_ENTRY = 1, SITE_CAM_KILLED = 2, SITE_UNIT_RUV = 4, SITE_UNIT_GLASS = 8, SITE_UNIT_SKY = 16,
+                   SITE_UNIT_REFL = 32;
+// Summed over variant 8's passes: [0] passes, [1] passes with a CAM_ENTRY lane, [2] with a CAM_KILLED lane, [3] with
+// both (a camera block saved), [4]-[7] passes with a RUV / GLASS / SKY / REFL lane, [8] passes with any of RUV, GLASS,
+// SKY (the shared unit() runs), [9] the number of those three present, summed (the unit() sites issued one per
+// material), [10] parked lanes, [11] lanes that take the camera block
+__device__ unsigned long long g_site_prof[12];
+#endif
 #ifdef CRT_PROFILE_LOOPS
 // Profiling build only (tools/build_profile_lib.sh loops -DCRT_PROFILE_LOOPS, tools/loop_fusion_count.py): the
 // regeneration pass's two rejection loops, counted from the XORWOW draw counter (d advances by 362437 per draw;
@@ -1311,51 +1330,23 @@ struct CamRegs {
 
 // Phase 1: give the lane a ray to trace — Camera::getRay for a new sample, the bounce-limit exit and
 // Russian roulette (CUDAKernels.h:110-121).  Returns false when the pixel has no samples left.
+//
+// A wave instruction costs its issue slot whatever the number of lanes that run it, so the camera block is written to
+// be issued once per call: the lanes that still have a path take the bounce-limit test and the roulette draw FIRST,
+// and the lanes those end join the lanes that came in without a path for one Camera::getRay.  (With the camera block
+// first, a wave holding both kinds of lane ran it twice, for disjoint lanes.)  Each lane's own sequence of draws is
+// the reference's: roulette, then the disk candidates, then the two pixel uniforms.  A new sample has bounce 0 and
+// leaves at once; only max_bounces <= 0 ends it on the spot, and the loop round the camera block is for that case alone.
 __device__ __forceinline__ bool next_ray(PathState& S, const CamRegs& C, int x, int y, int max_bounces) {
-    for (;;) {
-        if (S.need_new) {
-            if (S.remaining == 0) return false;
-            --S.remaining;
-            float da, db;                                    // Utility::randomPointInUnitDisk
-#ifdef CRT_PROFILE_LOOPS
-            const uint32_t pd0 = S.s.d;
+#ifdef CRT_PROFILE_SITES
+    if (S.need_new && S.remaining != 0) S.site |= SITE_CAM_ENTRY;
 #endif
-            for (;;) {
-                da = rand_pm1(S.s);
-                db = rand_pm1(S.s);
-                if (len2(v3(da, db, 0)) >= 1) continue;
-                break;
-            }
-#ifdef CRT_PROFILE_LOOPS
-            S.k2 += draws_since(pd0, S.s.d) / 2u;
-#endif
-            const V3 rd = C.lens * v3(da, db, 0);
-            const V3 off = v3(C.right.x * rd.x, C.right.y * rd.x, C.right.z * rd.x) +
-                           v3(C.up.x * rd.y, C.up.y * rd.y, C.up.z * rd.y);
-            const float au = (float)x + uniform(S.s);
-            const float av = (float)y + uniform(S.s);
-            float u, v;
-            if (C.fast_uv) {
-                u = uv_div(au, C.fw, C.rfw);
-                v = uv_div(av, C.fh, C.rfh);
-            } else {
-                __asm__ volatile("");   // a real branch: no if-conversion that would run both divisions
-                u = au / C.fw;
-                v = av / C.fh;
-            }
-            S.o = C.pos + off;
-            S.d = (((C.llc + u * C.hor) + v * C.ver) - C.pos) - off;
-            S.thr = v3(1.0f, 1.0f, 1.0f);
-            S.bounce = 0;
-            S.need_new = false;
-        }
+    if (!S.need_new) {
         if (S.bounce >= max_bounces) {                      // loop exhausted: final_color = 0
             S.pixel = S.pixel + v3(0.0f, 0.0f, 0.0f);
             ++S.paths;
             S.need_new = true;
-            continue;
-        }
-        if (S.bounce >= 3) {
+        } else if (S.bounce >= 3) {
             float p = fmaxf(S.thr.x, fmaxf(S.thr.y, S.thr.z));
             p = fminf(p, 0.95f);
 #ifdef CRT_PROFILE_LOOPS
@@ -1365,11 +1356,54 @@ __device__ __forceinline__ bool next_ray(PathState& S, const CamRegs& C, int x, 
                 S.pixel = S.pixel + v3(0.0f, 0.0f, 0.0f);
                 ++S.paths;
                 S.need_new = true;
-                continue;
+            } else {
+                S.thr = recip_exact_wave(p) * S.thr;   // 1 / p, exact (crt_device.h)
             }
-            S.thr = recip_exact_wave(p) * S.thr;   // 1 / p, exact (crt_device.h)
         }
-        return true;
+        if (!S.need_new) return true;
+#ifdef CRT_PROFILE_SITES
+        if (S.remaining != 0) S.site |= SITE_CAM_KILLED;
+#endif
+    }
+    for (;;) {
+        if (S.remaining == 0) return false;
+        --S.remaining;
+        float da, db;                                    // Utility::randomPointInUnitDisk
+#ifdef CRT_PROFILE_LOOPS
+        const uint32_t pd0 = S.s.d;
+#endif
+        for (;;) {
+            da = rand_pm1(S.s);
+            db = rand_pm1(S.s);
+            if (len2(v3(da, db, 0)) >= 1) continue;
+            break;
+        }
+#ifdef CRT_PROFILE_LOOPS
+        S.k2 += draws_since(pd0, S.s.d) / 2u;
+#endif
+        const V3 rd = C.lens * v3(da, db, 0);
+        const V3 off = v3(C.right.x * rd.x, C.right.y * rd.x, C.right.z * rd.x) +
+                       v3(C.up.x * rd.y, C.up.y * rd.y, C.up.z * rd.y);
+        const float au = (float)x + uniform(S.s);
+        const float av = (float)y + uniform(S.s);
+        float u, v;
+        if (C.fast_uv) {
+            u = uv_div(au, C.fw, C.rfw);
+            v = uv_div(av, C.fh, C.rfh);
+        } else {
+            __asm__ volatile("");   // a real branch: no if-conversion that would run both divisions
+            u = au / C.fw;
+            v = av / C.fh;
+        }
+        S.o = C.pos + off;
+        S.d = (((C.llc + u * C.hor) + v * C.ver) - C.pos) - off;
+        S.thr = v3(1.0f, 1.0f, 1.0f);
+        S.bounce = 0;
+        S.need_new = false;
+        if (max_bounces > 0) return true;                   // uniform
+        S.pixel = S.pixel + v3(0.0f, 0.0f, 0.0f);           // max_bounces <= 0: the sample ends at the bounce limit
+        ++S.paths;
+        S.need_new = true;
     }
 }
 
@@ -1409,38 +1443,47 @@ __device__ __forceinline__ void shade(PathState& S, const RenderParams& P, int h
 }
 __device__ __forceinline__ void shade_rec(PathState& S, const RenderParams& P, int hit_rank, float t, float4 r0,
                                           float4 m, bool staged, float inv_r) {
-    if (hit_rank < 0) {                                  // :137-142
-        S.pixel = S.pixel + S.thr * sky(S.d);
-        ++S.paths;
-        S.need_new = true;
-        return;
-    }
+    // A miss has no record (r0 = m = 0); SHADE_MISS keeps it out of every material's branch below
+    constexpr uint32_t SHADE_MISS = 15;
+    const bool miss = hit_rank < 0;
     const uint32_t kind = __float_as_uint(r0.w);
     const V3 hp = S.o + t * S.d;                         // Ray::pointAtDistance
     V3 outward = v3(r0.x, r0.y, r0.z);                   // triangle: unit(cross(e1, e2)), Mesh.cuh:303-304
-    if (kind & SHADE_SPHERE) {                           // Sphere.cuh:44: (1 / radius) * (p - center)
+    if (!miss && (kind & SHADE_SPHERE)) {                // Sphere.cuh:44: (1 / radius) * (p - center)
         const float ir = staged ? inv_r : P.shade[3u * (uint32_t)hit_rank + 2u].x;
         outward = ir * (hp - outward);
     }
     const bool front = dot(S.d, outward) < 0;            // HitInfo::setFaceNormal
     const V3 n = front ? outward : -outward;
-    const uint32_t code = kind & 15u;
-    if (code == SHADE_INVALID) {                         // :127 invalid material: same ray again
-        ++S.bounce;
-        return;
-    }
-    // Lambertian and Metal both draw one randomUnitVector first (their only draws): one rejection loop for
-    // both, so a wave holding both materials does not run the loop twice.
-    V3 ruv;
+    const uint32_t code = miss ? SHADE_MISS : kind & 15u;
+    // One normalisation for the whole pass.  Four places of the reference normalise a vector first: randomUnitVector
+    // (Lambertian and Metal, their only draws: one rejection loop for both), Dielectric::scatter and the sky the ray's
+    // direction.  Issued once per material they cost the wave one unit() each, for disjoint lanes; here every lane
+    // picks its vector, one unit() runs over the union of those lanes, and the materials go on from its result.  The
+    // square root and the reciprocal choose their fast or their IEEE sequence by a ballot over the lanes that run
+    // them; both sequences are correctly rounded, so the wider lane set changes no bit.
+    V3 q = S.d;                                          // dielectric, sky (CRTUtility.cuh:35)
 #ifdef CRT_PROFILE_LOOPS
     const uint32_t pd0 = S.s.d;
 #endif
-    if (code == SHADE_LAMBERT || code == SHADE_METAL) ruv = rand_unit_vector(S.s);
+    if (code == SHADE_LAMBERT || code == SHADE_METAL) q = rand_in_unit_sphere(S.s);
 #ifdef CRT_PROFILE_LOOPS
     S.k1 += draws_since(pd0, S.s.d) / 3u;
 #endif
-    if (code == SHADE_LAMBERT) {                         // Material.cuh:66-77
-        V3 sd = n + ruv;
+#ifdef CRT_PROFILE_SITES
+    S.site |= code <= SHADE_METAL ? SITE_UNIT_RUV : code == SHADE_DIELECTRIC ? SITE_UNIT_GLASS : miss ? SITE_UNIT_SKY : 0u;
+    if (code == SHADE_METAL) S.site |= SITE_UNIT_REFL;
+#endif
+    V3 uq = q;
+    if (code <= SHADE_DIELECTRIC || miss) uq = unit(q);  // Lambert, metal, dielectric, sky
+    if (miss) {                                          // :137-142
+        S.pixel = S.pixel + S.thr * sky_unit(uq);
+        ++S.paths;
+        S.need_new = true;
+    } else if (code == SHADE_INVALID) {                  // :127 invalid material: same ray again
+        ++S.bounce;
+    } else if (code == SHADE_LAMBERT) {                  // Material.cuh:66-77
+        V3 sd = n + uq;
         if (fabsf(sd.x) < 1e-8f && fabsf(sd.y) < 1e-8f && fabsf(sd.z) < 1e-8f) sd = n;
         S.thr = S.thr * v3(m.x, m.y, m.z);
         S.o = hp;
@@ -1448,7 +1491,7 @@ __device__ __forceinline__ void shade_rec(PathState& S, const RenderParams& P, i
         ++S.bounce;
     } else if (code == SHADE_METAL) {                    // :89-96
         V3 refl = reflect(S.d, n);
-        refl = unit(refl) + (m.w * ruv);
+        refl = unit(refl) + (m.w * uq);
         if (dot(refl, n) > 0) {
             S.thr = S.thr * v3(m.x, m.y, m.z);
             S.o = hp;
@@ -1462,7 +1505,7 @@ __device__ __forceinline__ void shade_rec(PathState& S, const RenderParams& P, i
     } else if (code == SHADE_DIELECTRIC) {               // :109-128
         const float ri = front ? m.y : m.x;              // 1.0f / ior (front face) or ior, from the shading record
         const float r0 = front ? m.z : m.w;              // Schlick's r0 for that ri
-        const V3 ud = unit(S.d);
+        const V3 ud = uq;                                // unit(S.d)
         const float cos_theta = fminf(dot(-ud, n), 1.0f);
         const bool cannot_refract = cannot_refract_exact(cos_theta, ri);
         V3 dir;
@@ -1612,6 +1655,10 @@ __global__ __launch_bounds__(64 * KernelShape<VARIANT>::waves, MINW) void crt_re
 #ifdef CRT_PROFILE_LOOPS
     S.k1 = S.k2 = S.kr = 0;
     unsigned long long lp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+#ifdef CRT_PROFILE_SITES
+    S.site = 0;
+    unsigned long long sites[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     if (valid && !PERSIST) {
         const uint32_t* r = P.rng + 6 * (size_t)pix;
@@ -1887,6 +1934,20 @@ __global__ __launch_bounds__(64 * KernelShape<VARIANT>::waves, MINW) void crt_re
                     lp[7] += (unsigned long long)n_parked;
                 }
 #endif
+#ifdef CRT_PROFILE_SITES
+                {
+                    const uint32_t st = S.site;   // only this pass's parked lanes have marks
+                    S.site = 0;
+                    const bool entry = wave_ballot(st & SITE_CAM_ENTRY) != 0, killed = wave_ballot(st & SITE_CAM_KILLED) != 0;
+                    const bool ruv = wave_ballot(st & SITE_UNIT_RUV) != 0, glass = wave_ballot(st & SITE_UNIT_GLASS) != 0;
+                    const bool sky = wave_ballot(st & SITE_UNIT_SKY) != 0, refl = wave_ballot(st & SITE_UNIT_REFL) != 0;
+                    sites[0] += 1; sites[1] += entry; sites[2] += killed; sites[3] += entry && killed;
+                    sites[4] += ruv; sites[5] += glass; sites[6] += sky; sites[7] += refl;
+                    sites[8] += ruv || glass || sky; sites[9] += (int)ruv + (int)glass + (int)sky;
+                    sites[10] += (unsigned long long)n_parked;
+                    sites[11] += (unsigned long long)__popcll(wave_ballot(st & (SITE_CAM_ENTRY | SITE_CAM_KILLED)));
+                }
+#endif
                 live_mask = wave_ballot(has_result);
                 if constexpr (kProfilePass) {
                     // the pass's section timers ran in divergent code, so each lane's accumulators hold only the passes
@@ -2025,6 +2086,10 @@ __global__ __launch_bounds__(64 * KernelShape<VARIANT>::waves, MINW) void crt_re
 #ifdef CRT_PROFILE_LOOPS
     if (lane == 0 && !P.probe_cost)
         for (int k = 0; k < 8; ++k) atomicAdd(&g_loop_prof[k], lp[k]);
+#endif
+#ifdef CRT_PROFILE_SITES
+    if (lane == 0 && !P.probe_cost)
+        for (int k = 0; k < 12; ++k) atomicAdd(&g_site_prof[k], sites[k]);
 #endif
 #ifdef CRT_PROFILE_WAVE_TIMES
     {
@@ -2214,6 +2279,17 @@ __global__ __launch_bounds__(256) void crt_selftest_sqrt_kernel(uint32_t lo, uin
         if (b > 0xffffffffu - stride) break;
     }
     if (nbad) atomicAdd(bad, nbad);
+}
+
+// unit() as shade_rec runs it: one call for all the lanes of a wave (in: n x 3 floats, one wave per 64 vectors), so the
+// wave-uniform choice between the fast and the IEEE square root and reciprocal is made over whatever mix of lengths
+// the caller puts into a wave.
+__global__ __launch_bounds__(64) void crt_selftest_unit_kernel(const float* __restrict__ in, int n,
+                                                               float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const V3 u = unit(v3(in[3 * i], in[3 * i + 1], in[3 * i + 2]));
+    out[3 * i] = u.x; out[3 * i + 1] = u.y; out[3 * i + 2] = u.z;
 }
 
 // Exhaustive check of next_ray's division for one frame dimension b: every float a in [lo, hi] (all values (x + U) can
@@ -4282,6 +4358,18 @@ extern "C" int crt_profile_loop_counts(unsigned long long* out8, int reset) {
     return CRT_OK;
 }
 #endif
+#ifdef CRT_PROFILE_SITES
+extern "C" int crt_profile_site_counts(unsigned long long* out12, int reset) {
+    if (!out12) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out12, HIP_SYMBOL(g_site_prof), 12 * 8, 0, hipMemcpyDeviceToHost));
+    if (reset) {
+        static const unsigned long long zero[12] = {};
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_site_prof), zero, sizeof zero, 0, hipMemcpyHostToDevice));
+    }
+    return CRT_OK;
+}
+#endif
 #ifdef CRT_PROFILE_CRIT_TRACE
 // out: 2 x 16384 trace words, then 2 x n_waves HW words
 extern "C" int crt_profile_crit_trace(unsigned long long* trace, unsigned* hw, int n_waves) {
@@ -4422,6 +4510,21 @@ int crt_selftest_sqrt(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* mi
     HIP_TRY(hipMemcpy(first_bad, dfirst, 4, hipMemcpyDeviceToHost));
     (void)hipFree(dbad);
     (void)hipFree(dfirst);
+    return CRT_OK;
+}
+
+int crt_selftest_unit(const float* in, int n, float* out) {
+    if (!in || !out || n <= 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (int rc = use_device(0)) return rc;
+    float *din, *dout;
+    HIP_TRY(hipMalloc((void**)&din, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void**)&dout, (size_t)n * 12));
+    HIP_TRY(hipMemcpy(din, in, (size_t)n * 12, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(crt_selftest_unit_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, din, n, dout);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 12, hipMemcpyDeviceToHost));
+    (void)hipFree(din);
+    (void)hipFree(dout);
     return CRT_OK;
 }
 
