@@ -286,6 +286,51 @@ int crt_scene_trace_device(const crt_scene* scene, const crt_ray* d_rays, int64_
  * never count; mode 1 over a 4-wide scene counts rays only). */
 int crt_scene_trace_last_stats(const crt_scene* scene, crt_trace_stats* out);
 
+/* ---- path steps (no reference counterpart: the reference keeps them inside rayColor) ----
+ * What a path tracer does between two ray queries, over batches (DESIGN.md "Path steps"): camera rays on the pixels'
+ * own RNG streams, and one bounce of material scattering with the bounce limit and Russian roulette.  With
+ * crt_scene_trace_device in between they form a wavefront path tracer whose sums, RNG state and ray count equal
+ * crt_renderer_render's bit for bit: every lane draws in the render kernels' order (disk candidates, the two pixel
+ * uniforms, then per bounce the roulette draw, the trace, the material's draws), and a pixel's sum receives the same
+ * additions in the same order, the + (0, 0, 0) of a killed path included.
+ * RNG state and sums have the renderer's layouts: 6 words per pixel (v[5], d) and W*H*3 floats, both indexed by pixel,
+ * so the entries run on crt_renderer_rng_device_ptr / crt_renderer_linear_device_ptr (or an attached buffer) and
+ * crt_renderer_init_rand / crt_renderer_resolve serve them unchanged.  Both device entries are asynchronous on
+ * `stream`; rays, hits and paths are 16-B aligned device arrays; n == 0 is CRT_OK with nothing launched; a null
+ * pointer, n < 0 or n >= 2^31 is CRT_ERR_INVALID_ARGUMENT, checked before any device use.  These entries joined ABI
+ * version 3 after its first release: a caller that may meet an older library looks the symbols up. */
+/* One path of a batch; two 16-B rows like crt_ray / crt_hit. */
+typedef struct crt_path { float throughput[3]; int32_t bounce; int32_t pixel; int32_t status; int32_t reserved[2]; } crt_path;
+#define CRT_PATH_ACTIVE 0
+#define CRT_PATH_ENDED  1
+/* Camera::getRay (Camera.cuh:32-44) for n pixels of the renderer's frame, each on its own RNG stream: the unit-disk
+ * rejection loop, then the two pixel uniforms, exactly the render kernels' camera block (with the fast or IEEE u, v
+ * division the renderer chose for its frame size).  d_pixels[k] = y * width + x (NULL: pixels 0..n-1); no pixel may
+ * appear twice in one call.  d_rng NULL = the renderer's own state.  Writes rays[k] = (o, +inf, d, 0) and paths[k] =
+ * {(1, 1, 1), 0, pixel, CRT_PATH_ACTIVE}.  A pixel outside the frame draws nothing and gets a CRT_PATH_ENDED path.
+ * CRT_ERR_INVALID_ARGUMENT for a renderer without a camera. */
+int crt_renderer_camera_rays_device(crt_renderer* r, const int32_t* d_pixels, int64_t n, uint32_t* d_rng,
+                                    crt_ray* d_rays, crt_path* d_paths, void* stream);
+/* One bounce for n paths: rayColor's loop body after the hit query (CUDAKernels.h:123-142, Material.cuh:66-146), then
+ * the NEXT iteration's bounce-limit test and Russian roulette (:110-121; nothing draws between the two).  hits[k] is
+ * the crt_hit of rays[k] as the ray queries write it for tmax = +inf (t < 0: a miss, the sky): the step reads t,
+ * material, normal and front_face; hit point = o + t * d, shading normal = front_face ? normal : -normal.  A material
+ * index outside the scene's materials is the reference's invalid-material bounce (the same ray again, ++bounce).
+ * A path that continues gets its scattered ray in rays[k] (tmax = +inf), its throughput and bounce updated and stays
+ * CRT_PATH_ACTIVE.  One that ends -- sky, light, absorbed metal, bounce limit, roulette -- adds its contribution,
+ * possibly (0, 0, 0), to d_linear[3 * pixel ..], keeps its ray and becomes CRT_PATH_ENDED.  Entries that come in
+ * CRT_PATH_ENDED, or whose pixel is outside [0, n_pixels), are left untouched (ray, path, RNG, sum).  d_rng and
+ * d_linear hold n_pixels pixels.  No two active entries of one call may name the same pixel.  max_bounces >= 1. */
+int crt_scene_path_step_device(const crt_scene* scene, crt_ray* d_rays, const crt_hit* d_hits, crt_path* d_paths,
+                               int64_t n, int max_bounces, uint32_t* d_rng, float* d_linear, int64_t n_pixels,
+                               void* stream);
+/* Host only, no GPU (like crt_scene_export_identity): the per-material rows the step kernel reads, n_materials x 8
+ * floats = (code, 0, 0, 0) (payload): code (int bits) 0 lambertian, 1 metal, 2 dielectric, 3 light, 4 unknown type
+ * (emits 0); payload (albedo.xyz, 0), (albedo.xyz, min(roughness, 1)), (ior, 1 / ior, r0(1 / ior), r0(ior)) with
+ * Schlick's r0(ri) = ((1 - ri) / (1 + ri))^2, (emission.xyz, 0), zeros -- the payloads of the render kernels' shading
+ * records, from the same host function.  out == NULL: only *n_materials is set. */
+int crt_scene_export_shade_rows(const crt_scene_desc* desc, float* out, int64_t* n_materials);
+
 /* ---- renderer (CUDARenderer) ---- */
 int  crt_renderer_create(int width, int height, int device, crt_renderer** out);
 void crt_renderer_destroy(crt_renderer* r);

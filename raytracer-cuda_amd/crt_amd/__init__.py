@@ -344,6 +344,12 @@ class Scene:
         check(_lib.hip().crt_scene_trace_last_stats(self.h, C.byref(s)), "crt_scene_trace_last_stats")
         return {k: (float if k == "kernel_ms" else int)(getattr(s, k)) for k, _ in _lib.TraceStats._fields_}
 
+    # ---- path steps (crt_hip.h "path steps", DESIGN.md "Path steps")
+    def path_step(self, rays, hits, paths, max_bounces, rng, linear):
+        """One bounce of material scattering for a batch of paths, in place on torch tensors (paths.path_step)."""
+        from . import paths as _paths
+        _paths.path_step(self, rays, hits, paths, max_bounces, rng, linear)
+
 
 def load_scene(obj_files, device: int = 0, **upload_options):
     hs = HostScene(obj_files)
@@ -516,6 +522,9 @@ class Renderer:
 
     def linear_device_ptr(self) -> int:
         return int(_lib.hip().crt_renderer_linear_device_ptr(self.h) or 0)
+
+    def rng_device_ptr(self) -> int:
+        return int(_lib.hip().crt_renderer_rng_device_ptr(self.h) or 0)
 
     def render_frame(self, scene: Scene, spp: int, max_bounces: int = 20, seed: int = 41, subsequence_base: int = 0,
                      stream=None):
@@ -693,3 +702,7 @@ def build_mesh_bvh(positions, indices, face_materials, device=None):
             raise err
         ms = t.value
     return nodes[:cnt.value], idx, fm, box, ms
+
+
+from . import paths  # noqa: E402  (path steps: camera_rays, Scene.path_step, the wavefront driver paths.render)
+from .paths import camera_rays  # noqa: E402

@@ -115,6 +115,14 @@ class TraceStats(C.Structure):       # crt_hip.h crt_trace_stats
 
 TRACE_COUNT_WORK = 1     # crt_scene_trace_device flags
 
+
+class Path(C.Structure):             # crt_hip.h crt_path: two 16-B rows
+    _fields_ = [("throughput", C.c_float * 3), ("bounce", C.c_int32), ("pixel", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+PATH_ACTIVE, PATH_ENDED = 0, 1       # crt_path.status
+
 # exported symbol lists (checked by tests against include/*.h)
 HIP_SYMBOLS = [
     "crt_abi_version", "crt_build_flags", "crt_last_error", "crt_device_count", "crt_scene_create", "crt_scene_create_ex", "crt_scene_get_stats", "crt_scene_compare", "crt_scene_compare_dump", "crt_scene_export",
@@ -135,7 +143,12 @@ HIP_SYMBOLS = [
     "crt_selftest_uv_div", "crt_selftest_sqrt", "crt_selftest_unit",
     "crt_trace_validate_rays", "crt_scene_export_identity", "crt_scene_trace", "crt_scene_occluded",
     "crt_scene_trace_device", "crt_scene_trace_last_stats",
+    "crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
 ]
+# Entries that joined ABI version 3 after its first release (the path steps): bound when the loaded library has them, so
+# an older build of the same ABI still loads; their Python front-ends raise CrtError through require() otherwise.
+OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows")
+
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
     "crth_scene_loader_arrays", "crth_camera", "crth_last_error", "crth_encode_image", "crth_write_image",
@@ -222,10 +235,15 @@ def hip():
             "crt_scene_occluded": ([P, P, C.c_int64, P, P], i32),
             "crt_scene_trace_device": ([P, P, C.c_int64, P, P, P, C.c_uint, P], i32),
             "crt_scene_trace_last_stats": ([P, P], i32),
+            "crt_renderer_camera_rays_device": ([P, P, C.c_int64, P, P, P, P], i32),
+            "crt_scene_path_step_device": ([P, P, P, P, C.c_int64, i32, P, P, C.c_int64, P], i32),
+            "crt_scene_export_shade_rows": ([P, P, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):
                 continue   # an A/B build of an older revision: self-tests added since then are absent
+            if name in OPTIONAL_SYMBOLS and not hasattr(L, name):
+                continue   # an older build of this ABI version: require() reports the missing entry when it is used
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = res
@@ -270,6 +288,15 @@ def host():
             fn.restype = res
         _host = L
     return _host
+
+
+def require(name: str, lib=None):
+    """The optional entry `name` of the loaded HIP library (OPTIONAL_SYMBOLS), or CrtError naming it."""
+    L = hip() if lib is None else lib
+    if not hasattr(L, name):
+        raise CrtError(f"{HIP_LIB} does not export {name}: it was built before the path steps were added "
+                       "(rebuild the library)")
+    return getattr(L, name)
 
 
 def check(rc: int, what: str = "") -> None:

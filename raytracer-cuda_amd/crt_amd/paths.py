@@ -1,0 +1,234 @@
+"""Path steps over ray batches (crt_hip.h "path steps"): what a path tracer does between two ray
+queries, as device calls on torch tensors.
+
+  camera_rays(renderer, pixels)        Camera::getRay for a batch of pixels, each on its own RNG stream
+  Scene.path_step(rays, hits, paths,   one bounce: the materials, the sky, the invalid-material re-loop, then the
+                  max_bounces, rng,    bounce limit and Russian roulette of the bounce that follows
+                  linear)
+  render(scene, renderer, spp)         the reference driver: a wavefront path tracer out of camera_rays, Scene.trace
+                                       and Scene.path_step whose sums, RNG state and ray count equal Renderer.render's
+                                       bit for bit; on_bounce is the hook of a custom integrator
+
+Everything is torch-only (the purpose is device-resident integrators), enqueued on torch's current stream, without a
+host copy.  Tensors: rays float32 [n, 8] (crt_ray rows), hits float32 or int32 [n, 8] (crt_hit rows, Scene.trace's
+"f32"), paths int32 or float32 [n, 8] (crt_path rows: throughput.xyz as float bits, bounce, pixel, status, 0, 0),
+rng int32 [pixels, 6], linear float32 [pixels * 3] in any shape; or the Renderer itself for its own state and sums.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import PATH_ACTIVE, PATH_ENDED, check
+
+# columns of a crt_path row viewed as int32
+PATH_BOUNCE, PATH_PIXEL, PATH_STATUS = 3, 4, 5
+
+
+def _rows(x, name, dtypes):
+    """x is a contiguous [n, 8] tensor of one of `dtypes`, or ValueError."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if x.dtype not in dtypes or x.dim() != 2 or x.shape[1] != 8 or not x.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [n, 8] tensor of {' or '.join(str(d) for d in dtypes)}")
+    return x
+
+
+def _flat(x, name, dtype, numel=None, multiple=1):
+    """x is a contiguous tensor of `dtype` with `numel` elements (or a multiple), or ValueError."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor or the Renderer")
+    if x.dtype != dtype or not x.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor")
+    if (numel is not None and x.numel() != numel) or x.numel() % multiple:
+        raise ValueError(f"{name} has {x.numel()} elements, expected "
+                         f"{numel if numel is not None else 'a multiple of ' + str(multiple)}")
+    return x
+
+
+def _on_device(device, **tensors):
+    """Checked last, so that a tensor wrong in kind is reported as that: every tensor lives on cuda:`device`."""
+    for name, x in tensors.items():
+        if x is not None and (not x.is_cuda or x.device.index != device):
+            raise ValueError(f"{name} must be on cuda:{device}")
+
+
+def _is_renderer(x) -> bool:
+    from . import Renderer
+    return isinstance(x, Renderer)
+
+
+def camera_rays(renderer, pixels=None, rng=None):
+    """Camera rays of a batch of pixels (crt_renderer_camera_rays_device): each pixel's next sample, drawn on its own
+    RNG stream exactly as the render kernels draw it.  pixels: int32 [n] of y * width + x on the renderer's device, no
+    pixel twice (None: every pixel, in order); rng: int32 [width * height, 6] (None: the renderer's own state).
+    Returns (rays float32 [n, 8], paths int32 [n, 8]): paths start with throughput (1, 1, 1), bounce 0, ACTIVE."""
+    import torch
+    dev = renderer.device
+    n_pix = renderer.width * renderer.height
+    if pixels is not None:
+        _flat(pixels, "pixels", torch.int32)
+        if pixels.dim() != 1:
+            raise ValueError("pixels must be one-dimensional")
+    if rng is not None:
+        _flat(rng, "rng", torch.int32, numel=6 * n_pix)
+    _on_device(dev, pixels=pixels, rng=rng)
+    fn = _lib.require("crt_renderer_camera_rays_device")
+    n = n_pix if pixels is None else pixels.shape[0]
+    tdev = torch.device("cuda", dev)
+    rays = torch.empty((n, 8), dtype=torch.float32, device=tdev)
+    paths = torch.empty((n, 8), dtype=torch.int32, device=tdev)
+    check(fn(renderer.h, None if pixels is None else pixels.data_ptr(), n, None if rng is None else rng.data_ptr(),
+             rays.data_ptr(), paths.data_ptr(), torch.cuda.current_stream(tdev).cuda_stream),
+          "crt_renderer_camera_rays_device")
+    return rays, paths
+
+
+def path_step(scene, rays, hits, paths, max_bounces, rng, linear):
+    """One bounce for every ACTIVE path, in place (crt_scene_path_step_device): rays[k] scattered off hits[k] by the
+    hit's material, or ended into linear[3 * pixel ..] (sky, light, absorbed metal, bounce limit, roulette); paths[k]
+    gets the new throughput, bounce and status.  hits: Scene.trace(rays)["f32"] of the same rays (tmax = inf).  rng,
+    linear: tensors (see the module text), or the Renderer for its own.  No two active paths on the same pixel."""
+    import torch
+    dev = scene.device
+    _rows(rays, "rays", (torch.float32,))
+    _rows(hits, "hits", (torch.float32, torch.int32))
+    _rows(paths, "paths", (torch.int32, torch.float32))
+    if not (rays.shape[0] == hits.shape[0] == paths.shape[0]):
+        raise ValueError("rays, hits and paths differ in length")
+    if int(max_bounces) < 1:
+        raise ValueError("max_bounces must be >= 1")
+    n_pix = None
+    for name, x, dtype, per in (("rng", rng, torch.int32, 6), ("linear", linear, torch.float32, 3)):
+        if _is_renderer(x):
+            if x.device != dev:
+                raise ValueError(f"{name}: the renderer is on another device than the scene")
+            k = x.width * x.height
+        else:
+            k = _flat(x, name, dtype, multiple=per).numel() // per
+        if n_pix is not None and k != n_pix:
+            raise ValueError(f"rng holds {n_pix} pixels, linear {k}")
+        n_pix = k
+    _on_device(dev, rays=rays, hits=hits, paths=paths, rng=None if _is_renderer(rng) else rng,
+               linear=None if _is_renderer(linear) else linear)
+    fn = _lib.require("crt_scene_path_step_device")
+    d_rng = rng.rng_device_ptr() if _is_renderer(rng) else rng.data_ptr()
+    d_linear = linear.linear_device_ptr() if _is_renderer(linear) else linear.data_ptr()
+    check(fn(scene.h, rays.data_ptr(), hits.data_ptr(), paths.data_ptr(), rays.shape[0], int(max_bounces), d_rng,
+             d_linear, n_pix, torch.cuda.current_stream(rays.device).cuda_stream), "crt_scene_path_step_device")
+
+
+def shade_rows(desc) -> np.ndarray:
+    """The per-material rows the step kernel reads (crt_scene_export_shade_rows; host only), float32 [materials, 2, 4]:
+    row 0 = (code as int bits, 0, 0, 0), row 1 = the payload."""
+    fn = _lib.require("crt_scene_export_shade_rows")
+    n = C.c_int64(0)
+    check(fn(C.byref(desc), None, C.byref(n)), "crt_scene_export_shade_rows")
+    out = np.zeros((n.value, 2, 4), np.float32)
+    check(fn(C.byref(desc), out.ctypes.data_as(C.c_void_p), C.byref(n)), "crt_scene_export_shade_rows")
+    return out
+
+
+class _Phases:
+    """Device time per phase of the driver's iterations, from torch events recorded on the current stream (only when the
+    caller asked for a profile; nothing is recorded or waited for otherwise)."""
+
+    def __init__(self, rows):
+        self.rows, self.marks = rows, []
+
+    def mark(self, name, **info):
+        if self.rows is not None:
+            import torch
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.marks.append((name, ev, info))
+
+    def close(self):
+        """One row per iteration: its info and the milliseconds of each phase (the time since the previous mark, the
+        device's idle time while the host sizes the next batch included)."""
+        if self.rows is None or not self.marks:
+            return
+        self.marks[-1][1].synchronize()
+        row = None
+        for (_, e0, _), (name, e1, info) in zip(self.marks, self.marks[1:]):
+            if name == "trace":
+                row = {}
+                self.rows.append(row)
+            if row is not None:
+                row[name + "_ms"] = row.get(name + "_ms", 0.0) + e0.elapsed_time(e1)
+                row.update({k: int(v) for k, v in info.items()})      # device scalars are read only now
+
+
+def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None, trace_options=None,
+           profile=None) -> dict:
+    """The reference driver: spp samples per pixel as a wavefront of camera_rays / Scene.trace / Scene.path_step calls on
+    the renderer's own RNG state and (fresh) sums, so renderer.linear(), rng_state() and resolve() work afterwards
+    and hold what renderer.render(scene, spp, max_bounces) leaves, bit for bit.
+
+    regenerate=True: a path that ends while its pixel has samples left is replaced by that pixel's next camera ray in
+    the same iteration, and the batch is compacted with torch indexing; False: sample by sample, each until its last
+    path ends.  on_bounce(rays, hits, paths) runs between the trace and the step of every iteration (the hook of a
+    custom integrator; it may edit the tensors in place).  trace_options: keywords of Scene.trace (mode, grid_waves,
+    ...).  profile: a list that receives one dict per iteration, its entries (n, ended) and the device milliseconds of
+    its phases (trace, step, select, camera, compact; tools/path_bench.py).
+    Returns {"rays": rays traced, "iterations": trace / step rounds}."""
+    import torch
+    spp, max_bounces = int(spp), int(max_bounces)
+    if max_bounces < 1:
+        raise ValueError("max_bounces must be >= 1")
+    opts = dict(trace_options or {})
+    n_pix = renderer.width * renderer.height
+    tdev = torch.device("cuda", renderer.device)
+    renderer.write_linear(np.zeros((renderer.height, renderer.width, 3), np.float32))   # a render starts from 0
+    total = iterations = 0
+    phases = _Phases(profile)
+
+    def bounce(rays, paths):
+        phases.mark("start")
+        hits = scene.trace(rays, **opts)["f32"]
+        phases.mark("trace", n=rays.shape[0])
+        if on_bounce is not None:
+            on_bounce(rays, hits, paths)
+        path_step(scene, rays, hits, paths, max_bounces, renderer, renderer)
+        phases.mark("step")
+
+    if regenerate and spp > 0:
+        remaining = torch.full((n_pix,), spp - 1, dtype=torch.int32, device=tdev)   # samples not yet started
+        rays, paths = camera_rays(renderer)
+        while rays.shape[0]:
+            total += rays.shape[0]
+            iterations += 1
+            bounce(rays, paths)
+            ended = paths[:, PATH_STATUS] == PATH_ENDED
+            again = ended & (remaining[paths[:, PATH_PIXEL].long()] > 0)
+            idx = again.nonzero().squeeze(1)
+            new = None
+            if idx.numel():
+                pix = paths[idx, PATH_PIXEL].contiguous()
+                remaining[pix.long()] -= 1
+                phases.mark("select")
+                new = camera_rays(renderer, pix)
+                phases.mark("camera")
+                rays[idx], paths[idx] = new
+            keep = ~ended | again
+            rays, paths = rays[keep], paths[keep]
+            phases.mark("compact", ended=ended.sum() if profile is not None else 0)
+    elif spp > 0:
+        for _ in range(spp):
+            phases.mark("start")
+            rays, paths = camera_rays(renderer)
+            phases.mark("camera")
+            while rays.shape[0]:
+                total += rays.shape[0]
+                iterations += 1
+                bounce(rays, paths)
+                keep = paths[:, PATH_STATUS] == PATH_ACTIVE
+                n_before = rays.shape[0]
+                rays, paths = rays[keep], paths[keep]
+                phases.mark("compact", ended=n_before - rays.shape[0])
+    phases.close()
+    return {"rays": total, "iterations": iterations}

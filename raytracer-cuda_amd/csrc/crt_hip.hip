@@ -3160,6 +3160,7 @@ struct crt_scene {
     long excluded = 0;
     int4* d_ident = nullptr;       // ray queries: per rank (object, primitive, material, 0), see identity_table
     struct TraceScratch* trace = nullptr;   // ray queries: scratch of the handle, allocated on first use (crt_trace.h)
+    float4* d_mat_rows = nullptr;  // path steps: per material (code, 0, 0, 0) (payload), see material_shade_rows
 };
 void crtx_free_trace_scratch(crt_scene* S);
 
@@ -3339,6 +3340,44 @@ int crt_scene_export(const crt_scene_desc* D, const crt_scene_options* opts, flo
 // Per-rank shading records (layout in crt_device.h).  The triangle normal is unit(cross(e1, e2)) in the
 // device's f32 operation order (the library is compiled with -ffp-contract=off and IEEE sqrt / division on
 // the host too), so the record holds exactly the value shade() used to compute per hit.
+// What shade() needs of material `mat`: its SHADE_* code and payload (crt_device.h); an index outside the scene's
+// materials is SHADE_INVALID.  The one source of the per-rank shading records and of the per-material rows of the path
+// steps (crt_paths.h), so both hold the same bits.
+static uint32_t material_shade_row(const crt_scene_desc* D, uint32_t mat, float4& pay) {
+    pay = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (mat >= (uint32_t)D->n_materials) return SHADE_INVALID;
+    const crt_material_desc& M = D->materials[mat];
+    switch (M.type) {
+        case CRT_LAMBERTIAN: pay = make_float4(M.albedo[0], M.albedo[1], M.albedo[2], 0.f); return SHADE_LAMBERT;
+        case CRT_METAL:
+            pay = make_float4(M.albedo[0], M.albedo[1], M.albedo[2], M.roughness < 1.f ? M.roughness : 1.f);
+            return SHADE_METAL;
+        case CRT_DIELECTRIC: {
+            // Material.cuh:113 ri = front ? 1.0f / ior : ior, and Schlick's r0 = ((1 - ri) / (1 + ri))^2
+            // (:133-134) for both faces, in IEEE f32 as the device would compute them per hit
+            auto r0 = [](float r) { const float x = (1 - r) / (1 + r); return x * x; };
+            const float inv = 1.0f / M.ior;
+            pay = make_float4(M.ior, inv, r0(inv), r0(M.ior));
+            return SHADE_DIELECTRIC;
+        }
+        case CRT_DIFFUSE_LIGHT: pay = make_float4(M.emission[0], M.emission[1], M.emission[2], 0.f); return SHADE_LIGHT;
+        default: return SHADE_NOEMIT;
+    }
+}
+
+// The path steps' per-material table: 2 x float4 per material, (code, 0, 0, 0) (payload).
+static std::vector<float4> material_shade_rows(const crt_scene_desc* D) {
+    std::vector<float4> out;
+    out.reserve(2 * (size_t)std::max(D->n_materials, 0));
+    for (int i = 0; i < D->n_materials; ++i) {
+        float4 pay;
+        const uint32_t code = material_shade_row(D, (uint32_t)i, pay);
+        out.push_back(make_float4(i2f((int)code), 0.f, 0.f, 0.f));
+        out.push_back(pay);
+    }
+    return out;
+}
+
 static std::vector<float4> shading_records(const std::vector<int>& rank_code, const std::vector<float4>& prims,
                                            const crt_scene_desc* D) {
     std::vector<float4> out(3 * rank_code.size(), make_float4(0.f, 0.f, 0.f, 0.f));
@@ -3348,32 +3387,8 @@ static std::vector<float4> shading_records(const std::vector<int>& rank_code, co
             const size_t p = (size_t)(rank_code[r] & ~SPHERE_BIT);
             const float4 f0 = prims[3 * p], f1 = prims[3 * p + 1], f2 = prims[3 * p + 2];
             const uint32_t mat = (uint32_t)i2i_host(sphere ? f1.y : f2.y);
-            uint32_t code = SHADE_INVALID;
-            float4 pay = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (mat < (uint32_t)D->n_materials) {
-                const crt_material_desc& M = D->materials[mat];
-                switch (M.type) {
-                    case CRT_LAMBERTIAN: code = SHADE_LAMBERT; pay = make_float4(M.albedo[0], M.albedo[1], M.albedo[2], 0.f); break;
-                    case CRT_METAL:
-                        code = SHADE_METAL;
-                        pay = make_float4(M.albedo[0], M.albedo[1], M.albedo[2], M.roughness < 1.f ? M.roughness : 1.f);
-                        break;
-                    case CRT_DIELECTRIC: {
-                        // Material.cuh:113 ri = front ? 1.0f / ior : ior, and Schlick's r0 = ((1 - ri) / (1 + ri))^2
-                        // (:133-134) for both faces, in IEEE f32 as the device would compute them per hit
-                        code = SHADE_DIELECTRIC;
-                        auto r0 = [](float r) { const float x = (1 - r) / (1 + r); return x * x; };
-                        const float inv = 1.0f / M.ior;
-                        pay = make_float4(M.ior, inv, r0(inv), r0(M.ior));
-                        break;
-                    }
-                    case CRT_DIFFUSE_LIGHT:
-                        code = SHADE_LIGHT;
-                        pay = make_float4(M.emission[0], M.emission[1], M.emission[2], 0.f);
-                        break;
-                    default: code = SHADE_NOEMIT; break;
-                }
-            }
+            float4 pay;
+            const uint32_t code = material_shade_row(D, mat, pay);
             float4 a;
             if (sphere) {
                 a = make_float4(f0.x, f0.y, f0.z, i2f((int)(code | SHADE_SPHERE)));
@@ -3501,12 +3516,14 @@ int crt_scene_create_ex(const crt_scene_desc* D, int device, const crt_scene_opt
     const std::vector<float4> shade = shading_records(rc, rebuilt ? RB.prims : F.prims, D);
     tr.lap("shading records");
     const std::vector<int32_t> ident = identity_table(F);
+    const std::vector<float4> mat_rows = material_shade_rows(D);
     hipError_t e;
     if ((e = up(&S->d_nodes, S->width == 4 ? swizzled : (rebuilt ? RB.nodes : F.nodes))) != hipSuccess ||
         (e = up(&S->d_prims, rebuilt ? RB.prims : F.prims)) != hipSuccess ||
         (e = up(&S->d_mats, mats)) != hipSuccess ||
         (e = up(&S->d_chain, rebuilt ? RB.chain : std::vector<float4>())) != hipSuccess ||
         (e = up(&S->d_shade, shade)) != hipSuccess ||
+        (e = up(&S->d_mat_rows, mat_rows)) != hipSuccess ||
         (e = hipMalloc((void**)&S->d_ident, std::max<size_t>(ident.size(), 4) * sizeof(int32_t))) != hipSuccess ||
         (!ident.empty() && (e = hipMemcpy(S->d_ident, ident.data(), ident.size() * sizeof(int32_t),
                                           hipMemcpyHostToDevice)) != hipSuccess)) {
@@ -3545,6 +3562,7 @@ void crt_scene_destroy(crt_scene* S) {
     if (S->d_shade) (void)hipFree(S->d_shade);
     if (S->d_chain) (void)hipFree(S->d_chain);
     if (S->d_ident) (void)hipFree(S->d_ident);
+    if (S->d_mat_rows) (void)hipFree(S->d_mat_rows);
     crtx_free_trace_scratch(S);
     delete S;
 }
@@ -4597,3 +4615,4 @@ int crt_selftest_rng(unsigned long long seed, const unsigned long long* subseq, 
 // Batch closest-hit / occlusion queries over a device scene: the kernels and their C ABI, in this translation unit
 // because they instantiate the traversal's device functions above (traverse_step4, trace, trace4, ray_spheres).
 #include "crt_trace.h"
+#include "crt_paths.h"
