@@ -324,6 +324,40 @@ int crt_renderer_camera_rays_device(crt_renderer* r, const int32_t* d_pixels, in
 int crt_scene_path_step_device(const crt_scene* scene, crt_ray* d_rays, const crt_hit* d_hits, crt_path* d_paths,
                                int64_t n, int max_bounces, uint32_t* d_rng, float* d_linear, int64_t n_pixels,
                                void* stream);
+/* Step, regenerate and compact in one kernel (DESIGN.md "Path queues"): what crt_scene_path_step_device does for each
+ * entry of a READ-ONLY input batch, then the entry's fate.  A path that goes on is appended to the output batch
+ * (d_rays_out, d_paths_out: n entries each, overlapping neither each other nor an input).  One that ended adds its
+ * contribution to its pixel's sum; while d_remaining[pixel] > 0 (int32 per pixel of the renderer's frame: samples not yet
+ * started) it decrements that count, draws the pixel's next camera sample as crt_renderer_camera_rays_device does, on the
+ * RNG state the lane already holds, and appends the new ray with the path {(1, 1, 1), 0, pixel, CRT_PATH_ACTIVE}.  One
+ * that ended with no sample left appends nothing.  Entries that come in CRT_PATH_ENDED, or whose pixel is outside the
+ * renderer's frame, draw nothing, add nothing and append nothing.  d_remaining NULL: never regenerate (step and compact).
+ * *d_count (device) is set to 0 on `stream` before the kernel and counts the entries appended; they are entries
+ * 0 .. *d_count - 1 of the outputs, in no particular order (no result depends on it), and the rest of the outputs is
+ * unspecified.  d_rng / d_linear NULL: the renderer's own state and sums; the camera and the fast / IEEE u, v choice are
+ * the renderer's, n_pixels its width * height.  No two active entries may name the same pixel.  Asynchronous.
+ * CRT_ERR_INVALID_ARGUMENT before any device use: a null or misaligned array, n < 0 or n >= 2^31, overlapping outputs,
+ * max_bounces < 1, scene and renderer on different devices, a renderer without a camera.  n == 0: CRT_OK, *d_count
+ * zeroed, no kernel. */
+int crt_scene_path_advance_device(const crt_scene* scene, crt_renderer* r, const crt_ray* d_rays, const crt_hit* d_hits,
+                                  const crt_path* d_paths, int64_t n, int max_bounces, uint32_t* d_rng, float* d_linear,
+                                  int32_t* d_remaining, crt_ray* d_rays_out, crt_path* d_paths_out, uint32_t* d_count,
+                                  void* stream);
+/* Input entries per reservation of output slots in this build of the advance kernel (64: one per wave; 256 .. 1024: one
+ * per 256-lane workgroup over 1 .. 4 chunks).  Host only; for measurements, no result depends on it. */
+int crt_path_advance_entries(void);
+/* A whole frame as a wavefront on the device: camera rays for every pixel, then trace / advance rounds over two
+ * ping-pong batches until none is left, spp samples per pixel with regeneration (remaining = spp - 1).  Sums, RNG
+ * state and the number of rays equal crt_renderer_render's bit for bit.  flags: CRT_RENDER_ACCUMULATE adds to the sums
+ * (they are zeroed otherwise); CRT_RENDER_COUNT_WORK is CRT_ERR_UNSUPPORTED, and so is a pixel shard other than (0, 1).
+ * trace_opts: the queries' options (NULL: defaults).  The host waits once per round, for the 4-byte size of the next
+ * batch.  Synchronous on return; a device error of a query is CRT_ERR_HIP.  spp == 0 clears the sums (unless
+ * accumulating) and traces nothing.  max_bounces >= 1.  The batches belong to the renderer handle: 164 B per pixel (two
+ * ray, two path and one hit batch, the per-pixel sample counts), about 0.6 GB at 2560x1440, allocated by the first call
+ * and freed with the handle.  stats_out (optional): rays traced, rounds, and HIP-event milliseconds round the loop. */
+typedef struct crt_wavefront_stats { uint64_t rays; uint32_t iterations; float ms; } crt_wavefront_stats;
+int crt_renderer_render_wavefront(crt_renderer* r, const crt_scene* scene, int spp, int max_bounces, unsigned flags,
+                                  const crt_trace_options* trace_opts, crt_wavefront_stats* stats_out, void* stream);
 /* Host only, no GPU (like crt_scene_export_identity): the per-material rows the step kernel reads, n_materials x 8
  * floats = (code, 0, 0, 0) (payload): code (int bits) 0 lambertian, 1 metal, 2 dielectric, 3 light, 4 unknown type
  * (emits 0); payload (albedo.xyz, 0), (albedo.xyz, min(roughness, 1)), (ior, 1 / ior, r0(1 / ior), r0(ior)) with

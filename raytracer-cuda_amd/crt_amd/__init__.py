@@ -350,6 +350,12 @@ class Scene:
         from . import paths as _paths
         _paths.path_step(self, rays, hits, paths, max_bounces, rng, linear)
 
+    def path_advance(self, renderer, rays, hits, paths, max_bounces, remaining, rng=None, linear=None, out=None):
+        """Step, regenerate and compact a batch of paths into an output batch (paths.advance): returns (rays_out,
+        paths_out, count), count a 1-element int32 device tensor."""
+        from . import paths as _paths
+        return _paths.advance(self, renderer, rays, hits, paths, max_bounces, remaining, rng, linear, out)
+
 
 def load_scene(obj_files, device: int = 0, **upload_options):
     hs = HostScene(obj_files)
@@ -418,6 +424,19 @@ class Renderer:
     def render(self, scene: Scene, spp: int, max_bounces: int = 20, accumulate=False, count_work=False, stream=None):
         flags = (RENDER_ACCUMULATE if accumulate else 0) | (RENDER_COUNT_WORK if count_work else 0)
         check(_lib.hip().crt_renderer_render(self.h, scene.h, int(spp), int(max_bounces), flags, stream), "render")
+
+    def render_wavefront(self, scene: Scene, spp: int, max_bounces: int = 20, accumulate=False, trace_options=None,
+                         stream=None) -> dict:
+        """The frame of render() as a wavefront in the library (crt_renderer_render_wavefront): camera rays, then trace /
+        advance rounds over the handle's own batches (164 B per pixel, allocated by the first call), one host wait per
+        round.  The same sums, RNG state and ray count, bit for bit.  trace_options: keywords of Scene.trace (mode,
+        grid_waves, stack_lds, refill_threshold).  Synchronous.  Returns {"rays", "iterations", "ms"}."""
+        fn = _lib.require("crt_renderer_render_wavefront")
+        o = Scene._trace_options(**dict(dict(mode=0, grid_waves=0, stack_lds=0, refill_threshold=0), **(trace_options or {})))
+        s = _lib.WavefrontStats()
+        check(fn(self.h, scene.h, int(spp), int(max_bounces), RENDER_ACCUMULATE if accumulate else 0, C.byref(o),
+                 C.byref(s), stream), "render_wavefront")
+        return {"rays": int(s.rays), "iterations": int(s.iterations), "ms": float(s.ms)}
 
     def resolve(self, scale: float, stream=None):
         check(_lib.hip().crt_renderer_resolve(self.h, C.c_float(scale), stream), "resolve")

@@ -123,6 +123,10 @@ class Path(C.Structure):             # crt_hip.h crt_path: two 16-B rows
 
 PATH_ACTIVE, PATH_ENDED = 0, 1       # crt_path.status
 
+
+class WavefrontStats(C.Structure):   # crt_hip.h crt_wavefront_stats
+    _fields_ = [("rays", C.c_uint64), ("iterations", C.c_uint32), ("ms", C.c_float)]
+
 # exported symbol lists (checked by tests against include/*.h)
 HIP_SYMBOLS = [
     "crt_abi_version", "crt_build_flags", "crt_last_error", "crt_device_count", "crt_scene_create", "crt_scene_create_ex", "crt_scene_get_stats", "crt_scene_compare", "crt_scene_compare_dump", "crt_scene_export",
@@ -144,10 +148,13 @@ HIP_SYMBOLS = [
     "crt_trace_validate_rays", "crt_scene_export_identity", "crt_scene_trace", "crt_scene_occluded",
     "crt_scene_trace_device", "crt_scene_trace_last_stats",
     "crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
+    "crt_scene_path_advance_device", "crt_path_advance_entries", "crt_renderer_render_wavefront",
 ]
-# Entries that joined ABI version 3 after its first release (the path steps): bound when the loaded library has them, so
-# an older build of the same ABI still loads; their Python front-ends raise CrtError through require() otherwise.
-OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows")
+# Entries that joined ABI version 3 after its first release (the path steps, then the path queues): bound when the loaded
+# library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
+# require() otherwise.
+OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
+                    "crt_scene_path_advance_device", "crt_path_advance_entries", "crt_renderer_render_wavefront")
 
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
@@ -238,6 +245,9 @@ def hip():
             "crt_renderer_camera_rays_device": ([P, P, C.c_int64, P, P, P, P], i32),
             "crt_scene_path_step_device": ([P, P, P, P, C.c_int64, i32, P, P, C.c_int64, P], i32),
             "crt_scene_export_shade_rows": ([P, P, P], i32),
+            "crt_scene_path_advance_device": ([P, P, P, P, P, C.c_int64, i32, P, P, P, P, P, P, P], i32),
+            "crt_path_advance_entries": ([], i32),
+            "crt_renderer_render_wavefront": ([P, P, i32, i32, C.c_uint, P, P, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):
@@ -294,7 +304,7 @@ def require(name: str, lib=None):
     """The optional entry `name` of the loaded HIP library (OPTIONAL_SYMBOLS), or CrtError naming it."""
     L = hip() if lib is None else lib
     if not hasattr(L, name):
-        raise CrtError(f"{HIP_LIB} does not export {name}: it was built before the path steps were added "
+        raise CrtError(f"{HIP_LIB} does not export {name}: it was built before that entry was added "
                        "(rebuild the library)")
     return getattr(L, name)
 

@@ -5,9 +5,13 @@ queries, as device calls on torch tensors.
   Scene.path_step(rays, hits, paths,   one bounce: the materials, the sky, the invalid-material re-loop, then the
                   max_bounces, rng,    bounce limit and Russian roulette of the bounce that follows
                   linear)
+  advance(scene, renderer, rays,       step, regenerate and compact in one kernel: the survivors and the ended pixels'
+          hits, paths, max_bounces,    next camera samples appended to an output batch, their number in a device counter
+          remaining)                   
   render(scene, renderer, spp)         the reference driver: a wavefront path tracer out of camera_rays, Scene.trace
-                                       and Scene.path_step whose sums, RNG state and ray count equal Renderer.render's
-                                       bit for bit; on_bounce is the hook of a custom integrator
+                                       and Scene.path_step (compact="torch") or Scene.path_advance (compact="device")
+                                       whose sums, RNG state and ray count equal Renderer.render's bit for bit;
+                                       on_bounce is the hook of a custom integrator
 
 Everything is torch-only (the purpose is device-resident integrators), enqueued on torch's current stream, without a
 host copy.  Tensors: rays float32 [n, 8] (crt_ray rows), hits float32 or int32 [n, 8] (crt_hit rows, Scene.trace's
@@ -122,6 +126,73 @@ def path_step(scene, rays, hits, paths, max_bounces, rng, linear):
              d_linear, n_pix, torch.cuda.current_stream(rays.device).cuda_stream), "crt_scene_path_step_device")
 
 
+def _same_memory(a, b) -> bool:
+    """The two tensors' bytes overlap."""
+    if a.device != b.device or not a.numel() or not b.numel():
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def advance(scene, renderer, rays, hits, paths, max_bounces, remaining, rng=None, linear=None, out=None):
+    """Step, regenerate and compact (crt_scene_path_advance_device): every ACTIVE path of the read-only batch takes one
+    bounce as path_step gives it; one that goes on is appended to the output batch; one that ended adds to its pixel's
+    sum and, while remaining[pixel] > 0, is replaced by that pixel's next camera sample (remaining[pixel] -= 1), drawn on
+    the RNG state of the same lane.  remaining: int32 [pixels] on the device, or None for "never regenerate".  rng,
+    linear: tensors as for path_step, or None for the renderer's own.  out: (rays_out float32 [>= n, 8], paths_out int32
+    or float32 [>= n, 8]) that overlap no input (None: allocated here).
+    Returns (rays_out, paths_out, count): count is a 1-element int32 device tensor, the entries appended; they are rows
+    [0, count) of the outputs in no particular order, the other rows are unspecified.  No host copy, no synchronisation;
+    enqueued on torch's current stream."""
+    import torch
+    dev = scene.device
+    _rows(rays, "rays", (torch.float32,))
+    _rows(hits, "hits", (torch.float32, torch.int32))
+    _rows(paths, "paths", (torch.int32, torch.float32))
+    n = rays.shape[0]
+    if not (n == hits.shape[0] == paths.shape[0]):
+        raise ValueError("rays, hits and paths differ in length")
+    if int(max_bounces) < 1:
+        raise ValueError("max_bounces must be >= 1")
+    if not _is_renderer(renderer):
+        raise ValueError("renderer must be a Renderer")
+    if renderer.device != dev:
+        raise ValueError("the renderer is on another device than the scene")
+    n_pix = renderer.width * renderer.height
+    if remaining is not None:
+        _flat(remaining, "remaining", torch.int32, numel=n_pix)
+    if rng is not None:
+        _flat(rng, "rng", torch.int32, numel=6 * n_pix)
+    if linear is not None:
+        _flat(linear, "linear", torch.float32, numel=3 * n_pix)
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError("out must be a pair (rays_out, paths_out)")
+        rays_out = _rows(out[0], "out rays", (torch.float32,))
+        paths_out = _rows(out[1], "out paths", (torch.int32, torch.float32))
+        if rays_out.shape[0] < n or paths_out.shape[0] < n:
+            raise ValueError("out is shorter than the batch: its length must be at least the rays' length")
+        for name, o in (("out rays", rays_out), ("out paths", paths_out)):
+            for x in (rays, hits, paths):
+                if _same_memory(o, x):
+                    raise ValueError(f"{name} aliases an input")
+        if _same_memory(rays_out, paths_out):
+            raise ValueError("out rays aliases out paths")
+    _on_device(dev, rays=rays, hits=hits, paths=paths, remaining=remaining, rng=rng, linear=linear,
+               **({} if out is None else {"out rays": out[0], "out paths": out[1]}))
+    fn = _lib.require("crt_scene_path_advance_device")
+    tdev = torch.device("cuda", dev)
+    if out is None:
+        rays_out = torch.empty((n, 8), dtype=torch.float32, device=tdev)
+        paths_out = torch.empty((n, 8), dtype=torch.int32, device=tdev)
+    count = torch.empty((1,), dtype=torch.int32, device=tdev)
+    ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+    check(fn(scene.h, renderer.h, rays.data_ptr(), hits.data_ptr(), paths.data_ptr(), n, int(max_bounces), ptr(rng),
+             ptr(linear), ptr(remaining), rays_out.data_ptr(), paths_out.data_ptr(), count.data_ptr(),
+             torch.cuda.current_stream(tdev).cuda_stream), "crt_scene_path_advance_device")
+    return rays_out, paths_out, count
+
+
 def shade_rows(desc) -> np.ndarray:
     """The per-material rows the step kernel reads (crt_scene_export_shade_rows; host only), float32 [materials, 2, 4]:
     row 0 = (code as int bits, 0, 0, 0), row 1 = the payload."""
@@ -164,7 +235,7 @@ class _Phases:
 
 
 def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None, trace_options=None,
-           profile=None) -> dict:
+           profile=None, compact="torch") -> dict:
     """The reference driver: spp samples per pixel as a wavefront of camera_rays / Scene.trace / Scene.path_step calls on
     the renderer's own RNG state and (fresh) sums, so renderer.linear(), rng_state() and resolve() work afterwards
     and hold what renderer.render(scene, spp, max_bounces) leaves, bit for bit.
@@ -175,11 +246,18 @@ def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None
     custom integrator; it may edit the tensors in place).  trace_options: keywords of Scene.trace (mode, grid_waves,
     ...).  profile: a list that receives one dict per iteration, its entries (n, ended) and the device milliseconds of
     its phases (trace, step, select, camera, compact; tools/path_bench.py).
+
+    compact="device": the step, the regeneration and the compaction are one advance() call per iteration on two
+    preallocated ping-pong batches, and the host waits once per iteration, for the 4-byte count (regenerate=False:
+    advance with remaining=None as the compaction).  No torch indexing; the same bits.  on_bounce then sees the batch
+    before the advance and may edit it in place; the profile's phases are trace, advance and count, its entries n.
     Returns {"rays": rays traced, "iterations": trace / step rounds}."""
     import torch
     spp, max_bounces = int(spp), int(max_bounces)
     if max_bounces < 1:
         raise ValueError("max_bounces must be >= 1")
+    if compact not in ("torch", "device"):
+        raise ValueError('compact must be "torch" or "device"')
     opts = dict(trace_options or {})
     n_pix = renderer.width * renderer.height
     tdev = torch.device("cuda", renderer.device)
@@ -196,7 +274,29 @@ def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None
         path_step(scene, rays, hits, paths, max_bounces, renderer, renderer)
         phases.mark("step")
 
-    if regenerate and spp > 0:
+    if compact == "device" and spp > 0:
+        remaining = torch.full((n_pix,), spp - 1, dtype=torch.int32, device=tdev) if regenerate else None
+        pong = (torch.empty((n_pix, 8), dtype=torch.float32, device=tdev),
+                torch.empty((n_pix, 8), dtype=torch.int32, device=tdev))
+        for _ in range(1 if regenerate else spp):
+            phases.mark("start")
+            ping = camera_rays(renderer)
+            rays, paths = ping
+            while rays.shape[0]:
+                total += rays.shape[0]
+                iterations += 1
+                phases.mark("start")
+                hits = scene.trace(rays, **opts)["f32"]
+                phases.mark("trace", n=rays.shape[0])
+                if on_bounce is not None:
+                    on_bounce(rays, hits, paths)
+                _, _, count = advance(scene, renderer, rays, hits, paths, max_bounces, remaining, out=pong)
+                phases.mark("advance")
+                m = int(count)                                # the iteration's one wait
+                phases.mark("count")
+                ping, pong = pong, ping
+                rays, paths = ping[0][:m], ping[1][:m]
+    elif regenerate and spp > 0:
         remaining = torch.full((n_pix,), spp - 1, dtype=torch.int32, device=tdev)   # samples not yet started
         rays, paths = camera_rays(renderer)
         while rays.shape[0]:

@@ -3228,7 +3228,9 @@ struct crt_renderer {
     int stack_lds = STACK_LDS;     // variant 4: per-lane stack entries kept in LDS
     float rcp_w = 1.f, rcp_h = 1.f; // RN(1 / width), RN(1 / height)
     int fast_uv = 0;               // next_ray divides by uv_div (verified for this size at creation, uv_div_mismatches)
+    struct WavefrontScratch* wavefront = nullptr;   // crt_renderer_render_wavefront: batches of the handle, allocated on first use (crt_paths.h)
 };
+void crtx_free_wavefront_scratch(crt_renderer* R);
 
 namespace {
 int use_device(int dev) {
@@ -3674,6 +3676,7 @@ void crt_renderer_destroy(crt_renderer* R) {
     if (R->d_pix_rays) (void)hipFree(R->d_pix_rays);
     if (R->d_tile_order) (void)hipFree(R->d_tile_order);
     if (R->d_rng_cache) (void)hipFree(R->d_rng_cache);
+    crtx_free_wavefront_scratch(R);
     for (auto& slot : R->ring)
         for (hipEvent_t& ev : slot)
             if (ev) (void)hipEventDestroy(ev);

@@ -184,6 +184,248 @@ __global__ __launch_bounds__(256) void crt_path_step_kernel(PathStepParams Q) {
     Q.paths[2 * (size_t)i + 1] = make_float4(p1.x, __int_as_float(ended ? CRT_PATH_ENDED : CRT_PATH_ACTIVE), p1.z, p1.w);
 }
 
+// ------------------------------------------------------------------ step, regenerate, compact
+// crt_path_advance_kernel   one lane per entry of a read-only input batch: crt_path_step_kernel's body, restated (a
+//                           shared device function would have to leave that kernel's assembly as it is), then the
+//                           entry's fate in the same lane.  A path that goes on is appended to the output batch.  One
+//                           that ended adds its contribution to its pixel's sum and, while remaining[pixel] > 0,
+//                           takes one of the pixel's samples and draws its camera ray with next_ray()'s camera block
+//                           on the RNG state the lane already holds: one load and one store of the state per entry.
+//                           Entries that came in ended or name no pixel of the frame draw, add and append nothing.
+//
+// Compaction: the lanes that append are counted with a wave ballot, a lane's place among them is the popcount of the
+// ballot below it, and output slots are reserved with atomicAdd on one device counter, CRT_ADVANCE_ENTRIES input
+// entries per reservation: 64 = one reservation per wave (no LDS), 256 = one per workgroup, 512 / 768 / 1024 = one per
+// workgroup that loops over 2 / 3 / 4 chunks of 256 entries and holds their results in registers until the base is
+// known.  The order of the output across reservations is whatever order the atomics ran in; no result depends on it.
+// 512 is the measured choice (profiles/wavefront/reservation_sweep.txt: the frame's 128 advance calls take 11.0 ms at
+// 64, 4.65 ms at 256, 4.05 ms at 512 and 4.16 ms at 1024, where 87 VGPRs leave 5 waves per SIMD).
+#ifndef CRT_ADVANCE_ENTRIES
+#define CRT_ADVANCE_ENTRIES 512
+#endif
+constexpr int ADV_ENTRIES = CRT_ADVANCE_ENTRIES;
+static_assert(ADV_ENTRIES == 64 || (ADV_ENTRIES % 256 == 0 && ADV_ENTRIES >= 256 && ADV_ENTRIES <= 1024),
+              "entries per reservation: a wave, or 1 to 4 chunks of a 256-lane workgroup");
+constexpr int ADV_CHUNKS = ADV_ENTRIES == 64 ? 1 : ADV_ENTRIES / 256;   // chunks of 256 entries per workgroup
+constexpr bool ADV_PER_WAVE = ADV_ENTRIES == 64;
+
+struct PathAdvanceParams {
+    const float4* __restrict__ rays;       // 2 rows per entry, read only
+    const float4* __restrict__ hits;
+    const float4* __restrict__ paths;
+    const float4* __restrict__ rows;       // per material: (code, 0, 0, 0) (payload)
+    uint32_t* __restrict__ rng;            // 6 words per pixel
+    float* __restrict__ linear;            // 3 floats per pixel
+    int32_t* __restrict__ remaining;       // per pixel: samples not yet started; null: never regenerate
+    float4* __restrict__ rays_out;         // n entries
+    float4* __restrict__ paths_out;
+    uint32_t* __restrict__ count;          // entries appended; zeroed on the stream before the launch
+    uint32_t n, n_pix;
+    int n_mats, max_bounces;
+    crt_camera_desc cam;
+    int width, height;
+    float rcp_w, rcp_h;
+    int fast_uv;
+};
+
+// What a lane appends: the four rows of its entry.
+struct AdvanceRows {
+    float4 r0, r1, p0, p1;
+};
+
+// One entry: true when `out` is to be appended.
+__device__ __forceinline__ bool advance_entry(const PathAdvanceParams& Q, uint32_t i, AdvanceRows& out) {
+    const float4 p0 = Q.paths[2 * (size_t)i], p1 = Q.paths[2 * (size_t)i + 1];
+    const uint32_t pix = __float_as_uint(p1.x);
+    if (__float_as_int(p1.y) != CRT_PATH_ACTIVE || pix >= Q.n_pix) return false;
+    const float4 ray0 = Q.rays[2 * (size_t)i], ray1 = Q.rays[2 * (size_t)i + 1];
+    const float4 h0 = Q.hits[2 * (size_t)i], h1 = Q.hits[2 * (size_t)i + 1];
+    uint32_t* rp = Q.rng + 6 * (size_t)pix;
+    Rng s{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5]};
+    V3 o = v3(ray0.x, ray0.y, ray0.z), d = v3(ray1.x, ray1.y, ray1.z), thr = v3(p0.x, p0.y, p0.z);
+    int bounce = __float_as_int(p0.w);
+    const float INF = __builtin_inff();
+
+    // ---- crt_path_step_kernel's body: shade_rec() on the hit record
+    constexpr uint32_t SHADE_MISS = 15;
+    const float t = h0.x;
+    const bool miss = t < 0;
+    uint32_t code = SHADE_MISS;
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!miss) {
+        const uint32_t mat = __float_as_uint(h0.w);
+        code = SHADE_INVALID;
+        if (mat < (uint32_t)Q.n_mats) {
+            code = __float_as_uint(Q.rows[2u * mat].x);
+            m = Q.rows[2u * mat + 1u];
+        }
+    }
+    const V3 hp = o + t * d;
+    const V3 outward = v3(h1.x, h1.y, h1.z);
+    const bool front = __float_as_int(h1.w) != 0;
+    const V3 n = front ? outward : -outward;
+    bool ended = false;
+    V3 add = v3(0.0f, 0.0f, 0.0f);
+    V3 q = d;
+    if (code == SHADE_LAMBERT || code == SHADE_METAL) q = rand_in_unit_sphere(s);
+    V3 uq = q;
+    if (code <= SHADE_DIELECTRIC || miss) uq = unit(q);
+    if (miss) {
+        add = thr * sky_unit(uq);
+        ended = true;
+    } else if (code == SHADE_INVALID) {
+        ++bounce;
+    } else if (code == SHADE_LAMBERT) {
+        V3 sd = n + uq;
+        if (fabsf(sd.x) < 1e-8f && fabsf(sd.y) < 1e-8f && fabsf(sd.z) < 1e-8f) sd = n;
+        thr = thr * v3(m.x, m.y, m.z);
+        o = hp;
+        d = sd;
+        ++bounce;
+    } else if (code == SHADE_METAL) {
+        V3 refl = reflect(d, n);
+        refl = unit(refl) + (m.w * uq);
+        if (dot(refl, n) > 0) {
+            thr = thr * v3(m.x, m.y, m.z);
+            o = hp;
+            d = refl;
+            ++bounce;
+        } else {
+            ended = true;
+        }
+    } else if (code == SHADE_DIELECTRIC) {
+        const float ri = front ? m.y : m.x;
+        const float r0 = front ? m.z : m.w;
+        const V3 ud = uq;
+        const float cos_theta = fminf(dot(-ud, n), 1.0f);
+        const bool cannot_refract = cannot_refract_exact(cos_theta, ri);
+        V3 dir;
+        if (cannot_refract || schlick_r0(cos_theta, r0) > uniform(s))
+            dir = reflect(ud, n);
+        else
+            dir = refract(ud, n, ri);
+        o = hp;
+        d = dir;
+        ++bounce;
+    } else {
+        if (code == SHADE_LIGHT) add = v3(m.x, m.y, m.z);
+        ended = true;
+    }
+    if (!ended) {                                            // the next bounce's limit test and roulette
+        if (bounce >= Q.max_bounces) {
+            ended = true;
+        } else if (bounce >= 3) {
+            float p = fmaxf(thr.x, fmaxf(thr.y, thr.z));
+            p = fminf(p, 0.95f);
+            if (uniform(s) > p) ended = true;
+            else thr = recip_exact_wave(p) * thr;
+        }
+    }
+
+    // ---- the entry's fate
+    bool keep = !ended;
+    float4 q1 = make_float4(p1.x, __int_as_float(CRT_PATH_ACTIVE), p1.z, p1.w);
+    if (ended) {
+        float* L = Q.linear + 3 * (size_t)pix;
+        const V3 sum = v3(L[0], L[1], L[2]) + add;           // pixel_color += ..., the (0, 0, 0) of a killed path too
+        L[0] = sum.x; L[1] = sum.y; L[2] = sum.z;
+        int32_t left = 0;
+        if (Q.remaining) left = Q.remaining[pix];
+        if (left > 0) {                                      // the pixel's next sample, as crt_camera_rays_kernel draws it
+            Q.remaining[pix] = left - 1;
+            const crt_camera_desc& Cd = Q.cam;
+            CamRegs C;
+            C.pos = v3(Cd.origin[0], Cd.origin[1], Cd.origin[2]);
+            C.llc = v3(Cd.lower_left[0], Cd.lower_left[1], Cd.lower_left[2]);
+            C.hor = v3(Cd.horizontal[0], Cd.horizontal[1], Cd.horizontal[2]);
+            C.ver = v3(Cd.vertical[0], Cd.vertical[1], Cd.vertical[2]);
+            C.right = v3(Cd.right[0], Cd.right[1], Cd.right[2]);
+            C.up = v3(Cd.up[0], Cd.up[1], Cd.up[2]);
+            C.lens = Cd.lens_radius;
+            C.fw = (float)Q.width;
+            C.fh = (float)Q.height;
+            C.rfw = Q.rcp_w;
+            C.rfh = Q.rcp_h;
+            C.fast_uv = Q.fast_uv;
+            PathState S{};
+            S.s = s;
+            S.pixel = v3(0.f, 0.f, 0.f);
+            S.thr = v3(1.f, 1.f, 1.f);
+            S.remaining = 1; S.bounce = 0; S.need_new = true; S.rays = 0; S.paths = 0;
+            next_ray(S, C, (int)(pix % (uint32_t)Q.width), (int)(pix / (uint32_t)Q.width), 1);
+            s = S.s;
+            o = S.o;
+            d = S.d;
+            thr = v3(1.f, 1.f, 1.f);
+            bounce = 0;
+            q1 = make_float4(p1.x, __int_as_float(CRT_PATH_ACTIVE), 0.f, 0.f);
+            keep = true;
+        }
+    }
+    rp[0] = s.v0; rp[1] = s.v1; rp[2] = s.v2; rp[3] = s.v3; rp[4] = s.v4; rp[5] = s.d;
+    out.r0 = make_float4(o.x, o.y, o.z, INF);
+    out.r1 = make_float4(d.x, d.y, d.z, 0.f);
+    out.p0 = make_float4(thr.x, thr.y, thr.z, __int_as_float(bounce));
+    out.p1 = q1;
+    return keep;
+}
+
+__device__ __forceinline__ void advance_store(const PathAdvanceParams& Q, uint32_t slot, const AdvanceRows& out) {
+    if (slot >= Q.n) return;                                 // cannot happen with a counter that started at 0
+    Q.rays_out[2 * (size_t)slot] = out.r0;
+    Q.rays_out[2 * (size_t)slot + 1] = out.r1;
+    Q.paths_out[2 * (size_t)slot] = out.p0;
+    Q.paths_out[2 * (size_t)slot + 1] = out.p1;
+}
+
+__global__ __launch_bounds__(256) void crt_path_advance_kernel(PathAdvanceParams Q) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    AdvanceRows out[ADV_CHUNKS];
+    bool keep[ADV_CHUNKS];
+    uint32_t rank[ADV_CHUNKS], cnt[ADV_CHUNKS];              // the lane's place among its wave's appending lanes, their number
+#pragma unroll
+    for (int c = 0; c < ADV_CHUNKS; ++c) {
+        const uint32_t i = (blockIdx.x * (uint32_t)ADV_CHUNKS + (uint32_t)c) * 256u + threadIdx.x;
+        keep[c] = false;
+        if (i < Q.n) keep[c] = advance_entry(Q, i, out[c]);
+        const unsigned long long b = __builtin_amdgcn_ballot_w64(keep[c]);
+        rank[c] = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        cnt[c] = (uint32_t)__builtin_popcountll(b);
+    }
+    if constexpr (ADV_PER_WAVE) {
+        uint32_t base = 0;
+        if (lane == 0 && cnt[0]) base = atomicAdd(Q.count, cnt[0]);
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        if (keep[0]) advance_store(Q, base + rank[0], out[0]);
+    } else {
+        __shared__ uint32_t wave_cnt[ADV_CHUNKS * 4];        // appending lanes per (chunk, wave)
+        __shared__ uint32_t group_base;
+        if (lane == 0)
+#pragma unroll
+            for (int c = 0; c < ADV_CHUNKS; ++c) wave_cnt[c * 4 + (int)wave] = cnt[c];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t total = 0;
+            for (int k = 0; k < ADV_CHUNKS * 4; ++k) total += wave_cnt[k];
+            group_base = total ? atomicAdd(Q.count, total) : 0u;
+        }
+        __syncthreads();
+        uint32_t at = group_base;
+#pragma unroll
+        for (int c = 0; c < ADV_CHUNKS; ++c) {
+            uint32_t before = 0, whole = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t k = wave_cnt[c * 4 + w];
+                if ((uint32_t)w < wave) before += k;
+                whole += k;
+            }
+            if (keep[c]) advance_store(Q, at + before + rank[c], out[c]);
+            at += whole;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ host side
 namespace {
 
@@ -251,6 +493,180 @@ int crt_scene_path_step_device(const crt_scene* S, crt_ray* d_rays, const crt_hi
     hipLaunchKernelGGL(crt_path_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Q);
     HIP_TRY(hipGetLastError());
     return CRT_OK;
+}
+
+int crt_scene_path_advance_device(const crt_scene* S, crt_renderer* R, const crt_ray* d_rays, const crt_hit* d_hits,
+                                  const crt_path* d_paths, int64_t n, int max_bounces, uint32_t* d_rng, float* d_linear,
+                                  int32_t* d_remaining, crt_ray* d_rays_out, crt_path* d_paths_out, uint32_t* d_count,
+                                  void* stream) {
+    if (!S) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: null scene");
+    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: null renderer");
+    if (int rc = path_batch_args("path advance", n, d_rays, d_hits, d_paths)) return rc;
+    if (max_bounces < 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: max_bounces must be >= 1");
+    if (!d_count) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: null count");
+    if (n > 0) {
+        if (!d_rays_out || !d_paths_out) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: null output array");
+        if (((uintptr_t)d_rays_out | (uintptr_t)d_paths_out) & 15u)
+            return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: output arrays must be 16-byte aligned");
+        const uintptr_t bytes = (uintptr_t)n * 32u;          // every batch array holds n 32-B entries
+        const uintptr_t in[3] = {(uintptr_t)d_rays, (uintptr_t)d_hits, (uintptr_t)d_paths};
+        const uintptr_t out[2] = {(uintptr_t)d_rays_out, (uintptr_t)d_paths_out};
+        for (uintptr_t a : out)
+            for (uintptr_t b : in)
+                if (a < b + bytes && b < a + bytes)
+                    return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: an output array overlaps an input array");
+        if (out[0] < out[1] + bytes && out[1] < out[0] + bytes)
+            return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: the output arrays overlap");
+    }
+    if (((uintptr_t)d_rng | (uintptr_t)d_linear | (uintptr_t)d_remaining | (uintptr_t)d_count) & 3u)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: RNG state, sums, remaining and count must be 4-byte aligned");
+    if (S->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: scene and renderer on different devices");
+    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: the renderer has no camera (crt_renderer_set_camera)");
+    HIP_TRY(hipSetDevice(S->device));
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
+    if (n == 0) return CRT_OK;
+    PathAdvanceParams Q{};
+    Q.rays = reinterpret_cast<const float4*>(d_rays);
+    Q.hits = reinterpret_cast<const float4*>(d_hits);
+    Q.paths = reinterpret_cast<const float4*>(d_paths);
+    Q.rows = S->d_mat_rows;
+    Q.rng = d_rng ? d_rng : R->d_rng;
+    Q.linear = d_linear ? d_linear : R->d_sum;
+    Q.remaining = d_remaining;
+    Q.rays_out = reinterpret_cast<float4*>(d_rays_out);
+    Q.paths_out = reinterpret_cast<float4*>(d_paths_out);
+    Q.count = d_count;
+    Q.n = (uint32_t)n;
+    Q.n_pix = (uint32_t)(R->width * R->height);
+    Q.n_mats = S->n_mats;
+    Q.max_bounces = max_bounces;
+    Q.cam = R->cam;
+    Q.width = R->width; Q.height = R->height;
+    Q.rcp_w = R->rcp_w; Q.rcp_h = R->rcp_h; Q.fast_uv = R->fast_uv;
+    const int64_t per_group = 256 * (int64_t)ADV_CHUNKS;
+    hipLaunchKernelGGL(crt_path_advance_kernel, dim3((unsigned)((n + per_group - 1) / per_group)), dim3(256), 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    return CRT_OK;
+}
+
+int crt_path_advance_entries(void) { return ADV_ENTRIES; }
+
+}  // extern "C"
+
+// The wavefront loop's scratch: owned by the renderer handle, allocated on first use, freed with the handle.
+struct WavefrontScratch {
+    crt_ray* rays[2] = {nullptr, nullptr};
+    crt_path* paths[2] = {nullptr, nullptr};
+    crt_hit* hits = nullptr;
+    int32_t* remaining = nullptr;
+    uint32_t* d_count = nullptr;
+    uint32_t* h_count = nullptr;            // pinned: [0] the count, [2..3] the trace error word
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+void crtx_free_wavefront_scratch(crt_renderer* R) {
+    WavefrontScratch* X = R->wavefront;
+    if (!X) return;
+    for (int k = 0; k < 2; ++k) {
+        if (X->rays[k]) (void)hipFree(X->rays[k]);
+        if (X->paths[k]) (void)hipFree(X->paths[k]);
+    }
+    if (X->hits) (void)hipFree(X->hits);
+    if (X->remaining) (void)hipFree(X->remaining);
+    if (X->d_count) (void)hipFree(X->d_count);
+    if (X->h_count) (void)hipHostFree(X->h_count);
+    if (X->ev0) (void)hipEventDestroy(X->ev0);
+    if (X->ev1) (void)hipEventDestroy(X->ev1);
+    delete X;
+    R->wavefront = nullptr;
+}
+
+namespace {
+
+int wavefront_scratch(crt_renderer* R, WavefrontScratch** out) {
+    if (!R->wavefront) {
+        WavefrontScratch* X = new (std::nothrow) WavefrontScratch;
+        if (!X) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+        R->wavefront = X;   // whatever is allocated below is freed with the handle
+        const size_t n_pix = (size_t)R->width * R->height;
+        for (int k = 0; k < 2; ++k) {
+            HIP_TRY(hipMalloc((void**)&X->rays[k], n_pix * sizeof(crt_ray)));
+            HIP_TRY(hipMalloc((void**)&X->paths[k], n_pix * sizeof(crt_path)));
+        }
+        HIP_TRY(hipMalloc((void**)&X->hits, n_pix * sizeof(crt_hit)));
+        HIP_TRY(hipMalloc((void**)&X->remaining, n_pix * 4));
+        HIP_TRY(hipMalloc((void**)&X->d_count, 4));
+        HIP_TRY(hipHostMalloc((void**)&X->h_count, 16));
+        HIP_TRY(hipEventCreate(&X->ev0));
+        HIP_TRY(hipEventCreate(&X->ev1));
+    }
+    WavefrontScratch* X = R->wavefront;
+    if (!X->rays[1] || !X->paths[1] || !X->hits || !X->remaining || !X->d_count || !X->h_count || !X->ev1)
+        return set_error(CRT_ERR_OUT_OF_MEMORY, "the wavefront scratch of this renderer could not be allocated");
+    *out = X;
+    return CRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crt_renderer_render_wavefront(crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags,
+                                  const crt_trace_options* trace_opts, crt_wavefront_stats* stats_out, void* stream) {
+    if (!R || !Sc) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: null argument");
+    if (spp < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: negative spp");
+    if (max_bounces < 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: max_bounces must be >= 1");
+    if (flags & ~(CRT_RENDER_ACCUMULATE | CRT_RENDER_COUNT_WORK))
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: unknown flag");
+    if (Sc->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: scene and renderer on different devices");
+    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: camera not set");
+    if (flags & CRT_RENDER_COUNT_WORK)
+        return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: work counters are the render kernels' (crt_renderer_render)");
+    if (R->tile_shards > 1) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: pixel sharding is crt_renderer_render's");
+    const int64_t n_pix = (int64_t)R->width * R->height;
+    if (n_pix >= ((int64_t)1 << 31)) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: 2^31 pixels or more");
+    crt_scene* S = const_cast<crt_scene*>(Sc);   // the trace scratch belongs to the handle (handles are not thread-safe)
+    HIP_TRY(hipSetDevice(R->device));
+    hipStream_t st = (hipStream_t)stream;
+    crt_wavefront_stats stats{};
+    if (!(flags & CRT_RENDER_ACCUMULATE))
+        HIP_TRY(hipMemsetAsync(R->d_sum, 0, (size_t)n_pix * 3 * sizeof(float), st));
+    if (spp == 0 || n_pix == 0) {
+        HIP_TRY(hipStreamSynchronize(st));
+        if (stats_out) *stats_out = stats;
+        return CRT_OK;
+    }
+    WavefrontScratch* X = nullptr;
+    if (int rc = wavefront_scratch(R, &X)) return rc;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->remaining, spp - 1, (size_t)n_pix, st));
+    HIP_TRY(hipEventRecord(X->ev0, st));
+    if (int rc = crt_renderer_camera_rays_device(R, nullptr, n_pix, nullptr, X->rays[0], X->paths[0], stream)) return rc;
+    int cur = 0;
+    int64_t m = n_pix;
+    while (m > 0) {
+        stats.rays += (uint64_t)m;
+        ++stats.iterations;
+        if (int rc = trace_enqueue(S, X->rays[cur], m, trace_opts, X->hits, nullptr, 0, st)) return rc;
+        if (int rc = crt_scene_path_advance_device(S, R, X->rays[cur], X->hits, X->paths[cur], m, max_bounces, nullptr,
+                                                   nullptr, X->remaining, X->rays[cur ^ 1], X->paths[cur ^ 1],
+                                                   X->d_count, stream))
+            return rc;
+        // the size of the next batch and this query's error word (the next query clears it), then the loop's one host wait
+        HIP_TRY(hipMemcpyAsync(X->h_count, X->d_count, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(X->h_count + 2, S->trace->d_stats + TRACE_ERR_WORD, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        m = std::min<int64_t>(X->h_count[0], n_pix);
+        cur ^= 1;
+        if (X->h_count[2] | X->h_count[3]) break;            // reported below, as trace_take_error words it
+    }
+    HIP_TRY(hipEventRecord(X->ev1, st));
+    HIP_TRY(hipEventSynchronize(X->ev1));
+    HIP_TRY(hipEventElapsedTime(&stats.ms, X->ev0, X->ev1));
+    if (stats_out) *stats_out = stats;
+    if (X->h_count[2] | X->h_count[3])
+        HIP_TRY(hipMemcpy(S->trace->d_stats + TRACE_ERR_WORD, X->h_count + 2, 8, hipMemcpyHostToDevice));
+    return trace_take_error(S->trace);
 }
 
 int crt_scene_export_shade_rows(const crt_scene_desc* D, float* out, int64_t* n_materials) {

@@ -3,7 +3,8 @@
     make -C <tree>/raytracer-cuda_amd isa > <tree>/isa.log 2>&1      (in both trees)
     python tools/kernels_unchanged.py <parent tree> <this tree> [--show 'crt_render_kernel<false, 8, 7>' ...]
 
-Compares, for every crt_render_kernel / crt_trace_kernel / crt_trace_lane_kernel instantiation, the figures of
+Compares, for every crt_render_kernel / crt_trace_kernel / crt_trace_lane_kernel instantiation and the two path-step
+kernels (crt_camera_rays_kernel, crt_path_step_kernel), the figures of
 -Rpass-analysis=kernel-resource-usage (isa.log) and the assembly text of build/crt_hip.s from the kernel's label to its
 .end_amdhsa_kernel: every instruction and the kernel descriptor.  The compiler numbers a function's local labels
 `.LBB<f>_<b>` with f = the function's position in the module; a kernel added ahead of the template instantiations
@@ -17,7 +18,7 @@ import subprocess
 import sys
 from pathlib import Path
 
-WANTED = ("crt_render_kernel", "crt_trace_kernel", "crt_trace_lane_kernel")
+WANTED = ("crt_render_kernel", "crt_trace_kernel", "crt_trace_lane_kernel", "crt_camera_rays_kernel", "crt_path_step_kernel")
 FIGURES = r"(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\])"
 
 
@@ -69,7 +70,7 @@ def main():
     for k in differ:
         print("DIFFERS:", names[k])
     n_render = sum("crt_render_kernel" in k for k in old)
-    print(f"{len(old)} kernels compared ({n_render} crt_render_kernel, {len(old) - n_render} crt_trace*): "
+    print(f"{len(old)} kernels compared ({n_render} crt_render_kernel, {len(old) - n_render} ray-query and path-step kernels): "
           f"{len(old) - len(differ)} with the same figures and assembly text, {len(differ)} different; "
           f"{sum(asm[0][k].count(chr(10)) for k in old):,} lines in the parent, "
           f"{sum(asm[1][k].count(chr(10)) for k in old if k in asm[1]):,} now")

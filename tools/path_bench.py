@@ -1,7 +1,8 @@
-"""The wavefront driver (crt_amd.paths.render) against Renderer.render on the same frame, and where its time goes.
+"""The wavefront drivers (crt_amd.paths.render with torch or device compaction, Renderer.render_wavefront) against
+Renderer.render on the same frame, and where their time goes.
 
     python tools/path_bench.py [--width 1280 --height 720] [--spp 16] [--bounces 20] [--reps 7] [--warmup 1]
-                               [--mode 0]
+                               [--mode 0] [--rows frame,phases,step,queue,advance]
 
 No pass / fail: JSON lines.  Scene: cornell_bunny, rebuilt 4-wide tree, default options, bench camera, seed 41.
 
@@ -12,6 +13,17 @@ No pass / fail: JSON lines.  Scene: cornell_bunny, rebuilt 4-wide tree, default 
   phases  one more wavefront frame with the driver's per-iteration profile: device milliseconds and shares of trace,
           step, camera and the torch work (select = finding the ended paths and their pixels, compact = scattering the
           new rays and boolean indexing); the rest of the frame time is host time between the phases.
+  queue    `reps` rounds of four frames, interleaved in one process: Renderer.render, paths.render with
+          torch compaction (the parent's code path), paths.render(compact="device") and Renderer.render_wavefront (its
+          own HIP events round the loop); medians, ratios to the torch driver, equal bits.
+  advance one more compact="device" frame with the per-iteration profile: device milliseconds and shares of trace,
+          advance and count (the 4-byte read the host waits for); the advance kernel's entries per second and the bytes
+          an entry moves -- ray, hit and path 32 B read each, RNG 24 B read and written, then 64 B written by an entry
+          that is appended, and the sum's 12 B read and written plus remaining's 4 B read (and written when a sample is
+          taken) by one that ended -- and `advance_entries`, the input entries per reservation of output slots in the
+          loaded build.  The reservation sweep is this row from builds with other constants:
+              tools/build_profile_lib.sh adv64 -DCRT_ADVANCE_ENTRIES=64        (also 512, 1024; the default is 256)
+              CRT_HIP_LIB=raytracer-cuda_amd/lib_exp/adv64/libcrt_hip.so python tools/path_bench.py --rows advance
   step    the step kernel alone over that frame's iterations: paths per second, and bytes per second against the bytes
           an entry must move -- ray 32 B read, hit 32 B read, path 32 B read and written, RNG 24 B read and written,
           then the ray's 32 B written by a path that goes on or the sum's 12 B read and written by one that ends.
@@ -38,7 +50,9 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mode", type=int, default=0, help="Scene.trace mode of the driver's queries (0 = automatic)")
+    ap.add_argument("--rows", default="frame,phases,step,queue,advance", help="the rows to measure, comma-separated")
     a = ap.parse_args()
+    want = set(a.rows.split(","))
 
     import torch
     if not torch.cuda.is_available():
@@ -59,12 +73,12 @@ def main():
         r.synchronize()
         return r.last_kernel_ms()
 
-    def wavefront(profile=None):
+    def wavefront(profile=None, compact="torch"):
         r.init_rand(41)
         r.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        res = paths.render(sc, r, a.spp, a.bounces, trace_options=opts, profile=profile)
+        res = paths.render(sc, r, a.spp, a.bounces, trace_options=opts, profile=profile, compact=compact)
         e1.record()
         e1.synchronize()
         return e0.elapsed_time(e1), res
@@ -73,6 +87,16 @@ def main():
         r.synchronize()
         return r.linear().view(np.uint32), r.rng_state()
 
+    def library():
+        r.init_rand(41)
+        r.synchronize()
+        res = r.render_wavefront(sc, a.spp, a.bounces, trace_options=opts)
+        return res["ms"], res
+
+    if want & {"queue", "advance"}:
+        queue_rows(a, want, case, direct, wavefront, library, state)
+    if not want & {"frame", "phases", "step"}:
+        return
     for _ in range(a.warmup):
         direct()
         wavefront()
@@ -117,6 +141,65 @@ def main():
                           gbytes_per_s=round(moved / ms["step"] / 1e6, 1),
                           large_iterations=len(big), large_gpaths_per_s=round(n_big / ms_big / 1e6, 3) if big else None)),
           flush=True)
+
+
+def queue_rows(a, want, case, direct, wavefront, library, state):
+    import crt_amd
+    entries = crt_amd._lib.require("crt_path_advance_entries")()
+    med = statistics.median
+    if "queue" in want:
+        for _ in range(a.warmup):
+            direct(), wavefront(), wavefront(compact="device"), library()
+        ms = {"render": [], "torch": [], "device": [], "library": []}
+        states, res = {}, {}
+        for _ in range(a.reps):
+            ms["render"].append(direct())
+            states["render"] = state()
+            for k, run in (("torch", wavefront), ("device", lambda: wavefront(compact="device")), ("library", library)):
+                t, res[k] = run()
+                ms[k].append(t)
+                states[k] = state()
+        equal = all(np.array_equal(states[k][0], states["render"][0]) and np.array_equal(states[k][1], states["render"][1])
+                    for k in ("torch", "device", "library"))
+        equal = equal and len({(res[k]["rays"], res[k]["iterations"]) for k in res}) == 1
+        print(json.dumps(dict(case, row="queue", reps=a.reps, advance_entries=entries,
+                              **{k + "_ms_median": round(med(v), 3) for k, v in ms.items()},
+                              **{k + "_ms_min": round(min(v), 3) for k, v in ms.items()},
+                              device_over_torch=round(med(ms["device"]) / med(ms["torch"]), 3),
+                              library_over_torch=round(med(ms["library"]) / med(ms["torch"]), 3),
+                              library_over_render=round(med(ms["library"]) / med(ms["render"]), 2),
+                              rays=res["library"]["rays"], iterations=res["library"]["iterations"], equal_bits=bool(equal))),
+              flush=True)
+    if "advance" in want:
+        wavefront(compact="device")
+        t_rows = []
+        wavefront(t_rows)                                     # the torch driver's profile: the entries that ended
+        ended = sum(row["ended"] for row in t_rows)
+        adv_ms, best = [], None
+        for _ in range(max(a.reps, 1)):
+            rows = []
+            total_ms, res = wavefront(rows, compact="device")
+            adv_ms.append(sum(row["advance_ms"] for row in rows))
+            if best is None or adv_ms[-1] <= min(adv_ms):
+                best = (total_ms, rows)
+        total_ms, rows = best
+        keys = ("trace", "advance", "count")
+        ms = {k: sum(row.get(k + "_ms", 0.0) for row in rows) for k in keys}
+        n = sum(row["n"] for row in rows)
+        appended = n - rows[0]["n"]                           # every batch but the first was appended by an advance
+        taken = appended - (n - ended)                        # ended entries that took a new sample
+        moved = n * (3 * 32 + 2 * 24) + appended * 64 + ended * (24 + 4) + taken * 4
+        big = [row for row in rows if row["n"] >= a.width * a.height // 2]
+        n_big, ms_big = sum(row["n"] for row in big), sum(row["advance_ms"] for row in big)
+        print(json.dumps(dict(case, row="advance", advance_entries=entries, reps=len(adv_ms), frame_ms=round(total_ms, 3),
+                              iterations=len(rows), **{k + "_ms": round(v, 3) for k, v in ms.items()},
+                              **{k + "_share": round(v / total_ms, 4) for k, v in ms.items()},
+                              host_and_gaps_share=round(1 - sum(ms.values()) / total_ms, 4),
+                              advance_ms_median=round(med(adv_ms), 3), advance_ms_min=round(min(adv_ms), 3),
+                              entries=n, ended=ended, regenerated=taken,
+                              gpaths_per_s=round(n / med(adv_ms) / 1e6, 3), bytes_per_entry=round(moved / n, 1),
+                              gbytes_per_s=round(moved / med(adv_ms) / 1e6, 1), large_iterations=len(big),
+                              large_gpaths_per_s=round(n_big / ms_big / 1e6, 3) if big else None)), flush=True)
 
 
 if __name__ == "__main__":
