@@ -54,6 +54,20 @@ def _flat(x, name, dtype, numel=None, multiple=1):
     return x
 
 
+def _batch(rays, hits, paths, max_bounces) -> int:
+    """rays, hits and paths are one batch for a step of at least one bounce, or ValueError; its length."""
+    import torch
+    _rows(rays, "rays", (torch.float32,))
+    _rows(hits, "hits", (torch.float32, torch.int32))
+    _rows(paths, "paths", (torch.int32, torch.float32))
+    n = rays.shape[0]
+    if not (n == hits.shape[0] == paths.shape[0]):
+        raise ValueError("rays, hits and paths differ in length")
+    if int(max_bounces) < 1:
+        raise ValueError("max_bounces must be >= 1")
+    return n
+
+
 def _on_device(device, **tensors):
     """Checked last, so that a tensor wrong in kind is reported as that: every tensor lives on cuda:`device`."""
     for name, x in tensors.items():
@@ -99,13 +113,7 @@ def path_step(scene, rays, hits, paths, max_bounces, rng, linear):
     linear: tensors (see the module text), or the Renderer for its own.  No two active paths on the same pixel."""
     import torch
     dev = scene.device
-    _rows(rays, "rays", (torch.float32,))
-    _rows(hits, "hits", (torch.float32, torch.int32))
-    _rows(paths, "paths", (torch.int32, torch.float32))
-    if not (rays.shape[0] == hits.shape[0] == paths.shape[0]):
-        raise ValueError("rays, hits and paths differ in length")
-    if int(max_bounces) < 1:
-        raise ValueError("max_bounces must be >= 1")
+    n = _batch(rays, hits, paths, max_bounces)
     n_pix = None
     for name, x, dtype, per in (("rng", rng, torch.int32, 6), ("linear", linear, torch.float32, 3)):
         if _is_renderer(x):
@@ -122,7 +130,7 @@ def path_step(scene, rays, hits, paths, max_bounces, rng, linear):
     fn = _lib.require("crt_scene_path_step_device")
     d_rng = rng.rng_device_ptr() if _is_renderer(rng) else rng.data_ptr()
     d_linear = linear.linear_device_ptr() if _is_renderer(linear) else linear.data_ptr()
-    check(fn(scene.h, rays.data_ptr(), hits.data_ptr(), paths.data_ptr(), rays.shape[0], int(max_bounces), d_rng,
+    check(fn(scene.h, rays.data_ptr(), hits.data_ptr(), paths.data_ptr(), n, int(max_bounces), d_rng,
              d_linear, n_pix, torch.cuda.current_stream(rays.device).cuda_stream), "crt_scene_path_step_device")
 
 
@@ -146,14 +154,7 @@ def advance(scene, renderer, rays, hits, paths, max_bounces, remaining, rng=None
     enqueued on torch's current stream."""
     import torch
     dev = scene.device
-    _rows(rays, "rays", (torch.float32,))
-    _rows(hits, "hits", (torch.float32, torch.int32))
-    _rows(paths, "paths", (torch.int32, torch.float32))
-    n = rays.shape[0]
-    if not (n == hits.shape[0] == paths.shape[0]):
-        raise ValueError("rays, hits and paths differ in length")
-    if int(max_bounces) < 1:
-        raise ValueError("max_bounces must be >= 1")
+    n = _batch(rays, hits, paths, max_bounces)
     if not _is_renderer(renderer):
         raise ValueError("renderer must be a Renderer")
     if renderer.device != dev:

@@ -133,6 +133,11 @@ __device__ __forceinline__ V3 refract(V3 uv, V3 n, float eta) {                 
 // ------------------------------------------------------------------ XORWOW
 // cuRAND XORWOW (CUDA 12.5 curand_kernel.h: curand, _curand_uniform) — see DESIGN.md.
 struct Rng { uint32_t v0, v1, v2, v3, v4, d; };
+// A state in memory is its six words in this order (crt_hip.h: 6 words per pixel, v[5], d).
+__device__ __forceinline__ Rng rng_load(const uint32_t* r) { return Rng{r[0], r[1], r[2], r[3], r[4], r[5]}; }
+__device__ __forceinline__ void rng_store(uint32_t* r, const Rng& s) {
+    r[0] = s.v0; r[1] = s.v1; r[2] = s.v2; r[3] = s.v3; r[4] = s.v4; r[5] = s.d;
+}
 
 __device__ __forceinline__ uint32_t next_u32(Rng& s) {
     uint32_t t = s.v0 ^ (s.v0 >> 2);

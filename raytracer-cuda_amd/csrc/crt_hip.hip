@@ -1327,6 +1327,23 @@ struct CamRegs {
     float rfw, rfh;   // RN(1 / fw), RN(1 / fh) (host IEEE division)
     int fast_uv;      // uv_div is verified exact for this frame size (crt_renderer_create): no IEEE division
 };
+__device__ __forceinline__ CamRegs cam_regs(const crt_camera_desc& Cd, int width, int height, float rcp_w, float rcp_h,
+                                            int fast_uv) {
+    CamRegs C;
+    C.pos = v3(Cd.origin[0], Cd.origin[1], Cd.origin[2]);
+    C.llc = v3(Cd.lower_left[0], Cd.lower_left[1], Cd.lower_left[2]);
+    C.hor = v3(Cd.horizontal[0], Cd.horizontal[1], Cd.horizontal[2]);
+    C.ver = v3(Cd.vertical[0], Cd.vertical[1], Cd.vertical[2]);
+    C.right = v3(Cd.right[0], Cd.right[1], Cd.right[2]);
+    C.up = v3(Cd.up[0], Cd.up[1], Cd.up[2]);
+    C.lens = Cd.lens_radius;
+    C.fw = (float)width;
+    C.fh = (float)height;
+    C.rfw = rcp_w;
+    C.rfh = rcp_h;
+    C.fast_uv = fast_uv;
+    return C;
+}
 
 // Phase 1: give the lane a ray to trace — Camera::getRay for a new sample, the bounce-limit exit and
 // Russian roulette (CUDAKernels.h:110-121).  Returns false when the pixel has no samples left.
@@ -1407,6 +1424,18 @@ __device__ __forceinline__ bool next_ray(PathState& S, const CamRegs& C, int x, 
     }
 }
 
+// The state of a lane that starts one new camera sample on the RNG state `s` and has no path: next_ray(S, C, x, y, 1)
+// on it runs the camera block alone and leaves the ray in S.o, S.d and the advanced state in S.s.  For the callers
+// that keep no PathState of their own (the path kernels of crt_paths.h, the geometry self-test).
+__device__ __forceinline__ PathState new_sample_state(Rng s) {
+    PathState S{};
+    S.s = s;
+    S.pixel = v3(0.f, 0.f, 0.f);
+    S.thr = v3(1.f, 1.f, 1.f);
+    S.remaining = 1; S.bounce = 0; S.need_new = true; S.rays = 0; S.paths = 0;
+    return S;
+}
+
 // Dielectric::scatter's total-internal-reflection test in double, as the reference computes it (Material.cuh:115-118):
 //   cannot = RN(ri * RN(sqrt(y))) > 1,   y = RN(1 - c * c)   (c * c is exact in double: two 24-bit factors).
 // sqrt and the product are correctly rounded and monotone, so ri^2 * y decides the outcome unless it is within a hair
@@ -1429,7 +1458,8 @@ __device__ __forceinline__ bool cannot_refract_exact(float cos_theta, float ri) 
 // Phase 3: material scatter / emit / sky (CUDAKernels.h:123-142, Material.cuh:66-146).  The hit's normal and
 // material come from its shading record (crt_device.h): one pair of independent loads per hit.
 // shade_rec: the same with the hit's shading record rows 0-1 already loaded (r0, m); a sphere's row 2 (1 / radius) is
-// inv_r when `staged`, else loaded here.
+// inv_r when `staged`, else loaded here.  crt_paths.h's scatter_step() is its twin on a crt_hit record, kept apart: one
+// shared core changes the assembly of 51 of the 58 kernels (profiles/shared_scatter/kernels_unchanged.txt).
 __device__ __forceinline__ void shade_rec(PathState& S, const RenderParams& P, int hit_rank, float t, float4 r0,
                                           float4 m, bool staged, float inv_r);
 __device__ __forceinline__ void shade(PathState& S, const RenderParams& P, int hit_rank, float t) {
@@ -1662,24 +1692,11 @@ __global__ __launch_bounds__(64 * KernelShape<VARIANT>::waves, MINW) void crt_re
 #endif
     if (valid && !PERSIST) {
         const uint32_t* r = P.rng + 6 * (size_t)pix;
-        S.s.v0 = r[0]; S.s.v1 = r[1]; S.s.v2 = r[2]; S.s.v3 = r[3]; S.s.v4 = r[4]; S.s.d = r[5];
+        S.s = rng_load(r);
         if (P.accumulate) S.pixel = v3(P.sum[3 * (size_t)pix], P.sum[3 * (size_t)pix + 1], P.sum[3 * (size_t)pix + 2]);
         S.remaining = P.spp;
     }
-    const crt_camera_desc& Cd = P.cam;
-    CamRegs C;
-    C.pos = v3(Cd.origin[0], Cd.origin[1], Cd.origin[2]);
-    C.llc = v3(Cd.lower_left[0], Cd.lower_left[1], Cd.lower_left[2]);
-    C.hor = v3(Cd.horizontal[0], Cd.horizontal[1], Cd.horizontal[2]);
-    C.ver = v3(Cd.vertical[0], Cd.vertical[1], Cd.vertical[2]);
-    C.right = v3(Cd.right[0], Cd.right[1], Cd.right[2]);
-    C.up = v3(Cd.up[0], Cd.up[1], Cd.up[2]);
-    C.lens = Cd.lens_radius;
-    C.fw = (float)P.width;
-    C.fh = (float)P.height;
-    C.rfw = P.rcp_w;
-    C.rfh = P.rcp_h;
-    C.fast_uv = P.fast_uv;
+    const CamRegs C = cam_regs(P.cam, P.width, P.height, P.rcp_w, P.rcp_h, P.fast_uv);
     TraceCounts cnt{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t wave_rays = 0;    // variant 8: rays of the wave (uniform); the other variants count per lane
 
@@ -1728,7 +1745,7 @@ __global__ __launch_bounds__(64 * KernelShape<VARIANT>::waves, MINW) void crt_re
                 }
                 if (have && !live) {     // the pixel's samples are done: store it (CUDAKernels.h:162-165)
                     uint32_t* r = P.rng + 6 * (size_t)ppix;
-                    r[0] = S.s.v0; r[1] = S.s.v1; r[2] = S.s.v2; r[3] = S.s.v3; r[4] = S.s.v4; r[5] = S.s.d;
+                    rng_store(r, S.s);
                     P.sum[3 * (size_t)ppix] = S.pixel.x;
                     P.sum[3 * (size_t)ppix + 1] = S.pixel.y;
                     P.sum[3 * (size_t)ppix + 2] = S.pixel.z;
@@ -1754,7 +1771,7 @@ __global__ __launch_bounds__(64 * KernelShape<VARIANT>::waves, MINW) void crt_re
                             px = ppix % P.width;
                             py = ppix / P.width;
                             const uint32_t* r = P.rng + 6 * (size_t)ppix;
-                            S.s.v0 = r[0]; S.s.v1 = r[1]; S.s.v2 = r[2]; S.s.v3 = r[3]; S.s.v4 = r[4]; S.s.d = r[5];
+                            S.s = rng_load(r);
                             S.pixel = P.accumulate ? v3(P.sum[3 * (size_t)ppix], P.sum[3 * (size_t)ppix + 1],
                                                         P.sum[3 * (size_t)ppix + 2])
                                                    : v3(0.f, 0.f, 0.f);
@@ -1765,7 +1782,7 @@ __global__ __launch_bounds__(64 * KernelShape<VARIANT>::waves, MINW) void crt_re
                             live = next_ray(S, C, px, py, P.max_bounces);
                             if (!live) {         // spp == 0: nothing to trace, store as is
                                 uint32_t* w = P.rng + 6 * (size_t)ppix;
-                                w[0] = S.s.v0; w[1] = S.s.v1; w[2] = S.s.v2; w[3] = S.s.v3; w[4] = S.s.v4; w[5] = S.s.d;
+                                rng_store(w, S.s);
                                 P.sum[3 * (size_t)ppix] = S.pixel.x;
                                 P.sum[3 * (size_t)ppix + 1] = S.pixel.y;
                                 P.sum[3 * (size_t)ppix + 2] = S.pixel.z;
@@ -2039,7 +2056,7 @@ __global__ __launch_bounds__(64 * KernelShape<VARIANT>::waves, MINW) void crt_re
     }
     if (valid && !PERSIST) {
         uint32_t* r = P.rng + 6 * (size_t)pix;
-        r[0] = S.s.v0; r[1] = S.s.v1; r[2] = S.s.v2; r[3] = S.s.v3; r[4] = S.s.v4; r[5] = S.s.d;
+        rng_store(r, S.s);
         P.sum[3 * (size_t)pix] = S.pixel.x;
         P.sum[3 * (size_t)pix + 1] = S.pixel.y;
         P.sum[3 * (size_t)pix + 2] = S.pixel.z;
@@ -2129,24 +2146,11 @@ __global__ __launch_bounds__(256) void crt_compare_kernel(CompareParams Q) {
     const int pix = y * P.width + x;
     PathState S;
     const uint32_t* r = P.rng + 6 * (size_t)pix;
-    S.s = Rng{r[0], r[1], r[2], r[3], r[4], r[5]};
+    S.s = rng_load(r);
     S.pixel = v3(0.f, 0.f, 0.f);
     S.o = v3(0, 0, 0); S.d = v3(0, 0, 1); S.thr = v3(1, 1, 1);
     S.remaining = P.spp; S.bounce = 0; S.need_new = true; S.rays = 0; S.paths = 0;
-    const crt_camera_desc& Cd = P.cam;
-    CamRegs C;
-    C.pos = v3(Cd.origin[0], Cd.origin[1], Cd.origin[2]);
-    C.llc = v3(Cd.lower_left[0], Cd.lower_left[1], Cd.lower_left[2]);
-    C.hor = v3(Cd.horizontal[0], Cd.horizontal[1], Cd.horizontal[2]);
-    C.ver = v3(Cd.vertical[0], Cd.vertical[1], Cd.vertical[2]);
-    C.right = v3(Cd.right[0], Cd.right[1], Cd.right[2]);
-    C.up = v3(Cd.up[0], Cd.up[1], Cd.up[2]);
-    C.lens = Cd.lens_radius;
-    C.fw = (float)P.width;
-    C.fh = (float)P.height;
-    C.rfw = P.rcp_w;
-    C.rfh = P.rcp_h;
-    C.fast_uv = P.fast_uv;
+    const CamRegs C = cam_regs(P.cam, P.width, P.height, P.rcp_w, P.rcp_h, P.fast_uv);
     TraceCounts cnt{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long n_rank = 0, n_t = 0, n_bmiss = 0, n_amiss = 0;
     while (next_ray(S, C, x, y, P.max_bounces)) {
@@ -2353,27 +2357,11 @@ __global__ void crt_selftest_geometry_kernel(int kind, const float* __restrict__
         out[i] = sphere_beyond(qa, hb, disc, q[10]) ? 1.f : 0.f;
     } else {
         const int* xy = reinterpret_cast<const int*>(in);
-        CamRegs C;
-        C.pos = v3(cam.origin[0], cam.origin[1], cam.origin[2]);
-        C.llc = v3(cam.lower_left[0], cam.lower_left[1], cam.lower_left[2]);
-        C.hor = v3(cam.horizontal[0], cam.horizontal[1], cam.horizontal[2]);
-        C.ver = v3(cam.vertical[0], cam.vertical[1], cam.vertical[2]);
-        C.right = v3(cam.right[0], cam.right[1], cam.right[2]);
-        C.up = v3(cam.up[0], cam.up[1], cam.up[2]);
-        C.lens = cam.lens_radius;
-        C.fw = (float)w;
-        C.fh = (float)h;
-        C.rfw = rcp_w;
-        C.rfh = rcp_h;
-        C.fast_uv = fast_uv;
-        PathState S;
+        const CamRegs C = cam_regs(cam, w, h, rcp_w, rcp_h, fast_uv);
         uint32_t* r = rng + 6 * (size_t)i;
-        S.s = Rng{r[0], r[1], r[2], r[3], r[4], r[5]};
-        S.pixel = v3(0.f, 0.f, 0.f);
-        S.thr = v3(1.f, 1.f, 1.f);
-        S.remaining = 1; S.bounce = 0; S.need_new = true; S.rays = 0; S.paths = 0;
-        next_ray(S, C, xy[2 * i], xy[2 * i + 1], 20);
-        r[0] = S.s.v0; r[1] = S.s.v1; r[2] = S.s.v2; r[3] = S.s.v3; r[4] = S.s.v4; r[5] = S.s.d;
+        PathState S = new_sample_state(rng_load(r));
+        next_ray(S, C, xy[2 * i], xy[2 * i + 1], 1);
+        rng_store(r, S.s);
         float* o6 = out + 6 * (size_t)i;
         o6[0] = S.o.x; o6[1] = S.o.y; o6[2] = S.o.z; o6[3] = S.d.x; o6[4] = S.d.y; o6[5] = S.d.z;
     }
@@ -2382,7 +2370,7 @@ __global__ void crt_selftest_geometry_kernel(int kind, const float* __restrict__
 __global__ void crt_selftest_rng_kernel(const uint32_t* st_in, int n, int n_draw, float* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Rng s{st_in[6 * i], st_in[6 * i + 1], st_in[6 * i + 2], st_in[6 * i + 3], st_in[6 * i + 4], st_in[6 * i + 5]};
+    Rng s = rng_load(st_in + 6 * i);
     for (int k = 0; k < n_draw; ++k) out[(size_t)i * n_draw + k] = uniform(s);
 }
 
@@ -3241,6 +3229,15 @@ int use_device(int dev) {
     HIP_TRY(hipSetDevice(dev));
     return CRT_OK;
 }
+
+// The renderer's camera and frame, the inputs of cam_regs(), into any kernel's parameter struct that carries them
+// (RenderParams, crt_paths.h's CameraRaysParams and PathAdvanceParams).
+template <class Params>
+void set_camera_frame(Params& P, const crt_renderer* R) {
+    P.cam = R->cam;
+    P.width = R->width; P.height = R->height;
+    P.rcp_w = R->rcp_w; P.rcp_h = R->rcp_h; P.fast_uv = R->fast_uv;
+}
 }  // namespace
 
 extern "C" {
@@ -3914,10 +3911,10 @@ static RenderParams render_params(const crt_renderer* R, const crt_scene* S, int
     P.nodes = S->d_nodes; P.prims = S->d_prims; P.mats = S->d_mats; P.shade = S->d_shade;
     P.n_nodes = S->n_nodes; P.n_mats = S->n_mats; P.n_prims = S->n_prims; P.n_layouts = S->layouts;
     P.err = reinterpret_cast<unsigned*>(R->d_counters + ERR_WORD);
-    P.width = R->width; P.height = R->height; P.spp = spp; P.max_bounces = max_bounces;
+    set_camera_frame(P, R);
+    P.spp = spp; P.max_bounces = max_bounces;
     P.accumulate = (flags & CRT_RENDER_ACCUMULATE) ? 1 : 0;
-    P.rng = R->d_rng; P.sum = R->d_sum; P.counters = R->d_counters; P.cam = R->cam;
-    P.rcp_w = R->rcp_w; P.rcp_h = R->rcp_h; P.fast_uv = R->fast_uv;
+    P.rng = R->d_rng; P.sum = R->d_sum; P.counters = R->d_counters;
     P.probe_stride = 1;
     P.crit_threshold = 64;
     P.top_levels = R->top_levels < 0 ? CRT_TOP_LEVELS : R->top_levels;

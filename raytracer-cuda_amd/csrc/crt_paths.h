@@ -1,15 +1,18 @@
 // crt_paths.h — path steps over ray batches: camera rays and one bounce of material scattering, kernels + C ABI.
 //
 // Textually part of crt_hip.hip (included at its end, after crt_trace.h): the kernels call that file's and
-// crt_device.h's device functions unchanged -- next_ray's camera block, the XORWOW draws, unit, reflect, refract,
-// schlick_r0, cannot_refract_exact, recip_exact_wave, sky_unit, rand_in_unit_sphere -- so a batch step computes what the
-// render kernels compute between two traces, bit for bit.  Nothing here is used by a render or trace kernel.
+// crt_device.h's device functions unchanged -- cam_regs, new_sample_state and next_ray's camera block, the XORWOW draws,
+// unit, reflect, refract, schlick_r0, cannot_refract_exact, recip_exact_wave, sky_unit, rand_in_unit_sphere -- so a
+// batch step computes what the render kernels compute between two traces, bit for bit.  Nothing here is used by a
+// render or trace kernel.
 //
 //   crt_camera_rays_kernel   one lane per pixel of the batch: next_ray() for a new sample on the pixel's RNG stream.
-//   crt_path_step_kernel     one lane per path: shade_rec()'s body on the crt_hit record instead of the per-rank
-//                            shading record (the normal, the face and the material index come from the record, the
-//                            material's code and payload from the scene's per-material rows), then next_ray()'s
-//                            bounce-limit test and Russian roulette for the bounce that follows.
+//   scatter_step()           one bounce of one path, the one copy both kernels below call: shade_rec()'s body on the
+//                            crt_hit record instead of the per-rank shading record (the normal, the face and the
+//                            material index come from the record, the material's code and payload from the scene's
+//                            per-material rows), then next_ray()'s bounce-limit test and Russian roulette for the
+//                            bounce that follows.
+//   crt_path_step_kernel     one lane per path: scatter_step() in place.
 //
 // unit(), the reciprocal and the glass test pick their fast or IEEE sequence by a ballot over the lanes that run them;
 // both sequences are correctly rounded, so the lanes a wave happens to hold (a partial last wave, entries that came in
@@ -40,28 +43,11 @@ __global__ __launch_bounds__(256) void crt_camera_rays_kernel(CameraRaysParams Q
         Q.paths[2 * (size_t)i + 1] = make_float4(__int_as_float(pix), __int_as_float(CRT_PATH_ENDED), 0.f, 0.f);
         return;
     }
-    const crt_camera_desc& Cd = Q.cam;
-    CamRegs C;
-    C.pos = v3(Cd.origin[0], Cd.origin[1], Cd.origin[2]);
-    C.llc = v3(Cd.lower_left[0], Cd.lower_left[1], Cd.lower_left[2]);
-    C.hor = v3(Cd.horizontal[0], Cd.horizontal[1], Cd.horizontal[2]);
-    C.ver = v3(Cd.vertical[0], Cd.vertical[1], Cd.vertical[2]);
-    C.right = v3(Cd.right[0], Cd.right[1], Cd.right[2]);
-    C.up = v3(Cd.up[0], Cd.up[1], Cd.up[2]);
-    C.lens = Cd.lens_radius;
-    C.fw = (float)Q.width;
-    C.fh = (float)Q.height;
-    C.rfw = Q.rcp_w;
-    C.rfh = Q.rcp_h;
-    C.fast_uv = Q.fast_uv;
-    PathState S{};
+    const CamRegs C = cam_regs(Q.cam, Q.width, Q.height, Q.rcp_w, Q.rcp_h, Q.fast_uv);
     uint32_t* r = Q.rng + 6 * (size_t)pix;
-    S.s = Rng{r[0], r[1], r[2], r[3], r[4], r[5]};
-    S.pixel = v3(0.f, 0.f, 0.f);
-    S.thr = v3(1.f, 1.f, 1.f);
-    S.remaining = 1; S.bounce = 0; S.need_new = true; S.rays = 0; S.paths = 0;
+    PathState S = new_sample_state(rng_load(r));
     next_ray(S, C, pix % Q.width, pix / Q.width, 1);       // a new sample: the camera block alone
-    r[0] = S.s.v0; r[1] = S.s.v1; r[2] = S.s.v2; r[3] = S.s.v3; r[4] = S.s.v4; r[5] = S.s.d;
+    rng_store(r, S.s);
     Q.rays[2 * (size_t)i] = make_float4(S.o.x, S.o.y, S.o.z, INF);
     Q.rays[2 * (size_t)i + 1] = make_float4(S.d.x, S.d.y, S.d.z, 0.f);
     Q.paths[2 * (size_t)i] = make_float4(1.f, 1.f, 1.f, __int_as_float(0));
@@ -79,20 +65,18 @@ struct PathStepParams {
     int n_mats, max_bounces;
 };
 
-__global__ __launch_bounds__(256) void crt_path_step_kernel(PathStepParams Q) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= Q.n) return;
-    const float4 p0 = Q.paths[2 * (size_t)i], p1 = Q.paths[2 * (size_t)i + 1];
-    const uint32_t pix = __float_as_uint(p1.x);
-    if (__float_as_int(p1.y) != CRT_PATH_ACTIVE || pix >= Q.n_pix) return;
-    const float4 ray0 = Q.rays[2 * (size_t)i], ray1 = Q.rays[2 * (size_t)i + 1];
-    const float4 h0 = Q.hits[2 * (size_t)i], h1 = Q.hits[2 * (size_t)i + 1];
-    uint32_t* rp = Q.rng + 6 * (size_t)pix;
-    Rng s{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5]};
-    V3 o = v3(ray0.x, ray0.y, ray0.z), d = v3(ray1.x, ray1.y, ray1.z), thr = v3(p0.x, p0.y, p0.z);
-    int bounce = __float_as_int(p0.w);
-    const float INF = __builtin_inff();
-
+// One bounce of one path: what the render kernels do between two traces.  Everything goes in by value and comes
+// back in one struct by value: with the state passed by reference both kernels below need 4 more VGPRs and the
+// advance kernel loses a wave per SIMD (profiles/shared_scatter/kernels_unchanged.txt).
+struct Scattered {
+    Rng s;
+    V3 o, d, thr;
+    int bounce;
+    bool ended;
+    V3 add;                                // what an ended path adds to its pixel
+};
+__device__ __forceinline__ Scattered scatter_step(float4 h0, float4 h1, const float4* __restrict__ rows, int n_mats,
+                                                  int max_bounces, Rng s, V3 o, V3 d, V3 thr, int bounce) {
     // ---- rayColor's loop body after the hit query: shade_rec() on the hit record
     constexpr uint32_t SHADE_MISS = 15;
     const float t = h0.x;
@@ -102,9 +86,9 @@ __global__ __launch_bounds__(256) void crt_path_step_kernel(PathStepParams Q) {
     if (!miss) {
         const uint32_t mat = __float_as_uint(h0.w);
         code = SHADE_INVALID;                                // CUDAKernels.h:127
-        if (mat < (uint32_t)Q.n_mats) {
-            code = __float_as_uint(Q.rows[2u * mat].x);
-            m = Q.rows[2u * mat + 1u];
+        if (mat < (uint32_t)n_mats) {
+            code = __float_as_uint(rows[2u * mat].x);
+            m = rows[2u * mat + 1u];
         }
     }
     const V3 hp = o + t * d;                                 // Ray::pointAtDistance
@@ -161,7 +145,7 @@ __global__ __launch_bounds__(256) void crt_path_step_kernel(PathStepParams Q) {
 
     // ---- the next iteration's head (CUDAKernels.h:110-121), next_ray()'s first block
     if (!ended) {
-        if (bounce >= Q.max_bounces) {                       // loop exhausted: final_color = 0
+        if (bounce >= max_bounces) {                       // loop exhausted: final_color = 0
             ended = true;
         } else if (bounce >= 3) {
             float p = fmaxf(thr.x, fmaxf(thr.y, thr.z));
@@ -170,28 +154,42 @@ __global__ __launch_bounds__(256) void crt_path_step_kernel(PathStepParams Q) {
             else thr = recip_exact_wave(p) * thr;            // 1 / p, exact (crt_device.h)
         }
     }
+    return Scattered{s, o, d, thr, bounce, ended, add};
+}
 
-    rp[0] = s.v0; rp[1] = s.v1; rp[2] = s.v2; rp[3] = s.v3; rp[4] = s.v4; rp[5] = s.d;
-    if (ended) {
+__global__ __launch_bounds__(256) void crt_path_step_kernel(PathStepParams Q) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= Q.n) return;
+    const float4 p0 = Q.paths[2 * (size_t)i], p1 = Q.paths[2 * (size_t)i + 1];
+    const uint32_t pix = __float_as_uint(p1.x);
+    if (__float_as_int(p1.y) != CRT_PATH_ACTIVE || pix >= Q.n_pix) return;
+    const float4 ray0 = Q.rays[2 * (size_t)i], ray1 = Q.rays[2 * (size_t)i + 1];
+    const float4 h0 = Q.hits[2 * (size_t)i], h1 = Q.hits[2 * (size_t)i + 1];
+    uint32_t* rp = Q.rng + 6 * (size_t)pix;
+    const float INF = __builtin_inff();
+    const Scattered r = scatter_step(h0, h1, Q.rows, Q.n_mats, Q.max_bounces, rng_load(rp), v3(ray0.x, ray0.y, ray0.z),
+                                     v3(ray1.x, ray1.y, ray1.z), v3(p0.x, p0.y, p0.z), __float_as_int(p0.w));
+    rng_store(rp, r.s);
+    if (r.ended) {
         float* L = Q.linear + 3 * (size_t)pix;
-        const V3 sum = v3(L[0], L[1], L[2]) + add;           // pixel_color += ..., the (0, 0, 0) of a killed path too
+        const V3 sum = v3(L[0], L[1], L[2]) + r.add;         // pixel_color += ..., the (0, 0, 0) of a killed path too
         L[0] = sum.x; L[1] = sum.y; L[2] = sum.z;
     } else {
-        Q.rays[2 * (size_t)i] = make_float4(o.x, o.y, o.z, INF);
-        Q.rays[2 * (size_t)i + 1] = make_float4(d.x, d.y, d.z, 0.f);
+        Q.rays[2 * (size_t)i] = make_float4(r.o.x, r.o.y, r.o.z, INF);
+        Q.rays[2 * (size_t)i + 1] = make_float4(r.d.x, r.d.y, r.d.z, 0.f);
     }
-    Q.paths[2 * (size_t)i] = make_float4(thr.x, thr.y, thr.z, __int_as_float(bounce));
-    Q.paths[2 * (size_t)i + 1] = make_float4(p1.x, __int_as_float(ended ? CRT_PATH_ENDED : CRT_PATH_ACTIVE), p1.z, p1.w);
+    Q.paths[2 * (size_t)i] = make_float4(r.thr.x, r.thr.y, r.thr.z, __int_as_float(r.bounce));
+    Q.paths[2 * (size_t)i + 1] = make_float4(p1.x, __int_as_float(r.ended ? CRT_PATH_ENDED : CRT_PATH_ACTIVE), p1.z, p1.w);
 }
 
 // ------------------------------------------------------------------ step, regenerate, compact
-// crt_path_advance_kernel   one lane per entry of a read-only input batch: crt_path_step_kernel's body, restated (a
-//                           shared device function would have to leave that kernel's assembly as it is), then the
-//                           entry's fate in the same lane.  A path that goes on is appended to the output batch.  One
-//                           that ended adds its contribution to its pixel's sum and, while remaining[pixel] > 0,
-//                           takes one of the pixel's samples and draws its camera ray with next_ray()'s camera block
-//                           on the RNG state the lane already holds: one load and one store of the state per entry.
-//                           Entries that came in ended or name no pixel of the frame draw, add and append nothing.
+// crt_path_advance_kernel   one lane per entry of a read-only input batch: scatter_step(), the function
+//                           crt_path_step_kernel calls, then the entry's fate in the same lane.  A path that goes on
+//                           is appended to the output batch.  One that ended adds its contribution to its pixel's sum
+//                           and, while remaining[pixel] > 0, takes one of the pixel's samples and draws its camera ray
+//                           with next_ray()'s camera block on the RNG state the lane already holds: one load and one
+//                           store of the state per entry.  Entries that came in ended or name no pixel of the frame
+//                           draw, add and append nothing.
 //
 // Compaction: the lanes that append are counted with a wave ballot, a lane's place among them is the popcount of the
 // ballot below it, and output slots are reserved with atomicAdd on one device counter, CRT_ADVANCE_ENTRIES input
@@ -241,117 +239,26 @@ __device__ __forceinline__ bool advance_entry(const PathAdvanceParams& Q, uint32
     const float4 ray0 = Q.rays[2 * (size_t)i], ray1 = Q.rays[2 * (size_t)i + 1];
     const float4 h0 = Q.hits[2 * (size_t)i], h1 = Q.hits[2 * (size_t)i + 1];
     uint32_t* rp = Q.rng + 6 * (size_t)pix;
-    Rng s{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5]};
-    V3 o = v3(ray0.x, ray0.y, ray0.z), d = v3(ray1.x, ray1.y, ray1.z), thr = v3(p0.x, p0.y, p0.z);
-    int bounce = __float_as_int(p0.w);
     const float INF = __builtin_inff();
-
-    // ---- crt_path_step_kernel's body: shade_rec() on the hit record
-    constexpr uint32_t SHADE_MISS = 15;
-    const float t = h0.x;
-    const bool miss = t < 0;
-    uint32_t code = SHADE_MISS;
-    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!miss) {
-        const uint32_t mat = __float_as_uint(h0.w);
-        code = SHADE_INVALID;
-        if (mat < (uint32_t)Q.n_mats) {
-            code = __float_as_uint(Q.rows[2u * mat].x);
-            m = Q.rows[2u * mat + 1u];
-        }
-    }
-    const V3 hp = o + t * d;
-    const V3 outward = v3(h1.x, h1.y, h1.z);
-    const bool front = __float_as_int(h1.w) != 0;
-    const V3 n = front ? outward : -outward;
-    bool ended = false;
-    V3 add = v3(0.0f, 0.0f, 0.0f);
-    V3 q = d;
-    if (code == SHADE_LAMBERT || code == SHADE_METAL) q = rand_in_unit_sphere(s);
-    V3 uq = q;
-    if (code <= SHADE_DIELECTRIC || miss) uq = unit(q);
-    if (miss) {
-        add = thr * sky_unit(uq);
-        ended = true;
-    } else if (code == SHADE_INVALID) {
-        ++bounce;
-    } else if (code == SHADE_LAMBERT) {
-        V3 sd = n + uq;
-        if (fabsf(sd.x) < 1e-8f && fabsf(sd.y) < 1e-8f && fabsf(sd.z) < 1e-8f) sd = n;
-        thr = thr * v3(m.x, m.y, m.z);
-        o = hp;
-        d = sd;
-        ++bounce;
-    } else if (code == SHADE_METAL) {
-        V3 refl = reflect(d, n);
-        refl = unit(refl) + (m.w * uq);
-        if (dot(refl, n) > 0) {
-            thr = thr * v3(m.x, m.y, m.z);
-            o = hp;
-            d = refl;
-            ++bounce;
-        } else {
-            ended = true;
-        }
-    } else if (code == SHADE_DIELECTRIC) {
-        const float ri = front ? m.y : m.x;
-        const float r0 = front ? m.z : m.w;
-        const V3 ud = uq;
-        const float cos_theta = fminf(dot(-ud, n), 1.0f);
-        const bool cannot_refract = cannot_refract_exact(cos_theta, ri);
-        V3 dir;
-        if (cannot_refract || schlick_r0(cos_theta, r0) > uniform(s))
-            dir = reflect(ud, n);
-        else
-            dir = refract(ud, n, ri);
-        o = hp;
-        d = dir;
-        ++bounce;
-    } else {
-        if (code == SHADE_LIGHT) add = v3(m.x, m.y, m.z);
-        ended = true;
-    }
-    if (!ended) {                                            // the next bounce's limit test and roulette
-        if (bounce >= Q.max_bounces) {
-            ended = true;
-        } else if (bounce >= 3) {
-            float p = fmaxf(thr.x, fmaxf(thr.y, thr.z));
-            p = fminf(p, 0.95f);
-            if (uniform(s) > p) ended = true;
-            else thr = recip_exact_wave(p) * thr;
-        }
-    }
+    const Scattered r = scatter_step(h0, h1, Q.rows, Q.n_mats, Q.max_bounces, rng_load(rp), v3(ray0.x, ray0.y, ray0.z),
+                                     v3(ray1.x, ray1.y, ray1.z), v3(p0.x, p0.y, p0.z), __float_as_int(p0.w));
+    Rng s = r.s;
+    V3 o = r.o, d = r.d, thr = r.thr;
+    int bounce = r.bounce;
 
     // ---- the entry's fate
-    bool keep = !ended;
+    bool keep = !r.ended;
     float4 q1 = make_float4(p1.x, __int_as_float(CRT_PATH_ACTIVE), p1.z, p1.w);
-    if (ended) {
+    if (r.ended) {
         float* L = Q.linear + 3 * (size_t)pix;
-        const V3 sum = v3(L[0], L[1], L[2]) + add;           // pixel_color += ..., the (0, 0, 0) of a killed path too
+        const V3 sum = v3(L[0], L[1], L[2]) + r.add;         // pixel_color += ..., the (0, 0, 0) of a killed path too
         L[0] = sum.x; L[1] = sum.y; L[2] = sum.z;
         int32_t left = 0;
         if (Q.remaining) left = Q.remaining[pix];
         if (left > 0) {                                      // the pixel's next sample, as crt_camera_rays_kernel draws it
             Q.remaining[pix] = left - 1;
-            const crt_camera_desc& Cd = Q.cam;
-            CamRegs C;
-            C.pos = v3(Cd.origin[0], Cd.origin[1], Cd.origin[2]);
-            C.llc = v3(Cd.lower_left[0], Cd.lower_left[1], Cd.lower_left[2]);
-            C.hor = v3(Cd.horizontal[0], Cd.horizontal[1], Cd.horizontal[2]);
-            C.ver = v3(Cd.vertical[0], Cd.vertical[1], Cd.vertical[2]);
-            C.right = v3(Cd.right[0], Cd.right[1], Cd.right[2]);
-            C.up = v3(Cd.up[0], Cd.up[1], Cd.up[2]);
-            C.lens = Cd.lens_radius;
-            C.fw = (float)Q.width;
-            C.fh = (float)Q.height;
-            C.rfw = Q.rcp_w;
-            C.rfh = Q.rcp_h;
-            C.fast_uv = Q.fast_uv;
-            PathState S{};
-            S.s = s;
-            S.pixel = v3(0.f, 0.f, 0.f);
-            S.thr = v3(1.f, 1.f, 1.f);
-            S.remaining = 1; S.bounce = 0; S.need_new = true; S.rays = 0; S.paths = 0;
+            const CamRegs C = cam_regs(Q.cam, Q.width, Q.height, Q.rcp_w, Q.rcp_h, Q.fast_uv);
+            PathState S = new_sample_state(s);
             next_ray(S, C, (int)(pix % (uint32_t)Q.width), (int)(pix / (uint32_t)Q.width), 1);
             s = S.s;
             o = S.o;
@@ -362,7 +269,7 @@ __device__ __forceinline__ bool advance_entry(const PathAdvanceParams& Q, uint32
             keep = true;
         }
     }
-    rp[0] = s.v0; rp[1] = s.v1; rp[2] = s.v2; rp[3] = s.v3; rp[4] = s.v4; rp[5] = s.d;
+    rng_store(rp, s);
     out.r0 = make_float4(o.x, o.y, o.z, INF);
     out.r1 = make_float4(d.x, d.y, d.z, 0.f);
     out.p0 = make_float4(thr.x, thr.y, thr.z, __int_as_float(bounce));
@@ -454,9 +361,7 @@ int crt_renderer_camera_rays_device(crt_renderer* R, const int32_t* d_pixels, in
         return set_error(CRT_ERR_INVALID_ARGUMENT, "camera rays: pixel and RNG arrays must be 4-byte aligned");
     HIP_TRY(hipSetDevice(R->device));
     CameraRaysParams Q{};
-    Q.cam = R->cam;
-    Q.width = R->width; Q.height = R->height;
-    Q.rcp_w = R->rcp_w; Q.rcp_h = R->rcp_h; Q.fast_uv = R->fast_uv;
+    set_camera_frame(Q, R);
     Q.pixels = d_pixels;
     Q.n = (uint32_t)n;
     Q.rng = d_rng ? d_rng : R->d_rng;
@@ -541,9 +446,7 @@ int crt_scene_path_advance_device(const crt_scene* S, crt_renderer* R, const crt
     Q.n_pix = (uint32_t)(R->width * R->height);
     Q.n_mats = S->n_mats;
     Q.max_bounces = max_bounces;
-    Q.cam = R->cam;
-    Q.width = R->width; Q.height = R->height;
-    Q.rcp_w = R->rcp_w; Q.rcp_h = R->rcp_h; Q.fast_uv = R->fast_uv;
+    set_camera_frame(Q, R);
     const int64_t per_group = 256 * (int64_t)ADV_CHUNKS;
     hipLaunchKernelGGL(crt_path_advance_kernel, dim3((unsigned)((n + per_group - 1) / per_group)), dim3(256), 0, st, Q);
     HIP_TRY(hipGetLastError());

@@ -2,15 +2,18 @@
 
     make -C <tree>/raytracer-cuda_amd isa > <tree>/isa.log 2>&1      (in both trees)
     python tools/kernels_unchanged.py <parent tree> <this tree> [--show 'crt_render_kernel<false, 8, 7>' ...]
+                                      [--expect-changed crt_path_step_kernel ...]
 
-Compares, for every crt_render_kernel / crt_trace_kernel / crt_trace_lane_kernel instantiation and the two path-step
-kernels (crt_camera_rays_kernel, crt_path_step_kernel), the figures of
+Compares, for every crt_render_kernel / crt_trace_kernel / crt_trace_lane_kernel instantiation and the three path
+kernels (crt_camera_rays_kernel, crt_path_step_kernel, crt_path_advance_kernel), the figures of
 -Rpass-analysis=kernel-resource-usage (isa.log) and the assembly text of build/crt_hip.s from the kernel's label to its
 .end_amdhsa_kernel: every instruction and the kernel descriptor.  The compiler numbers a function's local labels
 `.LBB<f>_<b>` with f = the function's position in the module; a kernel added ahead of the template instantiations
 shifts f for all of them without changing an instruction, so f is replaced by a constant before the comparison (b, the
 block number inside the function, stays).  Prints the kernels that differ, the totals, the figures of the kernels named
-with --show and of every kernel only the second tree has; exit status 1 if any kernel differs.
+with --show and of every kernel only the second tree has; exit status 1 if any kernel differs.  A kernel named with
+--expect-changed may differ: it is printed with both trees' figures and instruction counts, and sets exit status 1
+only if a figure got worse (more VGPRs, any scratch or spill, fewer waves per SIMD, more LDS).
 """
 import argparse
 import re
@@ -18,7 +21,8 @@ import subprocess
 import sys
 from pathlib import Path
 
-WANTED = ("crt_render_kernel", "crt_trace_kernel", "crt_trace_lane_kernel", "crt_camera_rays_kernel", "crt_path_step_kernel")
+WANTED = ("crt_render_kernel", "crt_trace_kernel", "crt_trace_lane_kernel", "crt_camera_rays_kernel", "crt_path_step_kernel",
+          "crt_path_advance_kernel")
 FIGURES = r"(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\])"
 
 
@@ -50,6 +54,22 @@ def figures(log: Path) -> dict:
     return {k: "; ".join(v) for k, v in out.items()}
 
 
+def worse(parent: str, now: str) -> list:
+    """The figures of `now` that are worse than `parent`'s."""
+    a, b = (dict((k, int(v)) for k, v in (f.split(": ") for f in s.split("; "))) for s in (parent, now))
+    out = [k for k in ("VGPRs", "LDS Size [bytes/block]") if b[k] > a[k]]
+    out += [k for k in ("ScratchSize [bytes/lane]", "SGPRs Spill", "VGPRs Spill") if b[k] > 0]
+    if b["Occupancy [waves/SIMD]"] < a["Occupancy [waves/SIMD]"]:
+        out.append("Occupancy [waves/SIMD]")
+    return out
+
+
+def instructions(text: str) -> int:
+    """Instruction lines of a kernel's text: from its label to s_endpgm, without labels, directives and comments."""
+    body = text.split(".section", 1)[0].split("\n")[1:]
+    return sum(1 for line in body if line.startswith("\t") and not line.lstrip().startswith((".", ";")))
+
+
 def demangle(names) -> dict:
     res = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
     return dict(zip(names, res))
@@ -60,6 +80,7 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("now")
     ap.add_argument("--show", nargs="*", default=[])
+    ap.add_argument("--expect-changed", nargs="*", default=[], metavar="NAME")
     a = ap.parse_args()
     trees = [Path(a.parent), Path(a.now)]
     asm = [kernels(t / "raytracer-cuda_amd" / "build" / "crt_hip.s") for t in trees]
@@ -67,15 +88,25 @@ def main():
     names = demangle(sorted(set(asm[0]) | set(asm[1])))
     old = [k for k in asm[0] if any(w in k for w in WANTED)]
     differ = [k for k in old if asm[1].get(k) != asm[0][k] or fig[1].get(k) != fig[0][k]]
+    short = {k: names[k].replace("void ", "").split("(")[0] for k in names}
+    failed = [k for k in differ if short[k] not in a.expect_changed]
     for k in differ:
-        print("DIFFERS:", names[k])
+        if k in failed:
+            print("DIFFERS:", names[k])
+            continue
+        bad = worse(fig[0][k], fig[1][k]) if k in asm[1] and k in fig[1] else ["missing"]
+        print("DIFFERS, as expected:" if not bad else "DIFFERS, and is WORSE in " + ", ".join(bad) + ":", names[k])
+        print(f"    parent: {fig[0][k]}; {instructions(asm[0][k])} instructions")
+        print(f"    now:    {fig[1].get(k)}; {instructions(asm[1].get(k, ''))} instructions")
+        if bad:
+            failed.append(k)
     n_render = sum("crt_render_kernel" in k for k in old)
     print(f"{len(old)} kernels compared ({n_render} crt_render_kernel, {len(old) - n_render} ray-query and path-step kernels): "
           f"{len(old) - len(differ)} with the same figures and assembly text, {len(differ)} different; "
           f"{sum(asm[0][k].count(chr(10)) for k in old):,} lines in the parent, "
           f"{sum(asm[1][k].count(chr(10)) for k in old if k in asm[1]):,} now")
     for k in old:
-        if names[k].replace("void ", "").split("(")[0] in a.show:
+        if short[k] in a.show:
             print(names[k])
             print("    parent:", fig[0][k])
             print("    now:   ", fig[1].get(k))
@@ -83,7 +114,7 @@ def main():
         if k not in asm[0]:
             print("new:", names[k])
             print("    ", fig[1].get(k))
-    sys.exit(1 if differ else 0)
+    sys.exit(1 if failed else 0)
 
 
 if __name__ == "__main__":
