@@ -282,6 +282,17 @@ int crt_scene_occluded(const crt_scene* scene, const crt_ray* rays, int64_t n, c
  * errors of the launch are reported by crt_scene_trace_last_stats. */
 int crt_scene_trace_device(const crt_scene* scene, const crt_ray* d_rays, int64_t n, const crt_trace_options* opts,
                            crt_hit* d_hits, uint8_t* d_occluded, unsigned flags, void* stream);
+/* The indirect query (DESIGN.md "Device-side batch sizes"): traces rays [0, min(*d_n, capacity)), where *d_n is a 4-byte
+ * aligned device word that the kernel reads on `stream` when it runs; the host never reads it.  capacity, in [0, 2^30]
+ * (one launch serves one query), is what the host sizes the launch by: the grids, and automatic mode's choice between
+ * the two kernels.  The clamp is in the kernel: whatever the word holds, no row at or beyond capacity is read or
+ * written, and rows of d_hits / d_occluded from min(*d_n, capacity) on are not written.  The rows that are written
+ * hold crt_scene_trace_device's records of the same rays, bit for bit, in every mode; with CRT_TRACE_COUNT_WORK the
+ * `rays` of crt_scene_trace_last_stats is the clamped count.  capacity == 0: CRT_OK, nothing launched.  Everything else
+ * as crt_scene_trace_device.  Joined ABI version 3 after its first release, like the path steps below. */
+int crt_scene_trace_indirect_device(const crt_scene* scene, const crt_ray* d_rays, const uint32_t* d_n, int64_t capacity,
+                                    const crt_trace_options* opts, crt_hit* d_hits, uint8_t* d_occluded,
+                                    unsigned flags, void* stream);
 /* Of the last trace on this scene; synchronises with it.  The work counts are 0 unless it counted (the host entries
  * never count; mode 1 over a 4-wide scene counts rays only). */
 int crt_scene_trace_last_stats(const crt_scene* scene, crt_trace_stats* out);
@@ -343,6 +354,17 @@ int crt_scene_path_advance_device(const crt_scene* scene, crt_renderer* r, const
                                   const crt_path* d_paths, int64_t n, int max_bounces, uint32_t* d_rng, float* d_linear,
                                   int32_t* d_remaining, crt_ray* d_rays_out, crt_path* d_paths_out, uint32_t* d_count,
                                   void* stream);
+/* The indirect advance: what crt_scene_path_advance_device does for entries [0, min(*d_n, capacity)), with *d_n read by
+ * the kernel on `stream` and the clamp in the kernel.  The arrays hold capacity entries (the overlap checks use it in
+ * place of n); the grid is sized by it and workgroups beyond the count do nothing.  d_count, zeroed on the stream and
+ * then counting the appended entries, must not be d_n.  d_totals: NULL, or two 8-byte aligned 64-bit device words that
+ * the kernel adds to and never clears: [0] += the clamped input count, [1] += 1 if that count is not 0 -- how a loop
+ * that runs ahead of the host still reports its rays and iterations.  Every input entry appends at most one output
+ * entry, so *d_count <= min(*d_n, capacity): a chain of trace / advance calls may keep the first capacity. */
+int crt_scene_path_advance_indirect_device(const crt_scene* scene, crt_renderer* r, const crt_ray* d_rays,
+        const crt_hit* d_hits, const crt_path* d_paths, const uint32_t* d_n, int64_t capacity, int max_bounces,
+        uint32_t* d_rng, float* d_linear, int32_t* d_remaining, crt_ray* d_rays_out, crt_path* d_paths_out,
+        uint32_t* d_count, uint64_t* d_totals, void* stream);
 /* Input entries per reservation of output slots in this build of the advance kernel (64: one per wave; 256 .. 1024: one
  * per 256-lane workgroup over 1 .. 4 chunks).  Host only; for measurements, no result depends on it. */
 int crt_path_advance_entries(void);
@@ -358,6 +380,17 @@ int crt_path_advance_entries(void);
 typedef struct crt_wavefront_stats { uint64_t rays; uint32_t iterations; float ms; } crt_wavefront_stats;
 int crt_renderer_render_wavefront(crt_renderer* r, const crt_scene* scene, int spp, int max_bounces, unsigned flags,
                                   const crt_trace_options* trace_opts, crt_wavefront_stats* stats_out, void* stream);
+/* The same frame with the loop enqueued ahead of the host: blocks of sync_every rounds of indirect trace and indirect
+ * advance on two ping-pong count words, then one copy of the count, the totals and the error word and one host wait.
+ * The last count the host read is the capacity of every round of the next block; rounds enqueued after the count
+ * reached 0 trace nothing and append nothing, so the frame does not depend on sync_every.  stats_out->rays and
+ * ->iterations come from the device totals and equal crt_renderer_render_wavefront's.  The queries of one call OR their
+ * device errors into one word that is cleared once per call and reported as CRT_ERR_HIP.  sync_every >= 1 as is; 0 the
+ * library's default; negative: CRT_ERR_INVALID_ARGUMENT.  At most 2^30 pixels.  Everything else, the refusals
+ * included, as crt_renderer_render_wavefront, whose scratch it shares. */
+int crt_renderer_render_wavefront_queued(crt_renderer* r, const crt_scene* scene, int spp, int max_bounces, unsigned flags,
+                                         const crt_trace_options* trace_opts, int sync_every,
+                                         crt_wavefront_stats* stats_out, void* stream);
 /* Host only, no GPU (like crt_scene_export_identity): the per-material rows the step kernel reads, n_materials x 8
  * floats = (code, 0, 0, 0) (payload): code (int bits) 0 lambertian, 1 metal, 2 dielectric, 3 light, 4 unknown type
  * (emits 0); payload (albedo.xyz, 0), (albedo.xyz, min(roughness, 1)), (ior, 1 / ior, r0(1 / ior), r0(ior)) with

@@ -265,24 +265,45 @@ class Scene:
         o.mode, o.grid_waves, o.stack_lds, o.refill_threshold = int(mode), int(grid_waves), int(stack_lds), int(refill_threshold)
         return o
 
-    def _trace_torch(self, rays, o, want_hits, count_work):
+    def _trace_torch(self, rays, o, want_hits, count_work, count=None, out=None):
         import torch
+        if count is not None or out is not None:
+            # the kinds first, the device last (these checks come before any library call)
+            if count is not None and (not _is_torch(count) or count.dtype != torch.int32 or count.numel() != 1
+                                      or count.dim() > 1):
+                raise ValueError("count must be a 1-element int32 tensor")
+            kind = (torch.float32, torch.int32) if want_hits else (torch.uint8,)
+            if out is not None and (not _is_torch(out) or out.dtype not in kind or not out.is_contiguous()
+                                    or tuple(out.shape) != ((rays.shape[0], 8) if want_hits else (rays.shape[0],))):
+                raise ValueError("out must be a contiguous " + ("float32 or int32 [n, 8]" if want_hits else "uint8 [n]")
+                                 + " tensor as long as the rays")
         if (rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous()
                 or not rays.is_cuda or rays.device.index != self.device):
             raise ValueError("rays must be a contiguous float32 [n, 8] tensor on the scene's device")
+        for name, x in (("count", count), ("out", out)):
+            if x is not None and (not x.is_cuda or x.device.index != self.device):
+                raise ValueError(f"{name} must be on the scene's device")
         n = rays.shape[0]
-        hits = torch.empty((n, 8), dtype=torch.float32, device=rays.device) if want_hits else None
-        occ = None if want_hits else torch.empty((n,), dtype=torch.uint8, device=rays.device)
+        if out is not None:
+            hits, occ = (out, None) if want_hits else (None, out)
+        else:
+            hits = torch.empty((n, 8), dtype=torch.float32, device=rays.device) if want_hits else None
+            occ = None if want_hits else torch.empty((n,), dtype=torch.uint8, device=rays.device)
         stream = torch.cuda.current_stream(rays.device).cuda_stream
-        check(_lib.hip().crt_scene_trace_device(self.h, rays.data_ptr(), n, C.byref(o),
-                                                hits.data_ptr() if want_hits else None,
-                                                None if want_hits else occ.data_ptr(),
-                                                _lib.TRACE_COUNT_WORK if count_work else 0, stream),
-              "crt_scene_trace_device")
+        flags = _lib.TRACE_COUNT_WORK if count_work else 0
+        if count is not None:
+            check(_lib.require("crt_scene_trace_indirect_device")(
+                self.h, rays.data_ptr(), count.data_ptr(), n, C.byref(o), hits.data_ptr() if want_hits else None,
+                None if want_hits else occ.data_ptr(), flags, stream), "crt_scene_trace_indirect_device")
+        else:
+            check(_lib.hip().crt_scene_trace_device(self.h, rays.data_ptr(), n, C.byref(o),
+                                                    hits.data_ptr() if want_hits else None,
+                                                    None if want_hits else occ.data_ptr(), flags, stream),
+                  "crt_scene_trace_device")
         return hits if want_hits else occ
 
     def trace(self, rays_or_o, d=None, tmax=None, *, mode=0, grid_waves=0, stack_lds=0, refill_threshold=0,
-              count_work=False) -> dict:
+              count_work=False, count=None, out=None) -> dict:
         """Closest hit of every ray over [0.001, inf), reported when t <= tmax: a dict of arrays t, object, primitive,
         material, normal [n, 3], front_face (a miss: t = -1, the rest 0; see crt_hit in crt_hip.h).
 
@@ -295,8 +316,22 @@ class Scene:
 
         A torch query (and a numpy one with count_work) is asynchronous: a device error of its kernel, such as a
         traversal-stack entry dropped below the tree's bound, is raised by the next trace_stats() call, not here.
-        The numpy path without count_work waits for the kernel and raises such an error itself."""
+        The numpy path without count_work waits for the kernel and raises such an error itself.
+
+        count (torch rays only): a 1-element int32 tensor on the scene's device.  The query traces rays [0, min(count,
+        n)), count read by the kernel on the stream when it runs and never by the host (crt_scene_trace_indirect_device;
+        a negative count is its bit pattern, so it clamps to n); the result has n rows of which only those are
+        written.  out: the [n, 8] float32 or int32 tensor to write the hit rows into instead of a new one."""
         o = self._trace_options(mode, grid_waves, stack_lds, refill_threshold)
+        if count is not None or out is not None:
+            if not _is_torch(rays_or_o):
+                raise ValueError("count= and out= take torch rays")
+            if d is not None or tmax is not None:
+                raise ValueError("a torch query takes one [n, 8] tensor of crt_ray rows")
+            torch = __import__("torch")
+            got = self._trace_torch(rays_or_o, o, True, count_work, count, out)
+            f32, i32 = (got.view(torch.float32), got.view(torch.int32))
+            return dict(_hit_fields(f32, i32), f32=f32, i32=i32)
         if _is_torch(rays_or_o):
             if d is not None or tmax is not None:
                 raise ValueError("a torch query takes one [n, 8] tensor of crt_ray rows")
@@ -314,11 +349,18 @@ class Scene:
         return {k: v.copy() for k, v in _hit_fields(f32, f32.view(np.int32)).items()}
 
     def occluded(self, rays_or_o, d=None, tmax=None, *, mode=0, grid_waves=0, stack_lds=0, refill_threshold=0,
-                 count_work=False):
+                 count_work=False, count=None, out=None):
         """uint8 [n]: 1 where trace() with the same rays reports a hit (the 4-wide stream kernel retires a lane at its
         first accepted hit with t <= tmax).  numpy in, numpy out; a torch tensor in, a torch tensor out (see trace,
-        also for where a device error of an asynchronous query is raised: trace_stats())."""
+        also for where a device error of an asynchronous query is raised: trace_stats(), and for count and out: out
+        is a uint8 [n] tensor here)."""
         o = self._trace_options(mode, grid_waves, stack_lds, refill_threshold)
+        if count is not None or out is not None:
+            if not _is_torch(rays_or_o):
+                raise ValueError("count= and out= take torch rays")
+            if d is not None or tmax is not None:
+                raise ValueError("a torch query takes one [n, 8] tensor of crt_ray rows")
+            return self._trace_torch(rays_or_o, o, False, count_work, count, out)
         if _is_torch(rays_or_o):
             if d is not None or tmax is not None:
                 raise ValueError("a torch query takes one [n, 8] tensor of crt_ray rows")
@@ -350,11 +392,14 @@ class Scene:
         from . import paths as _paths
         _paths.path_step(self, rays, hits, paths, max_bounces, rng, linear)
 
-    def path_advance(self, renderer, rays, hits, paths, max_bounces, remaining, rng=None, linear=None, out=None):
+    def path_advance(self, renderer, rays, hits, paths, max_bounces, remaining, rng=None, linear=None, out=None,
+                     count_in=None, totals=None):
         """Step, regenerate and compact a batch of paths into an output batch (paths.advance): returns (rays_out,
-        paths_out, count), count a 1-element int32 device tensor."""
+        paths_out, count), count a 1-element int32 device tensor.  count_in: the device count of the input entries
+        (the count of the advance before); totals: an int64 [2] device tensor the call adds to."""
         from . import paths as _paths
-        return _paths.advance(self, renderer, rays, hits, paths, max_bounces, remaining, rng, linear, out)
+        return _paths.advance(self, renderer, rays, hits, paths, max_bounces, remaining, rng, linear, out, count_in,
+                              totals)
 
 
 def load_scene(obj_files, device: int = 0, **upload_options):
@@ -426,16 +471,25 @@ class Renderer:
         check(_lib.hip().crt_renderer_render(self.h, scene.h, int(spp), int(max_bounces), flags, stream), "render")
 
     def render_wavefront(self, scene: Scene, spp: int, max_bounces: int = 20, accumulate=False, trace_options=None,
-                         stream=None) -> dict:
+                         stream=None, sync_every=None) -> dict:
         """The frame of render() as a wavefront in the library (crt_renderer_render_wavefront): camera rays, then trace /
         advance rounds over the handle's own batches (164 B per pixel, allocated by the first call), one host wait per
         round.  The same sums, RNG state and ray count, bit for bit.  trace_options: keywords of Scene.trace (mode,
-        grid_waves, stack_lds, refill_threshold).  Synchronous.  Returns {"rays", "iterations", "ms"}."""
-        fn = _lib.require("crt_renderer_render_wavefront")
+        grid_waves, stack_lds, refill_threshold).  Synchronous.  Returns {"rays", "iterations", "ms"}.
+
+        sync_every: None is that loop.  An int is the loop enqueued ahead (crt_renderer_render_wavefront_queued): the
+        rounds take their batch size from the device, and the host waits once per sync_every rounds (0: the library's
+        default).  The same frame and the same numbers for every value."""
         o = Scene._trace_options(**dict(dict(mode=0, grid_waves=0, stack_lds=0, refill_threshold=0), **(trace_options or {})))
         s = _lib.WavefrontStats()
-        check(fn(self.h, scene.h, int(spp), int(max_bounces), RENDER_ACCUMULATE if accumulate else 0, C.byref(o),
-                 C.byref(s), stream), "render_wavefront")
+        flags = RENDER_ACCUMULATE if accumulate else 0
+        if sync_every is None:
+            fn = _lib.require("crt_renderer_render_wavefront")
+            check(fn(self.h, scene.h, int(spp), int(max_bounces), flags, C.byref(o), C.byref(s), stream), "render_wavefront")
+        else:
+            fn = _lib.require("crt_renderer_render_wavefront_queued")
+            check(fn(self.h, scene.h, int(spp), int(max_bounces), flags, C.byref(o), int(sync_every), C.byref(s), stream),
+                  "render_wavefront_queued")
         return {"rays": int(s.rays), "iterations": int(s.iterations), "ms": float(s.ms)}
 
     def resolve(self, scale: float, stream=None):

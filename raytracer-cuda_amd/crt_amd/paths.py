@@ -68,6 +68,14 @@ def _batch(rays, hits, paths, max_bounces) -> int:
     return n
 
 
+def _count(x, name):
+    """x is a 1-element int32 tensor (a device count), or ValueError."""
+    import torch
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.int32 or x.numel() != 1 or x.dim() > 1:
+        raise ValueError(f"{name} must be a 1-element int32 tensor")
+    return x
+
+
 def _on_device(device, **tensors):
     """Checked last, so that a tensor wrong in kind is reported as that: every tensor lives on cuda:`device`."""
     for name, x in tensors.items():
@@ -142,7 +150,8 @@ def _same_memory(a, b) -> bool:
     return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
-def advance(scene, renderer, rays, hits, paths, max_bounces, remaining, rng=None, linear=None, out=None):
+def advance(scene, renderer, rays, hits, paths, max_bounces, remaining, rng=None, linear=None, out=None, count_in=None,
+            totals=None):
     """Step, regenerate and compact (crt_scene_path_advance_device): every ACTIVE path of the read-only batch takes one
     bounce as path_step gives it; one that goes on is appended to the output batch; one that ended adds to its pixel's
     sum and, while remaining[pixel] > 0, is replaced by that pixel's next camera sample (remaining[pixel] -= 1), drawn on
@@ -151,10 +160,23 @@ def advance(scene, renderer, rays, hits, paths, max_bounces, remaining, rng=None
     or float32 [>= n, 8]) that overlap no input (None: allocated here).
     Returns (rays_out, paths_out, count): count is a 1-element int32 device tensor, the entries appended; they are rows
     [0, count) of the outputs in no particular order, the other rows are unspecified.  No host copy, no synchronisation;
-    enqueued on torch's current stream."""
+    enqueued on torch's current stream.
+
+    count_in: a 1-element int32 device tensor, typically the count of the advance before.  The call then advances entries
+    [0, min(count_in, n)) of the batch, count_in read by the kernel on the stream and never by the host
+    (crt_scene_path_advance_indirect_device): a loop of Scene.trace(count=) and advance(count_in=) on ping-pong
+    batches runs without a host read, and since an entry appends at most one entry, the first batch's length serves
+    all of them.  totals (with count_in): an int64 [2] device tensor the kernel adds (min(count_in, n), 1 if that is not
+    0) to: the rays and the iterations of such a loop."""
     import torch
     dev = scene.device
     n = _batch(rays, hits, paths, max_bounces)
+    if count_in is not None:
+        _count(count_in, "count_in")
+    if totals is not None:
+        if count_in is None:
+            raise ValueError("totals needs count_in")
+        _flat(totals, "totals", torch.int64, numel=2)
     if not _is_renderer(renderer):
         raise ValueError("renderer must be a Renderer")
     if renderer.device != dev:
@@ -179,18 +201,24 @@ def advance(scene, renderer, rays, hits, paths, max_bounces, remaining, rng=None
                     raise ValueError(f"{name} aliases an input")
         if _same_memory(rays_out, paths_out):
             raise ValueError("out rays aliases out paths")
-    _on_device(dev, rays=rays, hits=hits, paths=paths, remaining=remaining, rng=rng, linear=linear,
-               **({} if out is None else {"out rays": out[0], "out paths": out[1]}))
-    fn = _lib.require("crt_scene_path_advance_device")
+    _on_device(dev, rays=rays, hits=hits, paths=paths, remaining=remaining, rng=rng, linear=linear, count_in=count_in,
+               totals=totals, **({} if out is None else {"out rays": out[0], "out paths": out[1]}))
+    fn = _lib.require("crt_scene_path_advance_device" if count_in is None else "crt_scene_path_advance_indirect_device")
     tdev = torch.device("cuda", dev)
     if out is None:
         rays_out = torch.empty((n, 8), dtype=torch.float32, device=tdev)
         paths_out = torch.empty((n, 8), dtype=torch.int32, device=tdev)
     count = torch.empty((1,), dtype=torch.int32, device=tdev)
     ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
-    check(fn(scene.h, renderer.h, rays.data_ptr(), hits.data_ptr(), paths.data_ptr(), n, int(max_bounces), ptr(rng),
-             ptr(linear), ptr(remaining), rays_out.data_ptr(), paths_out.data_ptr(), count.data_ptr(),
-             torch.cuda.current_stream(tdev).cuda_stream), "crt_scene_path_advance_device")
+    stream = torch.cuda.current_stream(tdev).cuda_stream
+    if count_in is None:
+        check(fn(scene.h, renderer.h, rays.data_ptr(), hits.data_ptr(), paths.data_ptr(), n, int(max_bounces), ptr(rng),
+                 ptr(linear), ptr(remaining), rays_out.data_ptr(), paths_out.data_ptr(), count.data_ptr(), stream),
+              "crt_scene_path_advance_device")
+    else:
+        check(fn(scene.h, renderer.h, rays.data_ptr(), hits.data_ptr(), paths.data_ptr(), count_in.data_ptr(), n,
+                 int(max_bounces), ptr(rng), ptr(linear), ptr(remaining), rays_out.data_ptr(), paths_out.data_ptr(),
+                 count.data_ptr(), ptr(totals), stream), "crt_scene_path_advance_indirect_device")
     return rays_out, paths_out, count
 
 
@@ -236,7 +264,7 @@ class _Phases:
 
 
 def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None, trace_options=None,
-           profile=None, compact="torch") -> dict:
+           profile=None, compact="torch", sync_every=1) -> dict:
     """The reference driver: spp samples per pixel as a wavefront of camera_rays / Scene.trace / Scene.path_step calls on
     the renderer's own RNG state and (fresh) sums, so renderer.linear(), rng_state() and resolve() work afterwards
     and hold what renderer.render(scene, spp, max_bounces) leaves, bit for bit.
@@ -252,6 +280,13 @@ def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None
     preallocated ping-pong batches, and the host waits once per iteration, for the 4-byte count (regenerate=False:
     advance with remaining=None as the compaction).  No torch indexing; the same bits.  on_bounce then sees the batch
     before the advance and may edit it in place; the profile's phases are trace, advance and count, its entries n.
+
+    sync_every (compact="device"): 1 is the loop above.  K > 1 enqueues blocks of K iterations of Scene.trace(count=)
+    and advance(count_in=) between two reads of the count: the kernels take the batch size from the device, and the
+    last size the host read bounds the batches of the whole block (a batch is never larger than the one before it).
+    The same bits, rays and iterations.  on_bounce is then called with a fourth argument, the device count: its first
+    three arguments are views of the bound's length, whose rows from the count on are stale, and only rows below the
+    count may be edited.  The profile's entries n are then the bounds.
     Returns {"rays": rays traced, "iterations": trace / step rounds}."""
     import torch
     spp, max_bounces = int(spp), int(max_bounces)
@@ -259,6 +294,11 @@ def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None
         raise ValueError("max_bounces must be >= 1")
     if compact not in ("torch", "device"):
         raise ValueError('compact must be "torch" or "device"')
+    if sync_every != int(sync_every) or int(sync_every) < 1:
+        raise ValueError("sync_every must be an integer >= 1")
+    sync_every = int(sync_every)
+    if sync_every != 1 and compact != "device":
+        raise ValueError('sync_every other than 1 needs compact="device"')
     opts = dict(trace_options or {})
     n_pix = renderer.width * renderer.height
     tdev = torch.device("cuda", renderer.device)
@@ -275,7 +315,33 @@ def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None
         path_step(scene, rays, hits, paths, max_bounces, renderer, renderer)
         phases.mark("step")
 
-    if compact == "device" and spp > 0:
+    if compact == "device" and spp > 0 and sync_every > 1:
+        remaining = torch.full((n_pix,), spp - 1, dtype=torch.int32, device=tdev) if regenerate else None
+        pong = (torch.empty((n_pix, 8), dtype=torch.float32, device=tdev),
+                torch.empty((n_pix, 8), dtype=torch.int32, device=tdev))
+        hits = torch.empty((n_pix, 8), dtype=torch.float32, device=tdev)
+        totals = torch.zeros((2,), dtype=torch.int64, device=tdev)
+        for _ in range(1 if regenerate else spp):
+            phases.mark("start")
+            batches, cur = [camera_rays(renderer), pong], 0
+            count = torch.full((1,), n_pix, dtype=torch.int32, device=tdev)
+            m = n_pix
+            while m:
+                for _ in range(sync_every):
+                    rays, paths = batches[cur][0][:m], batches[cur][1][:m]
+                    phases.mark("start")
+                    scene.trace(rays, count=count, out=hits[:m], **opts)
+                    phases.mark("trace", n=m)
+                    if on_bounce is not None:
+                        on_bounce(rays, hits[:m], paths, count)
+                    _, _, count = advance(scene, renderer, rays, hits[:m], paths, max_bounces, remaining,
+                                          out=batches[cur ^ 1], count_in=count, totals=totals)
+                    phases.mark("advance")
+                    cur ^= 1
+                m = min(int(count), m)                        # the block's one wait
+                phases.mark("count")
+        total, iterations = (int(v) for v in totals.tolist())
+    elif compact == "device" and spp > 0:
         remaining = torch.full((n_pix,), spp - 1, dtype=torch.int32, device=tdev) if regenerate else None
         pong = (torch.empty((n_pix, 8), dtype=torch.float32, device=tdev),
                 torch.empty((n_pix, 8), dtype=torch.int32, device=tdev))

@@ -13,6 +13,9 @@
 //                            per-material rows), then next_ray()'s bounce-limit test and Russian roulette for the
 //                            bounce that follows.
 //   crt_path_step_kernel     one lane per path: scatter_step() in place.
+//   crt_path_advance_kernel, crt_path_advance_indirect_kernel
+//                            further down: step, regenerate and compact, and the same body
+//                            (crt_path_advance_body.inc) over a device-side entry count (§18).
 //
 // unit(), the reciprocal and the glass test pick their fast or IEEE sequence by a ballot over the lanes that run them;
 // both sequences are correctly rounded, so the lanes a wave happens to hold (a partial last wave, entries that came in
@@ -286,51 +289,30 @@ __device__ __forceinline__ void advance_store(const PathAdvanceParams& Q, uint32
 }
 
 __global__ __launch_bounds__(256) void crt_path_advance_kernel(PathAdvanceParams Q) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    AdvanceRows out[ADV_CHUNKS];
-    bool keep[ADV_CHUNKS];
-    uint32_t rank[ADV_CHUNKS], cnt[ADV_CHUNKS];              // the lane's place among its wave's appending lanes, their number
-#pragma unroll
-    for (int c = 0; c < ADV_CHUNKS; ++c) {
-        const uint32_t i = (blockIdx.x * (uint32_t)ADV_CHUNKS + (uint32_t)c) * 256u + threadIdx.x;
-        keep[c] = false;
-        if (i < Q.n) keep[c] = advance_entry(Q, i, out[c]);
-        const unsigned long long b = __builtin_amdgcn_ballot_w64(keep[c]);
-        rank[c] = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-        cnt[c] = (uint32_t)__builtin_popcountll(b);
+#define ADVANCE_BODY_N Q.n
+#include "crt_path_advance_body.inc"
+#undef ADVANCE_BODY_N
+}
+
+// The indirect form: the number of input entries is a device word the kernel reads when it runs, clamped
+// to the capacity the host sized the grid and the arrays by (Q.n).  Workgroups beyond the count do nothing.
+struct PathAdvanceIndirectParams {
+    PathAdvanceParams Q;                   // n: the capacity
+    const uint32_t* __restrict__ d_n;      // the entry count, on the device
+    unsigned long long* __restrict__ totals;   // null, or [0] += the clamped count, [1] += 1 if it is not 0
+};
+
+__global__ __launch_bounds__(256) void crt_path_advance_indirect_kernel(PathAdvanceIndirectParams I) {
+    const PathAdvanceParams& Q = I.Q;
+    const uint32_t n = min(*I.d_n, Q.n);
+    if (I.totals && blockIdx.x == 0 && threadIdx.x == 0) {   // kernels of one stream are ordered: one lane, plain adds
+        I.totals[0] += n;
+        I.totals[1] += n ? 1u : 0u;
     }
-    if constexpr (ADV_PER_WAVE) {
-        uint32_t base = 0;
-        if (lane == 0 && cnt[0]) base = atomicAdd(Q.count, cnt[0]);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if (keep[0]) advance_store(Q, base + rank[0], out[0]);
-    } else {
-        __shared__ uint32_t wave_cnt[ADV_CHUNKS * 4];        // appending lanes per (chunk, wave)
-        __shared__ uint32_t group_base;
-        if (lane == 0)
-#pragma unroll
-            for (int c = 0; c < ADV_CHUNKS; ++c) wave_cnt[c * 4 + (int)wave] = cnt[c];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t total = 0;
-            for (int k = 0; k < ADV_CHUNKS * 4; ++k) total += wave_cnt[k];
-            group_base = total ? atomicAdd(Q.count, total) : 0u;
-        }
-        __syncthreads();
-        uint32_t at = group_base;
-#pragma unroll
-        for (int c = 0; c < ADV_CHUNKS; ++c) {
-            uint32_t before = 0, whole = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const uint32_t k = wave_cnt[c * 4 + w];
-                if ((uint32_t)w < wave) before += k;
-                whole += k;
-            }
-            if (keep[c]) advance_store(Q, at + before + rank[c], out[c]);
-            at += whole;
-        }
-    }
+    if (blockIdx.x * (256u * (uint32_t)ADV_CHUNKS) >= n) return;
+#define ADVANCE_BODY_N n
+#include "crt_path_advance_body.inc"
+#undef ADVANCE_BODY_N
 }
 
 // ------------------------------------------------------------------ host side
@@ -344,6 +326,70 @@ int path_batch_args(const char* what, int64_t n, const void* a, const void* b, c
     if (!a || !b || !c) return set_error(CRT_ERR_INVALID_ARGUMENT, std::string(what) + ": null array");
     if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u)
         return set_error(CRT_ERR_INVALID_ARGUMENT, std::string(what) + ": ray, hit and path arrays must be 16-byte aligned");
+    return CRT_OK;
+}
+
+// The advance entries: the argument checks, the count's reset and the launch.  d_n null: entries [0, n).  Otherwise the
+// indirect call: n is the capacity, the kernel advances entries [0, min(*d_n, n)) and adds to d_totals (optional).
+int advance_enqueue(const std::string& what, const crt_scene* S, crt_renderer* R, const crt_ray* d_rays,
+                    const crt_hit* d_hits, const crt_path* d_paths, const uint32_t* d_n, int64_t n, int max_bounces,
+                    uint32_t* d_rng, float* d_linear, int32_t* d_remaining, crt_ray* d_rays_out, crt_path* d_paths_out,
+                    uint32_t* d_count, uint64_t* d_totals, void* stream) {
+    if (!S) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": null scene");
+    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": null renderer");
+    if (int rc = path_batch_args(what.c_str(), n, d_rays, d_hits, d_paths)) return rc;
+    if (max_bounces < 1) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": max_bounces must be >= 1");
+    if (!d_count) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": null count");
+    if (d_n && d_n == d_count)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": the output count overlaps the input count");
+    if (n > 0) {
+        if (!d_rays_out || !d_paths_out) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": null output array");
+        if (((uintptr_t)d_rays_out | (uintptr_t)d_paths_out) & 15u)
+            return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": output arrays must be 16-byte aligned");
+        const uintptr_t bytes = (uintptr_t)n * 32u;          // every batch array holds n 32-B entries
+        const uintptr_t in[3] = {(uintptr_t)d_rays, (uintptr_t)d_hits, (uintptr_t)d_paths};
+        const uintptr_t out[2] = {(uintptr_t)d_rays_out, (uintptr_t)d_paths_out};
+        for (uintptr_t a : out)
+            for (uintptr_t b : in)
+                if (a < b + bytes && b < a + bytes)
+                    return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": an output array overlaps an input array");
+        if (out[0] < out[1] + bytes && out[1] < out[0] + bytes)
+            return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": the output arrays overlap");
+    }
+    if (((uintptr_t)d_rng | (uintptr_t)d_linear | (uintptr_t)d_remaining | (uintptr_t)d_count | (uintptr_t)d_n) & 3u)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": RNG state, sums, remaining and counts must be 4-byte aligned");
+    if ((uintptr_t)d_totals & 7u) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": totals must be 8-byte aligned");
+    if (S->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": scene and renderer on different devices");
+    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": the renderer has no camera (crt_renderer_set_camera)");
+    HIP_TRY(hipSetDevice(S->device));
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
+    if (n == 0) return CRT_OK;
+    PathAdvanceParams Q{};
+    Q.rays = reinterpret_cast<const float4*>(d_rays);
+    Q.hits = reinterpret_cast<const float4*>(d_hits);
+    Q.paths = reinterpret_cast<const float4*>(d_paths);
+    Q.rows = S->d_mat_rows;
+    Q.rng = d_rng ? d_rng : R->d_rng;
+    Q.linear = d_linear ? d_linear : R->d_sum;
+    Q.remaining = d_remaining;
+    Q.rays_out = reinterpret_cast<float4*>(d_rays_out);
+    Q.paths_out = reinterpret_cast<float4*>(d_paths_out);
+    Q.count = d_count;
+    Q.n = (uint32_t)n;
+    Q.n_pix = (uint32_t)(R->width * R->height);
+    Q.n_mats = S->n_mats;
+    Q.max_bounces = max_bounces;
+    set_camera_frame(Q, R);
+    const int64_t per_group = 256 * (int64_t)ADV_CHUNKS;
+    const dim3 grid((unsigned)((n + per_group - 1) / per_group));
+    if (d_n) {
+        const PathAdvanceIndirectParams I{Q, d_n, reinterpret_cast<unsigned long long*>(d_totals)};
+        hipLaunchKernelGGL(crt_path_advance_indirect_kernel, grid, dim3(256), 0, st, I);
+    } else {
+        hipLaunchKernelGGL(crt_path_advance_kernel, grid, dim3(256), 0, st, Q);
+    }
+    HIP_TRY(hipGetLastError());
     return CRT_OK;
 }
 
@@ -404,53 +450,17 @@ int crt_scene_path_advance_device(const crt_scene* S, crt_renderer* R, const crt
                                   const crt_path* d_paths, int64_t n, int max_bounces, uint32_t* d_rng, float* d_linear,
                                   int32_t* d_remaining, crt_ray* d_rays_out, crt_path* d_paths_out, uint32_t* d_count,
                                   void* stream) {
-    if (!S) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: null scene");
-    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: null renderer");
-    if (int rc = path_batch_args("path advance", n, d_rays, d_hits, d_paths)) return rc;
-    if (max_bounces < 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: max_bounces must be >= 1");
-    if (!d_count) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: null count");
-    if (n > 0) {
-        if (!d_rays_out || !d_paths_out) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: null output array");
-        if (((uintptr_t)d_rays_out | (uintptr_t)d_paths_out) & 15u)
-            return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: output arrays must be 16-byte aligned");
-        const uintptr_t bytes = (uintptr_t)n * 32u;          // every batch array holds n 32-B entries
-        const uintptr_t in[3] = {(uintptr_t)d_rays, (uintptr_t)d_hits, (uintptr_t)d_paths};
-        const uintptr_t out[2] = {(uintptr_t)d_rays_out, (uintptr_t)d_paths_out};
-        for (uintptr_t a : out)
-            for (uintptr_t b : in)
-                if (a < b + bytes && b < a + bytes)
-                    return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: an output array overlaps an input array");
-        if (out[0] < out[1] + bytes && out[1] < out[0] + bytes)
-            return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: the output arrays overlap");
-    }
-    if (((uintptr_t)d_rng | (uintptr_t)d_linear | (uintptr_t)d_remaining | (uintptr_t)d_count) & 3u)
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: RNG state, sums, remaining and count must be 4-byte aligned");
-    if (S->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: scene and renderer on different devices");
-    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, "path advance: the renderer has no camera (crt_renderer_set_camera)");
-    HIP_TRY(hipSetDevice(S->device));
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
-    if (n == 0) return CRT_OK;
-    PathAdvanceParams Q{};
-    Q.rays = reinterpret_cast<const float4*>(d_rays);
-    Q.hits = reinterpret_cast<const float4*>(d_hits);
-    Q.paths = reinterpret_cast<const float4*>(d_paths);
-    Q.rows = S->d_mat_rows;
-    Q.rng = d_rng ? d_rng : R->d_rng;
-    Q.linear = d_linear ? d_linear : R->d_sum;
-    Q.remaining = d_remaining;
-    Q.rays_out = reinterpret_cast<float4*>(d_rays_out);
-    Q.paths_out = reinterpret_cast<float4*>(d_paths_out);
-    Q.count = d_count;
-    Q.n = (uint32_t)n;
-    Q.n_pix = (uint32_t)(R->width * R->height);
-    Q.n_mats = S->n_mats;
-    Q.max_bounces = max_bounces;
-    set_camera_frame(Q, R);
-    const int64_t per_group = 256 * (int64_t)ADV_CHUNKS;
-    hipLaunchKernelGGL(crt_path_advance_kernel, dim3((unsigned)((n + per_group - 1) / per_group)), dim3(256), 0, st, Q);
-    HIP_TRY(hipGetLastError());
-    return CRT_OK;
+    return advance_enqueue("path advance", S, R, d_rays, d_hits, d_paths, nullptr, n, max_bounces, d_rng, d_linear,
+                           d_remaining, d_rays_out, d_paths_out, d_count, nullptr, stream);
+}
+
+int crt_scene_path_advance_indirect_device(const crt_scene* S, crt_renderer* R, const crt_ray* d_rays, const crt_hit* d_hits,
+                                           const crt_path* d_paths, const uint32_t* d_n, int64_t capacity, int max_bounces,
+                                           uint32_t* d_rng, float* d_linear, int32_t* d_remaining, crt_ray* d_rays_out,
+                                           crt_path* d_paths_out, uint32_t* d_count, uint64_t* d_totals, void* stream) {
+    if (!d_n) return set_error(CRT_ERR_INVALID_ARGUMENT, "indirect path advance: null input count");
+    return advance_enqueue("indirect path advance", S, R, d_rays, d_hits, d_paths, d_n, capacity, max_bounces, d_rng,
+                           d_linear, d_remaining, d_rays_out, d_paths_out, d_count, d_totals, stream);
 }
 
 int crt_path_advance_entries(void) { return ADV_ENTRIES; }
@@ -465,8 +475,16 @@ struct WavefrontScratch {
     int32_t* remaining = nullptr;
     uint32_t* d_count = nullptr;
     uint32_t* h_count = nullptr;            // pinned: [0] the count, [2..3] the trace error word
+    // the queued loop (crt_renderer_render_wavefront_queued): 8 device words and their pinned copy
+    uint32_t* d_queue = nullptr;            // [0], [1] the ping-pong counts, [2] the sticky error word, [4..7] the totals
+    uint32_t* h_queue = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
+
+constexpr int QUEUE_WORDS = 8, QUEUE_ERR = 2, QUEUE_TOTALS = 4;   // WavefrontScratch::d_queue
+// crt_renderer_render_wavefront_queued's sync_every = 0: iterations enqueued between two host waits
+// (profiles/indirect/path_bench.jsonl)
+constexpr int QUEUE_SYNC_EVERY = 32;
 
 void crtx_free_wavefront_scratch(crt_renderer* R) {
     WavefrontScratch* X = R->wavefront;
@@ -479,6 +497,8 @@ void crtx_free_wavefront_scratch(crt_renderer* R) {
     if (X->remaining) (void)hipFree(X->remaining);
     if (X->d_count) (void)hipFree(X->d_count);
     if (X->h_count) (void)hipHostFree(X->h_count);
+    if (X->d_queue) (void)hipFree(X->d_queue);
+    if (X->h_queue) (void)hipHostFree(X->h_queue);
     if (X->ev0) (void)hipEventDestroy(X->ev0);
     if (X->ev1) (void)hipEventDestroy(X->ev1);
     delete X;
@@ -501,11 +521,14 @@ int wavefront_scratch(crt_renderer* R, WavefrontScratch** out) {
         HIP_TRY(hipMalloc((void**)&X->remaining, n_pix * 4));
         HIP_TRY(hipMalloc((void**)&X->d_count, 4));
         HIP_TRY(hipHostMalloc((void**)&X->h_count, 16));
+        HIP_TRY(hipMalloc((void**)&X->d_queue, QUEUE_WORDS * 4));
+        HIP_TRY(hipHostMalloc((void**)&X->h_queue, QUEUE_WORDS * 4));
         HIP_TRY(hipEventCreate(&X->ev0));
         HIP_TRY(hipEventCreate(&X->ev1));
     }
     WavefrontScratch* X = R->wavefront;
-    if (!X->rays[1] || !X->paths[1] || !X->hits || !X->remaining || !X->d_count || !X->h_count || !X->ev1)
+    if (!X->rays[1] || !X->paths[1] || !X->hits || !X->remaining || !X->d_count || !X->h_count || !X->d_queue ||
+        !X->h_queue || !X->ev1)
         return set_error(CRT_ERR_OUT_OF_MEMORY, "the wavefront scratch of this renderer could not be allocated");
     *out = X;
     return CRT_OK;
@@ -569,6 +592,82 @@ int crt_renderer_render_wavefront(crt_renderer* R, const crt_scene* Sc, int spp,
     if (stats_out) *stats_out = stats;
     if (X->h_count[2] | X->h_count[3])
         HIP_TRY(hipMemcpy(S->trace->d_stats + TRACE_ERR_WORD, X->h_count + 2, 8, hipMemcpyHostToDevice));
+    return trace_take_error(S->trace);
+}
+
+int crt_renderer_render_wavefront_queued(crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags,
+                                         const crt_trace_options* trace_opts, int sync_every,
+                                         crt_wavefront_stats* stats_out, void* stream) {
+    if (!R || !Sc) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: null argument");
+    if (spp < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: negative spp");
+    if (max_bounces < 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: max_bounces must be >= 1");
+    if (sync_every < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: sync_every must be >= 0");
+    if (flags & ~(CRT_RENDER_ACCUMULATE | CRT_RENDER_COUNT_WORK))
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: unknown flag");
+    if (Sc->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: scene and renderer on different devices");
+    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: camera not set");
+    if (flags & CRT_RENDER_COUNT_WORK)
+        return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: work counters are the render kernels' (crt_renderer_render)");
+    if (R->tile_shards > 1) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: pixel sharding is crt_renderer_render's");
+    const int64_t n_pix = (int64_t)R->width * R->height;
+    if (n_pix >= ((int64_t)1 << 31)) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: 2^31 pixels or more");
+    if (n_pix > TRACE_LAUNCH_RAYS) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: the queued loop takes at most 2^30 pixels");
+    const int block = sync_every ? sync_every : QUEUE_SYNC_EVERY;
+    crt_scene* S = const_cast<crt_scene*>(Sc);   // the trace scratch belongs to the handle (handles are not thread-safe)
+    HIP_TRY(hipSetDevice(R->device));
+    hipStream_t st = (hipStream_t)stream;
+    crt_wavefront_stats stats{};
+    if (!(flags & CRT_RENDER_ACCUMULATE))
+        HIP_TRY(hipMemsetAsync(R->d_sum, 0, (size_t)n_pix * 3 * sizeof(float), st));
+    if (spp == 0 || n_pix == 0) {
+        HIP_TRY(hipStreamSynchronize(st));
+        if (stats_out) *stats_out = stats;
+        return CRT_OK;
+    }
+    WavefrontScratch* X = nullptr;
+    if (int rc = wavefront_scratch(R, &X)) return rc;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->remaining, spp - 1, (size_t)n_pix, st));
+    // the error word and the totals are cleared once per call; the first batch is every pixel
+    HIP_TRY(hipMemsetAsync(X->d_queue, 0, QUEUE_WORDS * 4, st));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->d_queue, (int)n_pix, 1, st));
+    HIP_TRY(hipEventRecord(X->ev0, st));
+    if (int rc = crt_renderer_camera_rays_device(R, nullptr, n_pix, nullptr, X->rays[0], X->paths[0], stream)) return rc;
+    unsigned* d_err = X->d_queue + QUEUE_ERR;
+    uint64_t* d_totals = reinterpret_cast<uint64_t*>(X->d_queue + QUEUE_TOTALS);
+    int cur = 0;
+    // A batch is never larger than the one before it (an input entry appends at most one output entry), so the last
+    // count the host read bounds every later one: it is the capacity of the whole block.  Iterations enqueued after the
+    // count reached 0 trace nothing and append nothing.
+    int64_t m = n_pix;
+    while (m > 0) {
+        for (int k = 0; k < block; ++k) {
+            if (int rc = trace_enqueue(S, X->rays[cur], m, trace_opts, X->hits, nullptr, 0, st, X->d_queue + cur, d_err))
+                return rc;
+            if (int rc = crt_scene_path_advance_indirect_device(S, R, X->rays[cur], X->hits, X->paths[cur], X->d_queue + cur,
+                                                                m, max_bounces, nullptr, nullptr, X->remaining,
+                                                                X->rays[cur ^ 1], X->paths[cur ^ 1], X->d_queue + (cur ^ 1),
+                                                                d_totals, stream))
+                return rc;
+            cur ^= 1;
+        }
+        // the block's one copy (the counts, the error word, the totals) and its one host wait
+        HIP_TRY(hipMemcpyAsync(X->h_queue, X->d_queue, QUEUE_WORDS * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        m = std::min<int64_t>(X->h_queue[cur], m);
+        if (X->h_queue[QUEUE_ERR]) break;                    // reported below, as trace_take_error words it
+    }
+    HIP_TRY(hipEventRecord(X->ev1, st));
+    HIP_TRY(hipEventSynchronize(X->ev1));
+    HIP_TRY(hipEventElapsedTime(&stats.ms, X->ev0, X->ev1));
+    uint64_t totals[2];
+    std::memcpy(totals, X->h_queue + QUEUE_TOTALS, sizeof totals);
+    stats.rays = totals[0];
+    stats.iterations = (uint32_t)totals[1];
+    if (stats_out) *stats_out = stats;
+    if (X->h_queue[QUEUE_ERR]) {                             // into the handle's own word, for trace_take_error's report
+        const unsigned long long word = X->h_queue[QUEUE_ERR];
+        HIP_TRY(hipMemcpy(S->trace->d_stats + TRACE_ERR_WORD, &word, 8, hipMemcpyHostToDevice));
+    }
     return trace_take_error(S->trace);
 }
 

@@ -12,6 +12,10 @@
 //                                  removed wavefront variant 5 paid a vmcnt wait per node load for them).
 //   crt_trace_lane_kernel<COUNT>   every scene: one ray per lane through trace<> (threaded) or trace4 (4-wide), the
 //                                  bit-exact baseline the stream kernel is measured against; no early exit.
+//   crt_trace_indirect_kernel<ANY, COUNT>, crt_trace_lane_indirect_kernel<COUNT>
+//                                  the same two bodies (crt_trace_stream_body.inc, crt_trace_lane_body.inc) with the
+//                                  number of rays read from a device word and clamped to the launch's capacity
+//                                  (DESIGN.md §18).
 #pragma once
 
 struct TraceParams {
@@ -67,124 +71,47 @@ __device__ __forceinline__ void trace_add_stats(const TraceParams& T, int lane, 
 
 template <bool ANY, bool COUNT>
 __global__ __launch_bounds__(64, 6) void crt_trace_kernel(TraceParams T) {
-    const RenderParams& P = T.P;
-    constexpr int SD = CRT_STACK6;           // LDS stack entries per lane at 6 one-wave workgroups per SIMD
-    constexpr int TOPN = TOP_NODES;
-    __shared__ WaveLdsWide L;
-    __shared__ uint32_t stk[SD * 64];
-    __shared__ __attribute__((aligned(16))) float sph_lds[32];   // the two per-ray spheres, as crt_render_kernel stages them
-    __shared__ float4 top_lds[TOPN > 0 ? 8 * TOPN : 1];
-    if (threadIdx.x < 32) {
-        const int k = threadIdx.x & 15;
-        const int src = k < 4 ? k : k < 9 ? k + 1 : k == 9 ? 10 : k == 10 ? 4 : -1;
-        sph_lds[threadIdx.x] = src < 0 ? 0.f : P.sph2[threadIdx.x >> 4][src];
-    }
-    if (TOPN > 0 && threadIdx.x < 8u * TOPN) {
-        const uint32_t m = threadIdx.x >> 3, k = threadIdx.x & 7;
-        int n = 0;
-        if (m > 0) {
-            const float4 rm = node_row(P.nodes, node_base(0), 6);
-            n = (int)(m - 1) < (__float_as_int(rm.y) & 0xff) ? __float_as_int(rm.x) + (int)(m - 1) : -1;
-        }
-        if (n >= 0 && n < P.n_nodes) top_lds[threadIdx.x] = node_row(P.nodes, node_base(n), k);
-    }
-    __syncthreads();
-    const int lane = threadIdx.x;
-    // the overflow stack region is indexed by grid lane, not by ray: (stack_cap - stack_lds) x grid lanes entries
-    const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane, n_gl = (size_t)gridDim.x * 64;
-    const float INF = __builtin_inff();
-    const uint64_t below = (1ull << lane) - 1ull;
-    const uint32_t NONE = 0xffffffffu;
-    TraceCounts cnt{};
-    uint64_t n_rays = 0, n_active = 0;       // COUNT only
-    // lane state: the ray, its traversal and its index; nothing else lives across the loop
-    V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f), inv = v3(0.f, 0.f, 0.f);
-    float tmax = INF, closest = INF;
-    uint32_t rows = 0, idx = NONE;
-    int node = -1, sp = 0, hit = -1;
-    // wave-uniform: first index of the reserved block, indices handed out.  Variant 7 reserves 64 pixels per
-    // atomicAdd; a ray is ~4 node steps where a pixel is whole paths, and at 64 rays per atomicAdd the one counter's
-    // address bounds the kernel (about 12 ns per atomic: 0.7 ms for 3.7 M rays whatever the grid, profiles/ray_query),
-    // so the host sizes the block with the query (trace_enqueue)
-    uint32_t pool = 0, used = T.block;
-    bool exhausted = false;
-    L.owner_at[lane] = 0;
-    for (;;) {
-        const bool idle = idx != NONE && node < 0;             // holds a finished ray
-        const int n_idle = __popcll(wave_ballot(idle));
-        const int n_have = __popcll(wave_ballot(idx != NONE));
-        if (n_idle >= T.refill_threshold || n_idle == n_have) {
-            if (idle) {
-                // the per-ray spheres against the traversal's closest hit, as finish_ray tests them (an occlusion
-                // lane that retired on a hit within tmax is occluded whatever they add)
-                if (!(ANY && hit >= 0 && closest <= tmax)) {
-                    if (COUNT) cnt.spheres += P.n_ray_spheres;
-                    ray_spheres<true>(P.prims, P.sphere_chain, P.n_chain, P.sphere_first, P.n_ray_spheres, o, d,
-                                      sphere_inv(d, inv), closest, hit, sph_lds);
-                }
-                trace_store(T, idx, o, d, tmax, closest, hit);
-                idx = NONE;
-            }
-            while (!exhausted) {                 // lanes without a ray take the next indices
-                const uint64_t need = wave_ballot(idx == NONE);
-                if (need == 0) break;
-                if (used >= T.block) {
-                    uint32_t b = 0;
-                    if (lane == 0) b = atomicAdd(T.next, T.block);
-                    pool = __builtin_amdgcn_readfirstlane(b);
-                    used = 0;
-                    if (pool >= T.n) { exhausted = true; break; }
-                }
-                const uint32_t take = min((uint32_t)__popcll(need), T.block - used);
-                const uint32_t rank = (uint32_t)__popcll(need & below);
-                if (idx == NONE && rank < take && pool + used + rank < T.n) {
-                    idx = pool + used + rank;
-                    const float4 r0 = T.rays[2 * (size_t)idx], r1 = T.rays[2 * (size_t)idx + 1];
-                    o = v3(r0.x, r0.y, r0.z);
-                    tmax = r0.w;
-                    d = v3(r1.x, r1.y, r1.z);
-                    if (COUNT) ++n_rays;
-                    node = 0;
-                    sp = 0;
-                    closest = INF;
-                    hit = -1;
-                    inv = box_inv(recip3_exact(d));   // the traversal's 1/d (wide_boxes)
-                    rows = ray_rows(inv);
-                    L.ray0[lane] = make_float4(o.x, o.y, o.z, d.x);
-                    if (TOPN > 0) top_steps<COUNT, TOPN>(P, top_lds, o, inv, rows, node, sp, cnt, stk, gl, n_gl);
-                }
-                used += take;
-            }
-            if (!wave_ballot(idx != NONE)) break;     // the counter is past the end and every lane is done
-        }
-        if (COUNT) n_active += node >= 0;
-        traverse_step4<COUNT>(P, o, d, inv, rows, node, sp, closest, hit, cnt, L, stk, lane, gl, n_gl);
-        // occlusion: the closest t is no larger than any accepted t, so the first accepted hit within tmax decides;
-        // the lane drops its stack and waits for the pass
-        if (ANY && node >= 0 && hit >= 0 && closest <= tmax) {
-            node = -1;
-            sp = 0;
-        }
-    }
-    if (COUNT) trace_add_stats(T, lane, n_rays, cnt, n_active);
+#define TRACE_BODY_N T.n
+#define TRACE_BODY_BLOCK T.block
+#include "crt_trace_stream_body.inc"
+#undef TRACE_BODY_N
+#undef TRACE_BODY_BLOCK
+}
+
+// The indirect forms: the number of rays is a device word the kernel reads when it runs, clamped to the
+// capacity the host sized the launch by (T.n).  No row at or beyond min(*d_n, T.n) is read or written.
+struct TraceIndirectParams {
+    TraceParams T;                         // n: the capacity; block is not used
+    const uint32_t* __restrict__ d_n;      // the ray count, on the device
+};
+
+template <bool ANY, bool COUNT>
+__global__ __launch_bounds__(64, 6) void crt_trace_indirect_kernel(TraceIndirectParams I) {
+    const TraceParams& T = I.T;
+    const uint32_t n = min(*I.d_n, T.n);
+    // trace_enqueue's rule for the indices per reservation, on the count read here and this kernel's own grid
+    const uint32_t block = 64u * min(8u, max(1u, n / (64u * gridDim.x)));
+#define TRACE_BODY_N n
+#define TRACE_BODY_BLOCK block
+#include "crt_trace_stream_body.inc"
+#undef TRACE_BODY_N
+#undef TRACE_BODY_BLOCK
 }
 
 template <bool COUNT>
 __global__ __launch_bounds__(256) void crt_trace_lane_kernel(TraceParams T) {
-    const RenderParams& P = T.P;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    TraceCounts cnt{};
-    if (i < T.n) {
-        const float4 r0 = T.rays[2 * (size_t)i], r1 = T.rays[2 * (size_t)i + 1];
-        const V3 o = v3(r0.x, r0.y, r0.z), d = v3(r1.x, r1.y, r1.z);
-        float t;
-        const int hit = T.width == 4 ? trace4(P.nodes, P.prims, P.sphere_chain, P.n_chain, P.sphere_first,
-                                              P.n_ray_spheres, o, d, t)
-                                     : trace<COUNT>(P.nodes, P.prims, P.n_nodes,
-                                                    layout_base(d, P.n_layouts, P.n_nodes), o, d, t, cnt);
-        trace_store(T, i, o, d, r0.w, t, hit);
-    }
-    if (COUNT) trace_add_stats(T, threadIdx.x & 63, i < T.n ? 1u : 0u, cnt, 0);
+#define TRACE_BODY_N T.n
+#include "crt_trace_lane_body.inc"
+#undef TRACE_BODY_N
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(256) void crt_trace_lane_indirect_kernel(TraceIndirectParams I) {
+    const TraceParams& T = I.T;
+    const uint32_t n = min(*I.d_n, T.n);
+#define TRACE_BODY_N n
+#include "crt_trace_lane_body.inc"
+#undef TRACE_BODY_N
 }
 
 // ------------------------------------------------------------------ host side
@@ -247,9 +174,12 @@ int trace_scratch(crt_scene* S, TraceScratch** out) {
     return CRT_OK;
 }
 
-// One query over device pointers, enqueued on st.
+// One query over device pointers, enqueued on st.  d_n null: rays [0, n).  Otherwise the indirect query: n is the
+// capacity (at most one launch's rays) that the grid, the persistent grid and automatic mode's choice are sized by, and
+// the kernel traces rays [0, min(*d_n, n)).  d_err: the word the kernels OR their error flags into; null: the handle's
+// own, which every query clears.
 int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trace_options* opts, crt_hit* d_hits,
-                  uint8_t* d_occ, unsigned flags, hipStream_t st) {
+                  uint8_t* d_occ, unsigned flags, hipStream_t st, const uint32_t* d_n = nullptr, unsigned* d_err = nullptr) {
     crt_trace_options o{};
     if (opts) o = *opts;
     if (o.mode < 0 || o.mode > 2) return set_error(CRT_ERR_INVALID_ARGUMENT, "trace mode must be 0, 1 or 2");
@@ -282,7 +212,7 @@ int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trac
     RenderParams& P = T.P;
     P.nodes = S->d_nodes; P.prims = S->d_prims; P.mats = S->d_mats; P.shade = S->d_shade;
     P.n_nodes = S->n_nodes; P.n_mats = S->n_mats; P.n_prims = S->n_prims; P.n_layouts = S->layouts;
-    P.err = reinterpret_cast<unsigned*>(X->d_stats + TRACE_ERR_WORD);
+    P.err = d_err ? d_err : reinterpret_cast<unsigned*>(X->d_stats + TRACE_ERR_WORD);
     P.top_levels = CRT_TOP_LEVELS;
     P.stack_cap = S->stack_cap;
     P.sphere_first = S->sphere_first;
@@ -333,7 +263,16 @@ int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trac
             T.block = 64u * (uint32_t)std::min<int64_t>(8, std::max<int64_t>(1, m / (64 * std::max<int64_t>(waves, 1))));
             HIP_TRY(hipMemsetAsync(X->d_next, 0, 4, st));
             if (at == 0) HIP_TRY(hipEventRecord(X->ev0, st));   // kernel_ms: from the first kernel, after the counter's reset
-            if (any) {
+            if (d_n) {                           // T.block stays unused: the kernel derives it from the count it reads
+                const TraceIndirectParams I{T, d_n};
+                if (any) {
+                    if (cnt) hipLaunchKernelGGL((crt_trace_indirect_kernel<true, true>), grid, block, 0, st, I);
+                    else hipLaunchKernelGGL((crt_trace_indirect_kernel<true, false>), grid, block, 0, st, I);
+                } else {
+                    if (cnt) hipLaunchKernelGGL((crt_trace_indirect_kernel<false, true>), grid, block, 0, st, I);
+                    else hipLaunchKernelGGL((crt_trace_indirect_kernel<false, false>), grid, block, 0, st, I);
+                }
+            } else if (any) {
                 if (cnt) hipLaunchKernelGGL((crt_trace_kernel<true, true>), grid, block, 0, st, T);
                 else hipLaunchKernelGGL((crt_trace_kernel<true, false>), grid, block, 0, st, T);
             } else {
@@ -343,7 +282,11 @@ int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trac
         } else {
             const dim3 grid((unsigned)((m + 255) / 256)), block(256);
             if (at == 0) HIP_TRY(hipEventRecord(X->ev0, st));
-            if (cnt) hipLaunchKernelGGL((crt_trace_lane_kernel<true>), grid, block, 0, st, T);
+            if (d_n) {
+                const TraceIndirectParams I{T, d_n};
+                if (cnt) hipLaunchKernelGGL((crt_trace_lane_indirect_kernel<true>), grid, block, 0, st, I);
+                else hipLaunchKernelGGL((crt_trace_lane_indirect_kernel<false>), grid, block, 0, st, I);
+            } else if (cnt) hipLaunchKernelGGL((crt_trace_lane_kernel<true>), grid, block, 0, st, T);
             else hipLaunchKernelGGL((crt_trace_lane_kernel<false>), grid, block, 0, st, T);
         }
         HIP_TRY(hipGetLastError());
@@ -445,6 +388,20 @@ int crt_scene_trace_device(const crt_scene* S, const crt_ray* d_rays, int64_t n,
     if (n == 0) return CRT_OK;
     if (!d_rays || (!d_hits && !d_occluded)) return set_error(CRT_ERR_INVALID_ARGUMENT, "null rays, or neither hits nor occluded");
     return trace_enqueue(const_cast<crt_scene*>(S), d_rays, n, opts, d_hits, d_occluded, flags, (hipStream_t)stream);
+}
+
+int crt_scene_trace_indirect_device(const crt_scene* S, const crt_ray* d_rays, const uint32_t* d_n, int64_t capacity,
+                                    const crt_trace_options* opts, crt_hit* d_hits, uint8_t* d_occluded, unsigned flags,
+                                    void* stream) {
+    if (!S) return set_error(CRT_ERR_INVALID_ARGUMENT, "indirect trace: null scene");
+    if (capacity < 0 || capacity > TRACE_LAUNCH_RAYS)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "indirect trace: capacity must be in [0, 2^30] (one launch serves one query)");
+    if (!d_n || ((uintptr_t)d_n & 3u))
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "indirect trace: the count must be a non-null, 4-byte aligned device word");
+    if (capacity == 0) return CRT_OK;
+    if (!d_rays || (!d_hits && !d_occluded))
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "indirect trace: null rays, or neither hits nor occluded");
+    return trace_enqueue(const_cast<crt_scene*>(S), d_rays, capacity, opts, d_hits, d_occluded, flags, (hipStream_t)stream, d_n);
 }
 
 int crt_scene_trace_last_stats(const crt_scene* S, crt_trace_stats* out) {

@@ -2,7 +2,7 @@
 Renderer.render on the same frame, and where their time goes.
 
     python tools/path_bench.py [--width 1280 --height 720] [--spp 16] [--bounces 20] [--reps 7] [--warmup 1]
-                               [--mode 0] [--rows frame,phases,step,queue,advance]
+                               [--mode 0] [--rows frame,phases,step,queue,advance,queued]
 
 No pass / fail: JSON lines.  Scene: cornell_bunny, rebuilt 4-wide tree, default options, bench camera, seed 41.
 
@@ -24,6 +24,10 @@ No pass / fail: JSON lines.  Scene: cornell_bunny, rebuilt 4-wide tree, default 
           loaded build.  The reservation sweep is this row from builds with other constants:
               tools/build_profile_lib.sh adv64 -DCRT_ADVANCE_ENTRIES=64        (also 512, 1024; the default is 256)
               CRT_HIP_LIB=raytracer-cuda_amd/lib_exp/adv64/libcrt_hip.so python tools/path_bench.py --rows advance
+  queued   `reps` rounds, interleaved in one process, of the queue row's four drivers and
+          Renderer.render_wavefront(sync_every=K) for K = 1, 2, 4, 8, 16, 32 and 0 (the library's default): medians, the
+          run-to-run spread of the existing library loop (the yardstick), each K's ratio to it, equal bits, rays and
+          iterations.
   step    the step kernel alone over that frame's iterations: paths per second, and bytes per second against the bytes
           an entry must move -- ray 32 B read, hit 32 B read, path 32 B read and written, RNG 24 B read and written,
           then the ray's 32 B written by a path that goes on or the sum's 12 B read and written by one that ends.
@@ -50,7 +54,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mode", type=int, default=0, help="Scene.trace mode of the driver's queries (0 = automatic)")
-    ap.add_argument("--rows", default="frame,phases,step,queue,advance", help="the rows to measure, comma-separated")
+    ap.add_argument("--rows", default="frame,phases,step,queue,advance,queued", help="the rows to measure, comma-separated")
     a = ap.parse_args()
     want = set(a.rows.split(","))
 
@@ -93,8 +97,16 @@ def main():
         res = r.render_wavefront(sc, a.spp, a.bounces, trace_options=opts)
         return res["ms"], res
 
+    def queued(sync_every):
+        r.init_rand(41)
+        r.synchronize()
+        res = r.render_wavefront(sc, a.spp, a.bounces, trace_options=opts, sync_every=sync_every)
+        return res["ms"], res
+
     if want & {"queue", "advance"}:
         queue_rows(a, want, case, direct, wavefront, library, state)
+    if "queued" in want:
+        queued_rows(a, case, direct, wavefront, library, queued, state)
     if not want & {"frame", "phases", "step"}:
         return
     for _ in range(a.warmup):
@@ -200,6 +212,39 @@ def queue_rows(a, want, case, direct, wavefront, library, state):
                               gpaths_per_s=round(n / med(adv_ms) / 1e6, 3), bytes_per_entry=round(moved / n, 1),
                               gbytes_per_s=round(moved / med(adv_ms) / 1e6, 1), large_iterations=len(big),
                               large_gpaths_per_s=round(n_big / ms_big / 1e6, 3) if big else None)), flush=True)
+
+
+QUEUED_KS = (1, 2, 4, 8, 16, 32, 0)          # 0: the library's default
+
+
+def queued_rows(a, case, direct, wavefront, library, queued, state):
+    med = statistics.median
+    runs = [("torch", wavefront), ("device", lambda: wavefront(compact="device")), ("library", library)]
+    runs += [(f"queued_{k}", lambda k=k: queued(k)) for k in QUEUED_KS]
+    for _ in range(a.warmup):
+        direct()
+        for _, run in runs:
+            run()
+    ms = {"render": [], **{k: [] for k, _ in runs}}
+    states, res = {}, {}
+    for _ in range(a.reps):
+        ms["render"].append(direct())
+        states["render"] = state()
+        for k, run in runs:
+            t, res[k] = run()
+            ms[k].append(t)
+            states[k] = state()
+    equal = all(np.array_equal(states[k][0], states["render"][0]) and np.array_equal(states[k][1], states["render"][1])
+                for k, _ in runs)
+    equal = equal and len({(res[k]["rays"], res[k]["iterations"]) for k in res}) == 1
+    lib = ms["library"]
+    print(json.dumps(dict(case, row="queued", reps=a.reps, **{k + "_ms_median": round(med(v), 3) for k, v in ms.items()},
+                          **{k + "_ms_min": round(min(v), 3) for k, v in ms.items()},
+                          library_ms_max=round(max(lib), 3), library_ms_spread=round(max(lib) - min(lib), 3),
+                          library_ms_all=[round(v, 3) for v in lib],
+                          **{f"queued_{k}_over_library": round(med(ms[f"queued_{k}"]) / med(lib), 3) for k in QUEUED_KS},
+                          rays=res["library"]["rays"], iterations=res["library"]["iterations"], equal_bits=bool(equal))),
+          flush=True)
 
 
 if __name__ == "__main__":
