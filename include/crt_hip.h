@@ -579,6 +579,30 @@ int crt_selftest_geometry(int kind, const float* in, int n, const crt_camera_des
 /* XORWOW device self-test: init(seed, subseq[i]) then n_draw uniforms per entry. */
 int crt_selftest_rng(unsigned long long seed, const unsigned long long* subseq, int n, int n_draw,
                      uint32_t* state_out /* n*6 */, float* uniforms_out /* n*n_draw */);
+/* Self-tests of the tile and pixel schedules (variants 7, 8, 10): the stages between a cost probe and the main kernel on
+ * caller-supplied costs, run by the host functions the renders call, in the renderer's own buffers (so their sizes, the
+ * scratch reuse and the guards are the renders').  No camera or scene is needed.  Synchronous; the results stay in the
+ * renderer's buffers and are read with crt_selftest_schedule_buffer.  The order buffer is filled with 0xffffffff
+ * first, so entries a stage did not write still hold that.  These entries joined ABI version 3 after its first release.
+ * Variant 8 / 10's tile schedule: pix_cost = width * height costs as a probe of `stride` (1, 2, 4) leaves them (only
+ * pixels with x, y % stride == 0 are read), key_mode 0..2 as crt_renderer_set_schedule's tile key, (shard, shards) as
+ * crt_renderer_set_pixel_shard, xcd_regions as crt_renderer_set_xcd_regions; the renderer's own settings are kept.
+ * Afterwards buffer 1 holds the tile keys as sorted (after the neighbour and shard steps) and buffer 0's first
+ * tiles_x * tiles_y entries the tile order.  stats_out (optional): the two words of the probe statistics, the largest
+ * tile work and the total work. */
+int crt_selftest_tile_schedule(crt_renderer* r, const uint32_t* pix_cost, int stride, int key_mode, int shard, int shards,
+                               int xcd_regions, unsigned long long* stats_out);
+/* Variant 7's orders into buffer 0.  kind 0: the probe order, the pixels most expensive first by in = width * height
+ * per-pixel costs (width * height entries).  kind 1: the temporal order from in = a rays-per-pixel map (uploaded as the
+ * last frame's; the renderer's next frame starts in row order again): buffer 4 = the tiles most expensive first, buffer 1
+ * their keys, buffer 0 = tiles * 64 pixel slots.  kind 2: the row-order slots.  kind 3: pixel sharding without the
+ * probe, entry k = the k-th tile of (shard, shards).  in is ignored for kinds 2 and 3, the shard for kinds 0..2. */
+int crt_selftest_pixel_order(crt_renderer* r, int kind, const uint32_t* in, int shard, int shards);
+/* Reads a schedule buffer of the renderer, whole: which 0 = the order (max(width * height, tiles * 64) words), 1 = the
+ * tile keys (tiles), 2 = the per-pixel probe costs (width * height; the sort scratch after a tile schedule), 3 = the
+ * rays per pixel of the last temporal variant-7 frame (width * height), 4 = the temporal tile order (tiles).  *n = the
+ * buffer's words, 0 while it is not allocated; min(*n, capacity) words are copied to out.  Waits for the device. */
+int crt_selftest_schedule_buffer(crt_renderer* r, int which, uint32_t* out, int64_t capacity, int64_t* n);
 
 #ifdef __cplusplus
 }

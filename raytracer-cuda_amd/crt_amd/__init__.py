@@ -569,6 +569,47 @@ class Renderer:
         """Variant 8: XCD groups render equal-cost screen strips (crt_renderer_set_xcd_regions)."""
         check(_lib.hip().crt_renderer_set_xcd_regions(self.h, int(bool(on))), "set_xcd_regions")
 
+    # ---- self-tests of the schedules (crt_hip.h crt_selftest_tile_schedule ff.): stages on caller-supplied costs
+    SCHEDULE_BUFFERS = {"order": 0, "tile_key": 1, "pix_cost": 2, "pix_rays": 3, "tile_order": 4}
+
+    def schedule_buffer(self, which: str) -> np.ndarray:
+        """A schedule buffer of this renderer, whole, as uint32 (crt_selftest_schedule_buffer): "order", "tile_key",
+        "pix_cost" (the probe's per-pixel costs), "pix_rays" (the last temporal frame's rays per pixel), "tile_order";
+        empty while the buffer is not allocated."""
+        fn = _lib.require("crt_selftest_schedule_buffer")
+        n = C.c_int64(0)
+        check(fn(self.h, self.SCHEDULE_BUFFERS[which], None, 0, C.byref(n)), "selftest_schedule_buffer")
+        out = np.zeros(n.value, np.uint32)
+        check(fn(self.h, self.SCHEDULE_BUFFERS[which], _p(out), n.value, C.byref(n)), "selftest_schedule_buffer")
+        return out
+
+    def selftest_tile_schedule(self, pix_cost, stride=1, key_mode=2, shard=0, shards=1, xcd_regions=False, stats=False):
+        """Variant 8 / 10's tile schedule on per-pixel costs (crt_selftest_tile_schedule): returns (keys as sorted
+        [tiles], order [tiles], the rest of the order buffer, (largest tile work, total work) or None)."""
+        c = np.ascontiguousarray(pix_cost, np.uint32).reshape(-1)
+        if c.size != self.width * self.height:
+            raise ValueError("pix_cost must hold width * height costs")
+        st = (C.c_ulonglong * 2)()
+        check(_lib.require("crt_selftest_tile_schedule")(self.h, _p(c), int(stride), int(key_mode), int(shard), int(shards),
+                                                         int(bool(xcd_regions)), st if stats else None),
+              "selftest_tile_schedule")
+        keys, order = self.schedule_buffer("tile_key"), self.schedule_buffer("order")
+        return keys, order[:keys.size], order[keys.size:], ((int(st[0]), int(st[1])) if stats else None)
+
+    def selftest_pixel_order(self, kind: str, costs=None, shard=0, shards=1) -> np.ndarray:
+        """Variant 7's orders (crt_selftest_pixel_order): kind "probe" (costs per pixel), "temporal" (costs = a
+        rays-per-pixel map), "rows", "shard".  Returns the whole order buffer; schedule_buffer("tile_order") and
+        ("tile_key") hold the temporal order's tiles and keys."""
+        k = {"probe": 0, "temporal": 1, "rows": 2, "shard": 3}[kind]
+        c = None
+        if k <= 1:
+            c = np.ascontiguousarray(costs, np.uint32).reshape(-1)
+            if c.size != self.width * self.height:
+                raise ValueError("costs must hold width * height entries")
+        check(_lib.require("crt_selftest_pixel_order")(self.h, k, None if c is None else _p(c), int(shard), int(shards)),
+              "selftest_pixel_order")
+        return self.schedule_buffer("order")
+
     def set_leaf_carry(self, lanes: int, max_pairs: int):
         """Variant 8's leaf-pair carry: measured and removed in round 5; the library reports
         CRT_ERR_UNSUPPORTED, so this raises CrtError (profiles/r04c/leaf_carry.patch restores the kernels)."""

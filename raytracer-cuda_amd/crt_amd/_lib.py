@@ -150,14 +150,17 @@ HIP_SYMBOLS = [
     "crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
     "crt_scene_path_advance_device", "crt_path_advance_entries", "crt_renderer_render_wavefront",
     "crt_scene_trace_indirect_device", "crt_scene_path_advance_indirect_device", "crt_renderer_render_wavefront_queued",
+    "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer",
 ]
-# Entries that joined ABI version 3 after its first release (the path steps, the path queues, then the indirect calls): bound when the loaded
+# Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, then
+# the schedule self-tests): bound when the loaded
 # library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
 # require() otherwise.
 OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
                     "crt_scene_path_advance_device", "crt_path_advance_entries", "crt_renderer_render_wavefront",
                     "crt_scene_trace_indirect_device", "crt_scene_path_advance_indirect_device",
-                    "crt_renderer_render_wavefront_queued")
+                    "crt_renderer_render_wavefront_queued",
+                    "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer")
 
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
@@ -254,6 +257,9 @@ def hip():
             "crt_scene_trace_indirect_device": ([P, P, P, C.c_int64, P, P, P, C.c_uint, P], i32),
             "crt_scene_path_advance_indirect_device": ([P, P, P, P, P, P, C.c_int64, i32, P, P, P, P, P, P, P, P], i32),
             "crt_renderer_render_wavefront_queued": ([P, P, i32, i32, C.c_uint, P, i32, P, P], i32),
+            "crt_selftest_tile_schedule": ([P, P, i32, i32, i32, i32, i32, P], i32),
+            "crt_selftest_pixel_order": ([P, i32, P, i32, i32], i32),
+            "crt_selftest_schedule_buffer": ([P, i32, P, C.c_int64, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):

@@ -3906,6 +3906,12 @@ static int order_tiles_by_probe(crt_renderer* R, hipStream_t st, int stride, boo
     return CRT_OK;
 }
 
+// Pixel sharding without the probe: d_order[k] = this shard's k-th tile in row order.
+static void shard_tiles_in_row_order(crt_renderer* R, hipStream_t st, int n_tiles, int shard, int shards) {
+    hipLaunchKernelGGL(crt_shard_tiles_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_order, n_tiles,
+                       shard, shards);
+}
+
 static RenderParams render_params(const crt_renderer* R, const crt_scene* S, int spp, int max_bounces, unsigned flags) {
     RenderParams P{};   // no order, queue, probe costs, overflow stack or ray counts: the schedules set what they use
     P.nodes = S->d_nodes; P.prims = S->d_prims; P.mats = S->d_mats; P.shade = S->d_shade;
@@ -4051,8 +4057,7 @@ static int render_tiles(crt_renderer* R, const crt_scene* S, hipStream_t st, Ren
             R->last_schedule[3] = (float)(mine / std::max(1, n_tiles / shards));
         }
     } else if (shards > 1) {   // pixel shard without the probe: this shard's tiles in row order
-        hipLaunchKernelGGL(crt_shard_tiles_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_order, n_tiles,
-                           shard, shards);
+        shard_tiles_in_row_order(R, st, n_tiles, shard, shards);
         P.order = R->d_order;
     }
     if (P.crit_tiles > 0) P.crit_tiles = (P.crit_tiles + shards - 1) / shards;
@@ -4061,12 +4066,45 @@ static int render_tiles(crt_renderer* R, const crt_scene* S, hipStream_t st, Ren
     return launch_render(R, RENDER_ROWS[render_row(variant, cnt, occ)], cnt, tgrid, dim3(64), st, P);
 }
 
+// Variant 7 without the probe: d_order = the n_tiles * 64 pixel slots of the 8x8 tiles, the tiles most expensive first
+// by d_pix_rays (temporal order, once a frame has written it) or in row order.  Allocates the temporal buffers on
+// first use (one stream synchronisation).
+static int order_tile_slots(crt_renderer* R, hipStream_t st) {
+    const size_t n_pix = (size_t)R->width * R->height;
+    const int tiles_x = (R->width + 7) / 8, n_tiles = tiles_x * ((R->height + 7) / 8);
+    const size_t n_tile_slots = (size_t)n_tiles * 64;
+    if (R->temporal && !R->d_pix_rays) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMalloc((void**)&R->d_pix_rays, n_pix * 4));
+        HIP_TRY(hipMalloc((void**)&R->d_tile_order, (size_t)n_tiles * 4));
+        if (!R->d_tile_key) HIP_TRY(hipMalloc((void**)&R->d_tile_key, (size_t)n_tiles * 4));
+        R->pix_rays_valid = false;
+    }
+    const dim3 sgrid((unsigned)((n_tile_slots + 255) / 256));
+    if (R->temporal && R->pix_rays_valid) {
+        // the interactive loop's frames repeat the last frame's cost map: its rays per pixel -> tile keys (the
+        // slowest pixel, raised to 3/4 of the neighbours', as variant 8's probe keys) -> tiles most expensive
+        // first, so the long paths start early and the launch does not end with them (profiles/r04i: a 1-spp
+        // frame in row order spends its last 31 % draining)
+        hipLaunchKernelGGL(crt_tile_cost_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_pix_rays,
+                           R->width, R->height, tiles_x, n_tiles, R->d_tile_order, 0, 1, nullptr);
+        hipLaunchKernelGGL(crt_tile_neighbour_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st,
+                           R->d_tile_order, tiles_x, n_tiles, R->d_tile_key);
+        if (int rc = sort_descending(R, st, R->d_tile_key, n_tiles, R->d_tile_order)) return rc;
+        hipLaunchKernelGGL(crt_expand_tile_order_kernel, sgrid, dim3(256), 0, st, R->d_tile_order, R->d_order,
+                           R->width, R->height, (int)n_tile_slots);
+    } else {
+        hipLaunchKernelGGL(crt_order_tiles_kernel, sgrid, dim3(256), 0, st, R->d_order, R->width, R->height,
+                           (int)n_tile_slots);
+    }
+    return CRT_OK;
+}
+
 // Variant 7: persistent workgroups whose lanes refill from a queue of pixel slots, ordered by a per-pixel cost probe,
 // by the previous frame's rays per pixel (temporal), or in 8x8-tile order.
 static int render_pixel_queue(crt_renderer* R, hipStream_t st, RenderParams& P, bool cnt, int spp, int occ) {
     const size_t n_pix = (size_t)R->width * R->height;
-    const int tiles_x = (R->width + 7) / 8, n_tiles = tiles_x * ((R->height + 7) / 8);
-    const size_t n_tile_slots = (size_t)n_tiles * 64;
+    const size_t n_tile_slots = (size_t)((R->width + 7) / 8) * ((R->height + 7) / 8) * 64;
     if (probe_spp_for(R, spp) > 0) {
         // cost probe: variant 4 at probe_spp samples over the same RNG state, read-only: rays per pixel
         RenderParams Q = P;
@@ -4079,30 +4117,7 @@ static int render_pixel_queue(crt_renderer* R, hipStream_t st, RenderParams& P, 
         if (int rc = sort_descending(R, st, R->d_tile_cost, (int)n_pix, R->d_order)) return rc;
         P.n_slots = (int)n_pix;
     } else {
-        if (R->temporal && !R->d_pix_rays) {
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMalloc((void**)&R->d_pix_rays, n_pix * 4));
-            HIP_TRY(hipMalloc((void**)&R->d_tile_order, (size_t)n_tiles * 4));
-            if (!R->d_tile_key) HIP_TRY(hipMalloc((void**)&R->d_tile_key, (size_t)n_tiles * 4));
-            R->pix_rays_valid = false;
-        }
-        const dim3 sgrid((unsigned)((n_tile_slots + 255) / 256));
-        if (R->temporal && R->pix_rays_valid) {
-            // the interactive loop's frames repeat the last frame's cost map: its rays per pixel -> tile keys (the
-            // slowest pixel, raised to 3/4 of the neighbours', as variant 8's probe keys) -> tiles most expensive
-            // first, so the long paths start early and the launch does not end with them (profiles/r04i: a 1-spp
-            // frame in row order spends its last 31 % draining)
-            hipLaunchKernelGGL(crt_tile_cost_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_pix_rays,
-                               R->width, R->height, tiles_x, n_tiles, R->d_tile_order, 0, 1, nullptr);
-            hipLaunchKernelGGL(crt_tile_neighbour_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st,
-                               R->d_tile_order, tiles_x, n_tiles, R->d_tile_key);
-            if (int rc = sort_descending(R, st, R->d_tile_key, n_tiles, R->d_tile_order)) return rc;
-            hipLaunchKernelGGL(crt_expand_tile_order_kernel, sgrid, dim3(256), 0, st, R->d_tile_order, R->d_order,
-                               R->width, R->height, (int)n_tile_slots);
-        } else {
-            hipLaunchKernelGGL(crt_order_tiles_kernel, sgrid, dim3(256), 0, st, R->d_order, R->width, R->height,
-                               (int)n_tile_slots);
-        }
+        if (int rc = order_tile_slots(R, st)) return rc;
         P.n_slots = (int)n_tile_slots;
         if (R->temporal) {
             P.pix_rays = R->d_pix_rays;
@@ -4606,6 +4621,97 @@ int crt_selftest_rng(unsigned long long seed, const unsigned long long* subseq, 
     HIP_TRY(hipMemcpy(state_out, dst, (size_t)n * 24, hipMemcpyDeviceToHost));
     if (n_draw) HIP_TRY(hipMemcpy(uniforms_out, du, (size_t)n * n_draw * 4, hipMemcpyDeviceToHost));
     (void)hipFree(dseq); (void)hipFree(dst); (void)hipFree(du);
+    return CRT_OK;
+}
+
+// The schedule stages on caller-supplied costs: the renderer's own buffers and the host functions the renders call
+// (order_tiles_by_probe, sort_descending, order_tile_slots, shard_tiles_in_row_order), on the null stream.
+int crt_selftest_tile_schedule(crt_renderer* R, const uint32_t* pix_cost, int stride, int key_mode, int shard, int shards,
+                               int xcd_regions, unsigned long long* stats_out) {
+    if (!R || !pix_cost) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
+    if ((stride != 1 && stride != 2 && stride != 4) || key_mode < 0 || key_mode > 2 || shards < 1 || shard < 0 ||
+        shard >= shards)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad stride, key mode or shard");
+    HIP_TRY(hipSetDevice(R->device));
+    const size_t n_pix = (size_t)R->width * R->height;
+    const int n_tiles = ((R->width + 7) / 8) * ((R->height + 7) / 8);
+    if (int rc = ensure_order_buffers(R, 0, n_pix, n_tiles, true)) return rc;
+    HIP_TRY(hipMemset(R->d_order, 0xff, std::max(n_pix, (size_t)n_tiles * 64) * 4));
+    HIP_TRY(hipMemcpy(R->d_tile_cost, pix_cost, n_pix * 4, hipMemcpyHostToDevice));
+    const int mode0 = R->tile_key_mode, xcd0 = R->xcd_regions;
+    R->tile_key_mode = key_mode;
+    R->xcd_regions = xcd_regions ? 1 : 0;
+    const int rc = order_tiles_by_probe(R, 0, stride, stats_out != nullptr, shard, shards);
+    R->tile_key_mode = mode0;
+    R->xcd_regions = xcd0;
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));
+    if (stats_out) { stats_out[0] = R->h_probe_stats[0]; stats_out[1] = R->h_probe_stats[1]; }
+    return CRT_OK;
+}
+
+int crt_selftest_pixel_order(crt_renderer* R, int kind, const uint32_t* in, int shard, int shards) {
+    if (!R || kind < 0 || kind > 3 || (kind <= 1 && !in)) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (kind == 3 && (shards < 1 || shard < 0 || shard >= shards))
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad shard");
+    HIP_TRY(hipSetDevice(R->device));
+    const size_t n_pix = (size_t)R->width * R->height;
+    const int n_tiles = ((R->width + 7) / 8) * ((R->height + 7) / 8);
+    if (int rc = ensure_order_buffers(R, 0, n_pix, n_tiles, kind == 3)) return rc;
+    HIP_TRY(hipMemset(R->d_order, 0xff, std::max(n_pix, (size_t)n_tiles * 64) * 4));
+    int rc = CRT_OK;
+    if (kind == 0) {
+        HIP_TRY(hipMemcpy(R->d_tile_cost, in, n_pix * 4, hipMemcpyHostToDevice));
+        rc = sort_descending(R, 0, R->d_tile_cost, (int)n_pix, R->d_order);
+    } else if (kind == 3) {
+        shard_tiles_in_row_order(R, 0, n_tiles, shard, shards);
+    } else {
+        const int temporal0 = R->temporal;
+        const bool valid0 = R->pix_rays_valid;
+        R->temporal = kind == 1;
+        if (kind == 1) {
+            if (!R->d_pix_rays) rc = order_tile_slots(R, 0);   // allocates the temporal buffers (row order this once)
+            if (!rc) {
+                hipError_t e = hipMemcpy(R->d_pix_rays, in, n_pix * 4, hipMemcpyHostToDevice);
+                if (e == hipSuccess) e = hipMemset(R->d_order, 0xff, (size_t)n_tiles * 64 * 4);
+                if (e != hipSuccess) rc = set_error(CRT_ERR_HIP, hipGetErrorString(e));
+            }
+            R->pix_rays_valid = true;
+        }
+        if (!rc) rc = order_tile_slots(R, 0);
+        R->temporal = temporal0;
+        R->pix_rays_valid = kind == 1 ? false : valid0;   // kind 1 replaced the last frame's map
+    }
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));
+    return CRT_OK;
+}
+
+int crt_selftest_schedule_buffer(crt_renderer* R, int which, uint32_t* out, int64_t capacity, int64_t* n_out) {
+    if (!R || !n_out || capacity < 0 || (capacity > 0 && !out))
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
+    const size_t n_pix = (size_t)R->width * R->height;
+    const size_t n_tiles = (size_t)((R->width + 7) / 8) * ((R->height + 7) / 8);
+    const uint32_t* src;
+    size_t n;
+    switch (which) {
+        case 0: src = R->d_order; n = std::max(n_pix, n_tiles * 64); break;
+        case 1: src = R->d_tile_key; n = n_tiles; break;
+        case 2: src = R->d_tile_cost; n = n_pix; break;
+        case 3: src = R->d_pix_rays; n = n_pix; break;
+        case 4: src = R->d_tile_order; n = n_tiles; break;
+        default: return set_error(CRT_ERR_INVALID_ARGUMENT, "unknown schedule buffer");
+    }
+    if (!src) n = 0;
+    *n_out = (int64_t)n;
+    n = std::min(n, (size_t)capacity);
+    if (n) {
+        HIP_TRY(hipSetDevice(R->device));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost));
+    }
     return CRT_OK;
 }
 
