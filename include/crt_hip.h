@@ -391,6 +391,38 @@ int crt_renderer_render_wavefront(crt_renderer* r, const crt_scene* scene, int s
 int crt_renderer_render_wavefront_queued(crt_renderer* r, const crt_scene* scene, int spp, int max_bounces, unsigned flags,
                                          const crt_trace_options* trace_opts, int sync_every,
                                          crt_wavefront_stats* stats_out, void* stream);
+/* Path finish (DESIGN.md "Path finish"): take a batch of paths and run them to their ends in one kernel, one lane per
+ * entry of a READ-ONLY batch (rays and paths; no hits).  The lane loads its pixel's RNG state, sum and
+ * d_remaining[pixel] once, then per ray: the lane kernels' closest-hit traversal in the lane, the crt_hit record in
+ * registers, the step of crt_scene_path_step_device, and when the path ended its contribution added to the sum and,
+ * while samples are left, one taken and its camera ray drawn as crt_scene_path_advance_device does.  At the end it
+ * stores the state, the sum and d_remaining[pixel] = 0.  The entry's first ray keeps its row's tmax; every later ray
+ * has +inf.  State, sums and d_remaining end as a loop of crt_scene_trace_device and crt_scene_path_advance_device run
+ * until its count is 0 leaves them, bit for bit.  Every iteration increments the bounce or ends the path, and an
+ * ended path takes a sample or leaves: a lane traces at most (d_remaining[pixel] + 1) * max_bounces rays, and the
+ * kernel's time is its longest lane's.  Entries: capacity, or min(*d_n, capacity) with *d_n (NULL: capacity entries)
+ * read by the kernel on `stream` and clamped there.  Entries that come in CRT_PATH_ENDED, whose pixel is outside the
+ * renderer's frame, or at or beyond the count read and write nothing.  d_rng / d_linear NULL: the renderer's own;
+ * d_remaining NULL: never regenerate, each path only to its own end.  d_totals: NULL, or the advance's two 64-bit
+ * words: [0] += the rays this call traced, [1] += 1 if the clamped count is not 0.  No two active entries may name
+ * the same pixel.  Asynchronous.  CRT_ERR_INVALID_ARGUMENT before any device use: a null or misaligned array, capacity
+ * < 0 or >= 2^31, a misaligned d_n or d_totals, max_bounces < 1, scene and renderer on different devices, a renderer
+ * without a camera.  CRT_ERR_UNSUPPORTED: a 4-wide scene whose stack bound the in-lane traversal's 64-entry stack
+ * cannot hold (3 * bound > 64; ray-query mode 1 refuses the same trees).  capacity == 0: CRT_OK, nothing launched. */
+int crt_scene_path_finish_device(const crt_scene* scene, crt_renderer* r, const crt_ray* d_rays, const crt_path* d_paths,
+        const uint32_t* d_n, int64_t capacity, int max_bounces, uint32_t* d_rng, float* d_linear, int32_t* d_remaining,
+        uint64_t* d_totals, void* stream);
+/* crt_renderer_render_wavefront_queued with a hand-off: whenever the host holds a batch size m (the number of pixels
+ * before the first round, then each block's read that gives m > 0) and m <= finish_below, the current batch goes to
+ * crt_scene_path_finish_device with its count word and capacity m, and the frame is done after one more copy and
+ * wait.  finish_below 0: never, the queued loop's frame, rounds and numbers; >= the number of pixels: the whole frame
+ * through the finish kernel straight after the camera rays; -1: the library's default (921,600 in this build, DESIGN.md §19's
+ * measurement, or 0 on a scene the finish call refuses); other negatives: CRT_ERR_INVALID_ARGUMENT.  finish_below > 0 on a scene the finish call refuses:
+ * CRT_ERR_UNSUPPORTED before any work.  The same sums, RNG state and rays for every value; stats_out->iterations: the
+ * rounds, plus one for a finish that got an entry.  Everything else as the queued entry. */
+int crt_renderer_render_wavefront_finish(crt_renderer* r, const crt_scene* scene, int spp, int max_bounces, unsigned flags,
+        const crt_trace_options* trace_opts, int sync_every, int64_t finish_below, crt_wavefront_stats* stats_out,
+        void* stream);
 /* Host only, no GPU (like crt_scene_export_identity): the per-material rows the step kernel reads, n_materials x 8
  * floats = (code, 0, 0, 0) (payload): code (int bits) 0 lambertian, 1 metal, 2 dielectric, 3 light, 4 unknown type
  * (emits 0); payload (albedo.xyz, 0), (albedo.xyz, min(roughness, 1)), (ior, 1 / ior, r0(1 / ior), r0(ior)) with

@@ -401,6 +401,12 @@ class Scene:
         return _paths.advance(self, renderer, rays, hits, paths, max_bounces, remaining, rng, linear, out, count_in,
                               totals)
 
+    def path_finish(self, renderer, rays, paths, max_bounces, remaining, rng=None, linear=None, count_in=None,
+                    totals=None):
+        """Run a batch of paths, and their pixels' remaining samples, to the end in one kernel (paths.finish)."""
+        from . import paths as _paths
+        _paths.finish(self, renderer, rays, paths, max_bounces, remaining, rng, linear, count_in, totals)
+
 
 def load_scene(obj_files, device: int = 0, **upload_options):
     hs = HostScene(obj_files)
@@ -471,7 +477,7 @@ class Renderer:
         check(_lib.hip().crt_renderer_render(self.h, scene.h, int(spp), int(max_bounces), flags, stream), "render")
 
     def render_wavefront(self, scene: Scene, spp: int, max_bounces: int = 20, accumulate=False, trace_options=None,
-                         stream=None, sync_every=None) -> dict:
+                         stream=None, sync_every=None, finish_below=None) -> dict:
         """The frame of render() as a wavefront in the library (crt_renderer_render_wavefront): camera rays, then trace /
         advance rounds over the handle's own batches (164 B per pixel, allocated by the first call), one host wait per
         round.  The same sums, RNG state and ray count, bit for bit.  trace_options: keywords of Scene.trace (mode,
@@ -479,11 +485,21 @@ class Renderer:
 
         sync_every: None is that loop.  An int is the loop enqueued ahead (crt_renderer_render_wavefront_queued): the
         rounds take their batch size from the device, and the host waits once per sync_every rounds (0: the library's
-        default).  The same frame and the same numbers for every value."""
+        default).  The same frame and the same numbers for every value.
+
+        finish_below: None keeps the dispatch above.  An int is the queued loop with a hand-off
+        (crt_renderer_render_wavefront_finish; sync_every None is then 0): as soon as the batch size the host holds
+        is <= finish_below, the batch goes to one kernel that runs its paths and their pixels' samples to the end
+        (Scene.path_finish).  0 never hands off, a value >= the number of pixels is the whole frame through that
+        kernel, -1 the library's default.  The same frame and rays; iterations counts the finish as one."""
         o = Scene._trace_options(**dict(dict(mode=0, grid_waves=0, stack_lds=0, refill_threshold=0), **(trace_options or {})))
         s = _lib.WavefrontStats()
         flags = RENDER_ACCUMULATE if accumulate else 0
-        if sync_every is None:
+        if finish_below is not None:
+            fn = _lib.require("crt_renderer_render_wavefront_finish")
+            check(fn(self.h, scene.h, int(spp), int(max_bounces), flags, C.byref(o), int(sync_every or 0),
+                     int(finish_below), C.byref(s), stream), "render_wavefront_finish")
+        elif sync_every is None:
             fn = _lib.require("crt_renderer_render_wavefront")
             check(fn(self.h, scene.h, int(spp), int(max_bounces), flags, C.byref(o), C.byref(s), stream), "render_wavefront")
         else:

@@ -150,16 +150,18 @@ HIP_SYMBOLS = [
     "crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
     "crt_scene_path_advance_device", "crt_path_advance_entries", "crt_renderer_render_wavefront",
     "crt_scene_trace_indirect_device", "crt_scene_path_advance_indirect_device", "crt_renderer_render_wavefront_queued",
+    "crt_scene_path_finish_device", "crt_renderer_render_wavefront_finish",
     "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer",
 ]
-# Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, then
-# the schedule self-tests): bound when the loaded
+# Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, the
+# schedule self-tests, then the path finish): bound when the loaded
 # library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
 # require() otherwise.
 OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
                     "crt_scene_path_advance_device", "crt_path_advance_entries", "crt_renderer_render_wavefront",
                     "crt_scene_trace_indirect_device", "crt_scene_path_advance_indirect_device",
                     "crt_renderer_render_wavefront_queued",
+                    "crt_scene_path_finish_device", "crt_renderer_render_wavefront_finish",
                     "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer")
 
 HOST_SYMBOLS = [
@@ -257,6 +259,8 @@ def hip():
             "crt_scene_trace_indirect_device": ([P, P, P, C.c_int64, P, P, P, C.c_uint, P], i32),
             "crt_scene_path_advance_indirect_device": ([P, P, P, P, P, P, C.c_int64, i32, P, P, P, P, P, P, P, P], i32),
             "crt_renderer_render_wavefront_queued": ([P, P, i32, i32, C.c_uint, P, i32, P, P], i32),
+            "crt_scene_path_finish_device": ([P, P, P, P, P, C.c_int64, i32, P, P, P, P, P], i32),
+            "crt_renderer_render_wavefront_finish": ([P, P, i32, i32, C.c_uint, P, i32, C.c_int64, P, P], i32),
             "crt_selftest_tile_schedule": ([P, P, i32, i32, i32, i32, i32, P], i32),
             "crt_selftest_pixel_order": ([P, i32, P, i32, i32], i32),
             "crt_selftest_schedule_buffer": ([P, i32, P, C.c_int64, P], i32),

@@ -8,6 +8,9 @@ queries, as device calls on torch tensors.
   advance(scene, renderer, rays,       step, regenerate and compact in one kernel: the survivors and the ended pixels'
           hits, paths, max_bounces,    next camera samples appended to an output batch, their number in a device counter
           remaining)                   
+  finish(scene, renderer, rays,        a batch of paths run to their ends in one kernel, one lane per path with the trace
+         paths, max_bounces,          in the lane: what a loop of Scene.trace and advance leaves, without the rounds
+         remaining)                   
   render(scene, renderer, spp)         the reference driver: a wavefront path tracer out of camera_rays, Scene.trace
                                        and Scene.path_step (compact="torch") or Scene.path_advance (compact="device")
                                        whose sums, RNG state and ray count equal Renderer.render's bit for bit;
@@ -222,6 +225,50 @@ def advance(scene, renderer, rays, hits, paths, max_bounces, remaining, rng=None
     return rays_out, paths_out, count
 
 
+def finish(scene, renderer, rays, paths, max_bounces, remaining, rng=None, linear=None, count_in=None, totals=None):
+    """Run a batch of paths to their ends in one kernel (crt_scene_path_finish_device): every ACTIVE path of the
+    read-only batch is traced, scattered and traced again in its own lane until it ends; it then adds to its pixel's
+    sum and, while remaining[pixel] > 0, goes on with that pixel's next camera sample.  At the end the pixel's RNG
+    state and sum are stored and remaining[pixel] = 0: what Scene.trace and advance leave when they are repeated until
+    the count is 0, bit for bit.  The first ray of an entry keeps its row's tmax.  rays float32 [n, 8], paths int32 or
+    float32 [n, 8]; no hits.  remaining: int32 [pixels] on the device, or None for "never regenerate" (each path only to
+    its own end).  rng, linear: tensors as for advance, or None for the renderer's own.  count_in: a 1-element int32
+    device tensor; the kernel then takes entries [0, min(count_in, n)), count_in read on the stream.  totals: an int64
+    [2] device tensor the kernel adds (rays traced, 1 if it had an entry) to.  No two active entries on one pixel.
+    Returns nothing.  No host copy, no synchronisation; enqueued on torch's current stream.  A lane traces at most
+    (remaining[pixel] + 1) * max_bounces rays, and the call takes as long as its longest lane."""
+    import torch
+    dev = scene.device
+    _rows(rays, "rays", (torch.float32,))
+    _rows(paths, "paths", (torch.int32, torch.float32))
+    n = rays.shape[0]
+    if n != paths.shape[0]:
+        raise ValueError("rays and paths differ in length")
+    if int(max_bounces) < 1:
+        raise ValueError("max_bounces must be >= 1")
+    if count_in is not None:
+        _count(count_in, "count_in")
+    if totals is not None:
+        _flat(totals, "totals", torch.int64, numel=2)
+    if not _is_renderer(renderer):
+        raise ValueError("renderer must be a Renderer")
+    if renderer.device != dev:
+        raise ValueError("the renderer is on another device than the scene")
+    n_pix = renderer.width * renderer.height
+    if remaining is not None:
+        _flat(remaining, "remaining", torch.int32, numel=n_pix)
+    if rng is not None:
+        _flat(rng, "rng", torch.int32, numel=6 * n_pix)
+    if linear is not None:
+        _flat(linear, "linear", torch.float32, numel=3 * n_pix)
+    _on_device(dev, rays=rays, paths=paths, remaining=remaining, rng=rng, linear=linear, count_in=count_in, totals=totals)
+    fn = _lib.require("crt_scene_path_finish_device")
+    ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+    check(fn(scene.h, renderer.h, rays.data_ptr(), paths.data_ptr(), ptr(count_in), n, int(max_bounces), ptr(rng),
+             ptr(linear), ptr(remaining), ptr(totals), torch.cuda.current_stream(torch.device("cuda", dev)).cuda_stream),
+          "crt_scene_path_finish_device")
+
+
 def shade_rows(desc) -> np.ndarray:
     """The per-material rows the step kernel reads (crt_scene_export_shade_rows; host only), float32 [materials, 2, 4]:
     row 0 = (code as int bits, 0, 0, 0), row 1 = the payload."""
@@ -264,7 +311,7 @@ class _Phases:
 
 
 def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None, trace_options=None,
-           profile=None, compact="torch", sync_every=1) -> dict:
+           profile=None, compact="torch", sync_every=1, finish_below=0) -> dict:
     """The reference driver: spp samples per pixel as a wavefront of camera_rays / Scene.trace / Scene.path_step calls on
     the renderer's own RNG state and (fresh) sums, so renderer.linear(), rng_state() and resolve() work afterwards
     and hold what renderer.render(scene, spp, max_bounces) leaves, bit for bit.
@@ -287,6 +334,12 @@ def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None
     The same bits, rays and iterations.  on_bounce is then called with a fourth argument, the device count: its first
     three arguments are views of the bound's length, whose rows from the count on are stale, and only rows below the
     count may be edited.  The profile's entries n are then the bounds.
+
+    finish_below (compact="device"): K > 0 hands the batch to finish() as soon as the count the host holds (every pixel
+    at the start, then each count it reads) is <= K; finish() runs those paths and their pixels' remaining samples to
+    the end in one kernel.  The same bits and rays; the finish counts as one iteration.  on_bounce is called for the
+    wavefront rounds only, never for the bounces inside finish(): a hybrid integrator does its own work on the first
+    rounds and lets the library complete the frame.  The profile has no row for the finish.  0: never.
     Returns {"rays": rays traced, "iterations": trace / step rounds}."""
     import torch
     spp, max_bounces = int(spp), int(max_bounces)
@@ -299,6 +352,11 @@ def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None
     sync_every = int(sync_every)
     if sync_every != 1 and compact != "device":
         raise ValueError('sync_every other than 1 needs compact="device"')
+    if finish_below != int(finish_below) or int(finish_below) < 0:
+        raise ValueError("finish_below must be an integer >= 0")
+    finish_below = int(finish_below)
+    if finish_below and compact != "device":
+        raise ValueError('finish_below other than 0 needs compact="device"')
     opts = dict(trace_options or {})
     n_pix = renderer.width * renderer.height
     tdev = torch.device("cuda", renderer.device)
@@ -327,6 +385,10 @@ def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None
             count = torch.full((1,), n_pix, dtype=torch.int32, device=tdev)
             m = n_pix
             while m:
+                if m <= finish_below:
+                    finish(scene, renderer, batches[cur][0][:m], batches[cur][1][:m], max_bounces, remaining,
+                           count_in=count, totals=totals)
+                    break
                 for _ in range(sync_every):
                     rays, paths = batches[cur][0][:m], batches[cur][1][:m]
                     phases.mark("start")
@@ -350,6 +412,12 @@ def render(scene, renderer, spp, max_bounces=20, regenerate=True, on_bounce=None
             ping = camera_rays(renderer)
             rays, paths = ping
             while rays.shape[0]:
+                if rays.shape[0] <= finish_below:
+                    totals = torch.zeros((2,), dtype=torch.int64, device=tdev)
+                    finish(scene, renderer, rays, paths, max_bounces, remaining, totals=totals)
+                    total += int(totals[0])
+                    iterations += 1
+                    break
                 total += rays.shape[0]
                 iterations += 1
                 phases.mark("start")

@@ -16,6 +16,8 @@
 //   crt_path_advance_kernel, crt_path_advance_indirect_kernel
 //                            further down: step, regenerate and compact, and the same body
 //                            (crt_path_advance_body.inc) over a device-side entry count (§18).
+//   crt_path_finish_kernel   after those: one lane per path, run to the end of its pixel's samples with the lane
+//                            kernels' trace in the lane (§19).
 //
 // unit(), the reciprocal and the glass test pick their fast or IEEE sequence by a ballot over the lanes that run them;
 // both sequences are correctly rounded, so the lanes a wave happens to hold (a partial last wave, entries that came in
@@ -315,6 +317,122 @@ __global__ __launch_bounds__(256) void crt_path_advance_indirect_kernel(PathAdva
 #undef ADVANCE_BODY_N
 }
 
+// ------------------------------------------------------------------ finish
+// crt_path_finish_kernel    one lane per entry of a read-only input batch (rays, paths; no hits): the lane runs its
+//                           pixel's trace / advance rounds to the end by itself.  It loads the RNG state, the pixel's sum
+//                           and remaining[pixel] once, then per ray: the lane kernels' trace (trace4, or trace<> on the
+//                           ray's layout), the hit record by trace_store's rule in registers, scatter_step(), and on an
+//                           end the sum's addition and, while samples are left, next_ray()'s camera block on the state
+//                           it holds, exactly advance_entry()'s.  Three stores at the end: the state, the sum, 0 samples
+//                           left.  Every iteration increments the bounce or ends the path, and an ended path takes one
+//                           of the pixel's samples or leaves: at most (remaining + 1) * max_bounces rays per lane.
+//
+// One wave per workgroup: the batches this is for are a few thousand entries, which so spread over the CUs, and the
+// kernel's time is its longest lane's chain of traces.  The entry count is Q.n, or min(*Q.d_n, Q.n) with *Q.d_n read
+// here (§18's rule).  Entries that come in ended, name no pixel of the frame or lie at or beyond the count read and
+// write nothing.  The functions that pick a fast or an IEEE sequence by ballot are correctly rounded either way, so the
+// divergent loop changes no bit (see the head of this file).
+struct PathFinishParams {
+    const float4* __restrict__ rays;       // 2 rows per entry, read only
+    const float4* __restrict__ paths;
+    const float4* __restrict__ nodes;      // the scene, as TraceParams carries it
+    const float4* __restrict__ prims;
+    const float4* __restrict__ chain;
+    const float4* __restrict__ shade;
+    const int4* __restrict__ ident;
+    const float4* __restrict__ rows;       // per material: (code, 0, 0, 0) (payload)
+    int n_nodes, n_layouts, n_chain, sphere_first, n_ray_spheres;
+    int scene_width;                       // 2 = threaded nodes (trace<>), 4 = 4-wide nodes (trace4)
+    uint32_t* __restrict__ rng;            // 6 words per pixel
+    float* __restrict__ linear;            // 3 floats per pixel
+    int32_t* __restrict__ remaining;       // per pixel: samples not yet started; null: never regenerate
+    const uint32_t* __restrict__ d_n;      // null, or the entry count on the device
+    unsigned long long* __restrict__ totals;   // null, or [0] += rays traced, [1] += 1 if the count is not 0
+    uint32_t n, n_pix;                     // n: the entries, or their capacity with d_n
+    int n_mats, max_bounces;
+    crt_camera_desc cam;
+    int width, height;
+    float rcp_w, rcp_h;
+    int fast_uv;
+};
+
+__global__ __launch_bounds__(64) void crt_path_finish_kernel(PathFinishParams Q) {
+    const uint32_t n = Q.d_n ? min(*Q.d_n, Q.n) : Q.n;
+    if (blockIdx.x * 64u >= n) return;                       // the whole wave: the lanes below stay together for the sum
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    const float INF = __builtin_inff();
+    uint64_t traced = 0;
+    float4 p1 = make_float4(0.f, __int_as_float(CRT_PATH_ENDED), 0.f, 0.f);
+    if (i < n) p1 = Q.paths[2 * (size_t)i + 1];
+    const uint32_t pix = __float_as_uint(p1.x);
+    if (i < n && __float_as_int(p1.y) == CRT_PATH_ACTIVE && pix < Q.n_pix) {
+        const float4 p0 = Q.paths[2 * (size_t)i];
+        const float4 ray0 = Q.rays[2 * (size_t)i], ray1 = Q.rays[2 * (size_t)i + 1];
+        uint32_t* rp = Q.rng + 6 * (size_t)pix;
+        float* L = Q.linear + 3 * (size_t)pix;
+        Rng s = rng_load(rp);
+        V3 sum = v3(L[0], L[1], L[2]);
+        int32_t left = Q.remaining ? Q.remaining[pix] : 0;
+        V3 o = v3(ray0.x, ray0.y, ray0.z), d = v3(ray1.x, ray1.y, ray1.z), thr = v3(p0.x, p0.y, p0.z);
+        int bounce = __float_as_int(p0.w);
+        float tmax = ray0.w;                                 // the entry's first ray keeps its row's; +inf afterwards
+        for (;;) {
+            // ---- the lane kernels' trace (crt_trace_lane_body.inc)
+            float t;
+            TraceCounts cnt{};
+            const int hit = Q.scene_width == 4 ? trace4(Q.nodes, Q.prims, Q.chain, Q.n_chain, Q.sphere_first,
+                                                        Q.n_ray_spheres, o, d, t)
+                                               : trace<false>(Q.nodes, Q.prims, Q.n_nodes,
+                                                              layout_base(d, Q.n_layouts, Q.n_nodes), o, d, t, cnt);
+            ++traced;
+            // ---- its record, by trace_store()'s rule
+            float4 h0 = make_float4(-1.f, 0.f, 0.f, 0.f), h1 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (hit >= 0 && t <= tmax) {
+                const int4 id = Q.ident[hit];
+                const float4* R = Q.shade + 3u * (uint32_t)hit;
+                const float4 r0 = R[0];
+                V3 nrm = v3(r0.x, r0.y, r0.z);
+                if (__float_as_uint(r0.w) & SHADE_SPHERE) {
+                    const float ir = R[2].x;
+                    const V3 hp = o + t * d;                 // Ray::pointAtDistance
+                    nrm = ir * (hp - nrm);
+                }
+                const bool front = dot(d, nrm) < 0;          // HitInfo::setFaceNormal
+                h0 = make_float4(t, __int_as_float(id.x), __int_as_float(id.y), __int_as_float(id.z));
+                h1 = make_float4(nrm.x, nrm.y, nrm.z, __int_as_float(front ? 1 : 0));
+            }
+            tmax = INF;
+            const Scattered r = scatter_step(h0, h1, Q.rows, Q.n_mats, Q.max_bounces, s, o, d, thr, bounce);
+            s = r.s;
+            o = r.o; d = r.d; thr = r.thr;
+            bounce = r.bounce;
+            if (r.ended) {                                   // ---- the entry's fate, as advance_entry()
+                sum = sum + r.add;                           // pixel_color += ..., the (0, 0, 0) of a killed path too
+                if (left <= 0) break;
+                --left;                                      // the pixel's next sample, as crt_camera_rays_kernel draws it
+                const CamRegs C = cam_regs(Q.cam, Q.width, Q.height, Q.rcp_w, Q.rcp_h, Q.fast_uv);
+                PathState S = new_sample_state(s);
+                next_ray(S, C, (int)(pix % (uint32_t)Q.width), (int)(pix / (uint32_t)Q.width), 1);
+                s = S.s;
+                o = S.o;
+                d = S.d;
+                thr = v3(1.f, 1.f, 1.f);
+                bounce = 0;
+            }
+        }
+        rng_store(rp, s);
+        L[0] = sum.x; L[1] = sum.y; L[2] = sum.z;
+        if (Q.remaining) Q.remaining[pix] = 0;
+    }
+    if (Q.totals) {
+        const uint64_t rays = wave_sum_u64(traced);
+        if (threadIdx.x == 0) {
+            if (rays) atomicAdd(&Q.totals[0], (unsigned long long)rays);
+            if (blockIdx.x == 0) atomicAdd(&Q.totals[1], 1ull);   // n != 0: this workgroup did not leave above
+        }
+    }
+}
+
 // ------------------------------------------------------------------ host side
 namespace {
 
@@ -393,6 +511,10 @@ int advance_enqueue(const std::string& what, const crt_scene* S, crt_renderer* R
     return CRT_OK;
 }
 
+// trace_enqueue's lane_ok: trace4's per-lane stack takes up to three entries per branching ancestor and drops what does
+// not fit without a report, so a 4-wide tree whose bound could overflow it never goes through the finish kernel.
+bool finish_lane_ok(const crt_scene* S) { return S->width != 4 || 3 * (int64_t)S->stack_bound <= TRACE4_STACK; }
+
 }  // namespace
 
 extern "C" {
@@ -465,6 +587,48 @@ int crt_scene_path_advance_indirect_device(const crt_scene* S, crt_renderer* R, 
 
 int crt_path_advance_entries(void) { return ADV_ENTRIES; }
 
+int crt_scene_path_finish_device(const crt_scene* S, crt_renderer* R, const crt_ray* d_rays, const crt_path* d_paths,
+                                 const uint32_t* d_n, int64_t capacity, int max_bounces, uint32_t* d_rng, float* d_linear,
+                                 int32_t* d_remaining, uint64_t* d_totals, void* stream) {
+    const std::string what = "path finish";
+    if (!S) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": null scene");
+    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": null renderer");
+    if (int rc = path_batch_args(what.c_str(), capacity, d_rays, d_paths, d_rays)) return rc;
+    if (max_bounces < 1) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": max_bounces must be >= 1");
+    if (((uintptr_t)d_rng | (uintptr_t)d_linear | (uintptr_t)d_remaining | (uintptr_t)d_n) & 3u)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": RNG state, sums, remaining and the count must be 4-byte aligned");
+    if ((uintptr_t)d_totals & 7u) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": totals must be 8-byte aligned");
+    if (S->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": scene and renderer on different devices");
+    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, what + ": the renderer has no camera (crt_renderer_set_camera)");
+    if (!finish_lane_ok(S))
+        return set_error(CRT_ERR_UNSUPPORTED, what + ": the tree's stack bound exceeds the in-lane traversal's 64-entry "
+                                              "stack (3 entries per level)");
+    if (capacity == 0) return CRT_OK;
+    HIP_TRY(hipSetDevice(S->device));
+    PathFinishParams Q{};
+    Q.rays = reinterpret_cast<const float4*>(d_rays);
+    Q.paths = reinterpret_cast<const float4*>(d_paths);
+    Q.nodes = S->d_nodes; Q.prims = S->d_prims; Q.chain = S->d_chain; Q.shade = S->d_shade;
+    Q.ident = S->d_ident;
+    Q.rows = S->d_mat_rows;
+    Q.n_nodes = S->n_nodes; Q.n_layouts = S->layouts; Q.n_chain = S->n_chain;
+    Q.sphere_first = S->sphere_first; Q.n_ray_spheres = S->n_ray_spheres;
+    Q.scene_width = S->width;
+    Q.rng = d_rng ? d_rng : R->d_rng;
+    Q.linear = d_linear ? d_linear : R->d_sum;
+    Q.remaining = d_remaining;
+    Q.d_n = d_n;
+    Q.totals = reinterpret_cast<unsigned long long*>(d_totals);
+    Q.n = (uint32_t)capacity;
+    Q.n_pix = (uint32_t)(R->width * R->height);
+    Q.n_mats = S->n_mats;
+    Q.max_bounces = max_bounces;
+    set_camera_frame(Q, R);
+    hipLaunchKernelGGL(crt_path_finish_kernel, dim3((unsigned)((capacity + 63) / 64)), dim3(64), 0, (hipStream_t)stream, Q);
+    HIP_TRY(hipGetLastError());
+    return CRT_OK;
+}
+
 }  // extern "C"
 
 // The wavefront loop's scratch: owned by the renderer handle, allocated on first use, freed with the handle.
@@ -485,6 +649,10 @@ constexpr int QUEUE_WORDS = 8, QUEUE_ERR = 2, QUEUE_TOTALS = 4;   // WavefrontSc
 // crt_renderer_render_wavefront_queued's sync_every = 0: iterations enqueued between two host waits
 // (profiles/indirect/path_bench.jsonl)
 constexpr int QUEUE_SYNC_EVERY = 32;
+// crt_renderer_render_wavefront_finish's finish_below = -1: batches of at most this many entries go to the finish kernel.
+// The fastest setting of the sweep (profiles/finish/path_bench.jsonl): the 921,600 pixels of its
+// 1280x720 frame, the whole frame through the finish kernel (15.5 ms against 27.5 ms at 0).  Larger frames were not measured.
+constexpr int64_t QUEUE_FINISH_BELOW = 921600;
 
 void crtx_free_wavefront_scratch(crt_renderer* R) {
     WavefrontScratch* X = R->wavefront;
@@ -595,9 +763,16 @@ int crt_renderer_render_wavefront(crt_renderer* R, const crt_scene* Sc, int spp,
     return trace_take_error(S->trace);
 }
 
-int crt_renderer_render_wavefront_queued(crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags,
-                                         const crt_trace_options* trace_opts, int sync_every,
-                                         crt_wavefront_stats* stats_out, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// The queued loop (crt_renderer_render_wavefront_queued) and its hand-off (crt_renderer_render_wavefront_finish):
+// whenever the host holds a batch size m <= finish_below, the current batch goes to crt_scene_path_finish_device and
+// the frame is done after one more copy and wait.  finish_below 0: never.
+int wavefront_queued(crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags,
+                     const crt_trace_options* trace_opts, int sync_every, int64_t finish_below,
+                     crt_wavefront_stats* stats_out, void* stream) {
     if (!R || !Sc) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: null argument");
     if (spp < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: negative spp");
     if (max_bounces < 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: max_bounces must be >= 1");
@@ -612,6 +787,9 @@ int crt_renderer_render_wavefront_queued(crt_renderer* R, const crt_scene* Sc, i
     const int64_t n_pix = (int64_t)R->width * R->height;
     if (n_pix >= ((int64_t)1 << 31)) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: 2^31 pixels or more");
     if (n_pix > TRACE_LAUNCH_RAYS) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: the queued loop takes at most 2^30 pixels");
+    if (finish_below > 0 && !finish_lane_ok(Sc))
+        return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: finish_below needs a tree whose stack bound fits the "
+                                              "in-lane traversal's 64-entry stack (3 entries per level)");
     const int block = sync_every ? sync_every : QUEUE_SYNC_EVERY;
     crt_scene* S = const_cast<crt_scene*>(Sc);   // the trace scratch belongs to the handle (handles are not thread-safe)
     HIP_TRY(hipSetDevice(R->device));
@@ -640,6 +818,14 @@ int crt_renderer_render_wavefront_queued(crt_renderer* R, const crt_scene* Sc, i
     // count reached 0 trace nothing and append nothing.
     int64_t m = n_pix;
     while (m > 0) {
+        if (m <= finish_below) {                             // the hand-off: the lanes run their pixels to the end
+            if (int rc = crt_scene_path_finish_device(S, R, X->rays[cur], X->paths[cur], X->d_queue + cur, m, max_bounces,
+                                                      nullptr, nullptr, X->remaining, d_totals, stream))
+                return rc;
+            HIP_TRY(hipMemcpyAsync(X->h_queue, X->d_queue, QUEUE_WORDS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            break;
+        }
         for (int k = 0; k < block; ++k) {
             if (int rc = trace_enqueue(S, X->rays[cur], m, trace_opts, X->hits, nullptr, 0, st, X->d_queue + cur, d_err))
                 return rc;
@@ -668,7 +854,28 @@ int crt_renderer_render_wavefront_queued(crt_renderer* R, const crt_scene* Sc, i
         const unsigned long long word = X->h_queue[QUEUE_ERR];
         HIP_TRY(hipMemcpy(S->trace->d_stats + TRACE_ERR_WORD, &word, 8, hipMemcpyHostToDevice));
     }
-    return trace_take_error(S->trace);
+    // a frame handed over before its first round ran no query: a scene that was never traced has no scratch to ask
+    return S->trace ? trace_take_error(S->trace) : CRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crt_renderer_render_wavefront_queued(crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags,
+                                         const crt_trace_options* trace_opts, int sync_every,
+                                         crt_wavefront_stats* stats_out, void* stream) {
+    return wavefront_queued(R, Sc, spp, max_bounces, flags, trace_opts, sync_every, 0, stats_out, stream);
+}
+
+int crt_renderer_render_wavefront_finish(crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags,
+                                         const crt_trace_options* trace_opts, int sync_every, int64_t finish_below,
+                                         crt_wavefront_stats* stats_out, void* stream) {
+    if (finish_below < -1)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: finish_below must be >= 0, or -1 for the default");
+    // the default never refuses a scene: a tree the finish kernel cannot take keeps the queued loop
+    if (finish_below < 0) finish_below = Sc && finish_lane_ok(Sc) ? QUEUE_FINISH_BELOW : 0;
+    return wavefront_queued(R, Sc, spp, max_bounces, flags, trace_opts, sync_every, finish_below, stats_out, stream);
 }
 
 int crt_scene_export_shade_rows(const crt_scene_desc* D, float* out, int64_t* n_materials) {

@@ -5,8 +5,8 @@
                                       [--expect-changed crt_path_step_kernel ...]
 
 Compares, for every crt_render_kernel / crt_trace_kernel / crt_trace_lane_kernel instantiation, their indirect forms
-and the path kernels (crt_camera_rays_kernel, crt_path_step_kernel, crt_path_advance_kernel and its indirect form), the
-figures of
+and the path kernels (crt_camera_rays_kernel, crt_path_step_kernel, crt_path_advance_kernel and its indirect form,
+crt_path_finish_kernel), the figures of
 -Rpass-analysis=kernel-resource-usage (isa.log) and the assembly text of build/crt_hip.s from the kernel's label to its
 .end_amdhsa_kernel: every instruction and the kernel descriptor.  The compiler numbers a function's local labels
 `.LBB<f>_<b>` with f = the function's position in the module; a kernel added ahead of the template instantiations
@@ -24,7 +24,7 @@ from pathlib import Path
 
 WANTED = ("crt_render_kernel", "crt_trace_kernel", "crt_trace_lane_kernel", "crt_camera_rays_kernel", "crt_path_step_kernel",
           "crt_path_advance_kernel", "crt_trace_indirect_kernel", "crt_trace_lane_indirect_kernel",
-          "crt_path_advance_indirect_kernel")
+          "crt_path_advance_indirect_kernel", "crt_path_finish_kernel")
 FIGURES = r"(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\])"
 
 

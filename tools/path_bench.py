@@ -2,7 +2,7 @@
 Renderer.render on the same frame, and where their time goes.
 
     python tools/path_bench.py [--width 1280 --height 720] [--spp 16] [--bounces 20] [--reps 7] [--warmup 1]
-                               [--mode 0] [--rows frame,phases,step,queue,advance,queued]
+                               [--mode 0] [--rows frame,phases,step,queue,advance,queued,finish]
 
 No pass / fail: JSON lines.  Scene: cornell_bunny, rebuilt 4-wide tree, default options, bench camera, seed 41.
 
@@ -28,6 +28,13 @@ No pass / fail: JSON lines.  Scene: cornell_bunny, rebuilt 4-wide tree, default 
           Renderer.render_wavefront(sync_every=K) for K = 1, 2, 4, 8, 16, 32 and 0 (the library's default): medians, the
           run-to-run spread of the existing library loop (the yardstick), each K's ratio to it, equal bits, rays and
           iterations.
+  finish  (only when asked for) `reps` rounds, interleaved in one process after a warm-up of every
+          driver: Renderer.render, Renderer.render_wavefront(sync_every=0) (the yardstick, with its spread over the
+          runs) and Renderer.render_wavefront(sync_every=0, finish_below=K) for K = 0, 1k, 4k, 16k, 64k, 256k and the
+          number of pixels.  One line per driver: median and minimum ms, rays, iterations, equal bits; for a K also its
+          ratio to the yardstick, the batch handed over (the bound the host held and the device's count) and the
+          finish kernel's own milliseconds, from events round paths.finish in a Python copy of the loop that stops at
+          the same hand-off.  A last line names the fastest K and its margin over K = 0 against the yardstick's spread.
   step    the step kernel alone over that frame's iterations: paths per second, and bytes per second against the bytes
           an entry must move -- ray 32 B read, hit 32 B read, path 32 B read and written, RNG 24 B read and written,
           then the ray's 32 B written by a path that goes on or the sum's 12 B read and written by one that ends.
@@ -107,6 +114,8 @@ def main():
         queue_rows(a, want, case, direct, wavefront, library, state)
     if "queued" in want:
         queued_rows(a, case, direct, wavefront, library, queued, state)
+    if "finish" in want:
+        finish_rows(a, case, sc, r, opts, direct, queued, state)
     if not want & {"frame", "phases", "step"}:
         return
     for _ in range(a.warmup):
@@ -245,6 +254,93 @@ def queued_rows(a, case, direct, wavefront, library, queued, state):
                           **{f"queued_{k}_over_library": round(med(ms[f"queued_{k}"]) / med(lib), 3) for k in QUEUED_KS},
                           rays=res["library"]["rays"], iterations=res["library"]["iterations"], equal_bits=bool(equal))),
           flush=True)
+
+
+FINISH_KS = (0, 1 << 10, 1 << 12, 1 << 14, 1 << 16, 1 << 18)     # and the number of pixels
+QUEUE_SYNC_EVERY = 32                                             # the library's block for sync_every = 0
+
+
+def finish_rows(a, case, sc, r, opts, direct, queued, state):
+    import torch
+    import crt_amd
+    from crt_amd import paths
+    med = statistics.median
+    n_pix = a.width * a.height
+    ks = FINISH_KS + (n_pix,)
+
+    def handoff(k):
+        r.init_rand(41)
+        r.synchronize()
+        res = r.render_wavefront(sc, a.spp, a.bounces, trace_options=opts, sync_every=0, finish_below=k)
+        return res["ms"], res
+
+    def kernel(k):
+        """The library's loop at sync_every = 0 out of the Python calls, up to the same hand-off: the bound the host
+        holds, the device's count and the milliseconds of paths.finish alone."""
+        r.init_rand(41)
+        r.write_linear(np.zeros((a.height, a.width, 3), np.float32))
+        tdev = torch.device("cuda", 0)
+        remaining = torch.full((n_pix,), a.spp - 1, dtype=torch.int32, device=tdev)
+        batches = [crt_amd.camera_rays(r), (torch.empty((n_pix, 8), dtype=torch.float32, device=tdev),
+                                            torch.empty((n_pix, 8), dtype=torch.int32, device=tdev))]
+        hits = torch.empty((n_pix, 8), dtype=torch.float32, device=tdev)
+        count = torch.full((1,), n_pix, dtype=torch.int32, device=tdev)
+        m, cur = n_pix, 0
+        while m:
+            if m <= k:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                paths.finish(sc, r, batches[cur][0][:m], batches[cur][1][:m], a.bounces, remaining, count_in=count)
+                e1.record()
+                e1.synchronize()
+                return {"handed_bound": m, "handed_entries": int(count), "finish_kernel_ms": round(e0.elapsed_time(e1), 3)}
+            for _ in range(QUEUE_SYNC_EVERY):
+                rays, pth = batches[cur][0][:m], batches[cur][1][:m]
+                sc.trace(rays, count=count, out=hits[:m], **opts)
+                _, _, count = paths.advance(sc, r, rays, hits[:m], pth, a.bounces, remaining, out=batches[cur ^ 1],
+                                            count_in=count)
+                cur ^= 1
+            m = min(int(count), m)
+        return {"handed_bound": 0, "handed_entries": 0, "finish_kernel_ms": None}
+
+    runs = [("queued_0", lambda: queued(0))] + [(f"finish_{k}", lambda k=k: handoff(k)) for k in ks]
+    for _ in range(a.warmup):
+        direct()
+        for _, run in runs:
+            run()
+    ms = {"render": [], **{k: [] for k, _ in runs}}
+    states, res = {}, {}
+    for _ in range(a.reps):
+        ms["render"].append(direct())
+        states["render"] = state()
+        for k, run in runs:
+            t, res[k] = run()
+            ms[k].append(t)
+            states[k] = state()
+    equal = {k: bool(np.array_equal(states[k][0], states["render"][0]) and np.array_equal(states[k][1], states["render"][1])
+                     and res[k]["rays"] == res["queued_0"]["rays"]) for k, _ in runs}
+    yard = ms["queued_0"]
+    spread = max(yard) - min(yard)
+    print(json.dumps(dict(case, row="finish", driver="render", reps=a.reps, ms_median=round(med(ms["render"]), 3),
+                          ms_min=round(min(ms["render"]), 3))), flush=True)
+    print(json.dumps(dict(case, row="finish", driver="render_wavefront(sync_every=0)", reps=a.reps,
+                          ms_median=round(med(yard), 3), ms_min=round(min(yard), 3), ms_max=round(max(yard), 3),
+                          ms_spread=round(spread, 3), ms_all=[round(v, 3) for v in yard], rays=res["queued_0"]["rays"],
+                          iterations=res["queued_0"]["iterations"], equal_bits=equal["queued_0"])), flush=True)
+    for k in ks:
+        v = ms[f"finish_{k}"]
+        print(json.dumps(dict(case, row="finish", driver=f"render_wavefront(sync_every=0, finish_below={k})", finish_below=k,
+                              reps=a.reps, ms_median=round(med(v), 3), ms_min=round(min(v), 3), ms_max=round(max(v), 3),
+                              over_yardstick=round(med(v) / med(yard), 3), rays=res[f"finish_{k}"]["rays"],
+                              iterations=res[f"finish_{k}"]["iterations"], equal_bits=equal[f"finish_{k}"], **kernel(k))),
+              flush=True)
+    best = min(ks, key=lambda k: med(ms[f"finish_{k}"]))
+    gain = med(ms["finish_0"]) - med(ms[f"finish_{best}"])
+    print(json.dumps(dict(case, row="finish", driver="summary", fastest_finish_below=best,
+                          fastest_ms_median=round(med(ms[f"finish_{best}"]), 3), finish_0_ms_median=round(med(ms["finish_0"]), 3),
+                          gain_over_finish_0_ms=round(gain, 3), yardstick_spread_ms=round(spread, 3),
+                          default_rule_says=best if gain > spread else 0)), flush=True)
 
 
 if __name__ == "__main__":
