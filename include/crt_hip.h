@@ -423,6 +423,50 @@ int crt_scene_path_finish_device(const crt_scene* scene, crt_renderer* r, const 
 int crt_renderer_render_wavefront_finish(crt_renderer* r, const crt_scene* scene, int spp, int max_bounces, unsigned flags,
         const crt_trace_options* trace_opts, int sync_every, int64_t finish_below, crt_wavefront_stats* stats_out,
         void* stream);
+/* ---- adaptive sampling (no reference counterpart; DESIGN.md "Adaptive sampling") ----
+ * A frame whose 8x8 tiles (the tile kernels' own: tiles_x = (W + 7) / 8, tile t covers x = (t % tiles_x) * 8 .. + 7,
+ * y = (t / tiles_x) * 8 .. + 7) stop receiving samples once they look converged.  Every pixel first receives spp_min
+ * samples, in two ordinary renders of spp_min / 2 (the automatic kernel choice, fresh sums).  Then for n = spp_min,
+ * 2 spp_min, ... while n < spp_max, the tiles that hold n samples get an error estimate from the two halves of their
+ * samples (P = the sums after n / 2, Q = the sums of the other n / 2; per pixel d = |P - Q| summed over the channels,
+ * I = the sum of the channels / n, e = I > 0 ? (d / (n / 2)) / sqrt(I) : 0, the term of Dammertz et al.'s stopping
+ * condition; the tile's error E is the mean of e over its in-frame pixels).  A tile with !(E <= tolerance) is refined
+ * to min(2n, spp_max) samples by one launch of the tile kernel (variant 8 on 4-wide scenes, 10 on threaded ones) over
+ * the list of such tiles, in tile order; a tile with E <= tolerance is never looked at again.  The host waits once
+ * per pass, for the 4-byte length of the list.  Because a pixel's samples come from its own RNG stream in order, a tile
+ * that ends with n samples holds the sums and RNG state of crt_renderer_render(n), bit for bit.  The estimate is biased:
+ * the stopping rule looks at the samples it stops, and a tile whose first spp_min samples miss a rare bright path is
+ * declared converged.  tolerance = +inf is the frame of spp_min samples (with tile errors), tolerance < 0 that of spp_max.
+ * reserved: 0; measurements only, no result depends on them: bit 0 lists the tiles of a pass by error, largest first
+ * (measured slower than tile order);
+ * bit 1 runs the first tiles of a pass's list at crt_renderer_set_critical_tiles' threshold (variant 8).
+ * stats_out (optional): samples = the sum over tiles of in-frame pixels x samples; passes = refinement launches;
+ * tiles_refined = tiles that got at least one; tiles_at_max = tiles that ended at spp_max; ms = HIP events round the call.
+ * Synchronous on return; device errors as crt_renderer_synchronize reports them.  Before any device work,
+ * CRT_ERR_INVALID_ARGUMENT: a null handle or options, spp_min < 2 or odd, spp_max < spp_min, a NaN tolerance, max_bounces
+ * < 1, scene and renderer on different devices, no camera; CRT_ERR_UNSUPPORTED: any render flag, a pixel shard other than
+ * (0, 1).  The state belongs to the renderer handle (W*H*3 floats and six words per tile), allocated by the first call
+ * and freed with the handle.  The listed tiles are compacted by one workgroup (and, for the self-test's list and bit 0, ordered by
+ * counting: listed^2 integer compares, DESIGN.md section 20 has the times).  These entries joined ABI version 3 after its first release. */
+typedef struct crt_adaptive_options { int32_t spp_min, spp_max; float tolerance; int32_t reserved; } crt_adaptive_options;
+typedef struct crt_adaptive_stats { uint64_t samples; uint32_t passes, tiles_refined, tiles_at_max; float ms; } crt_adaptive_stats;
+int crt_renderer_render_adaptive(crt_renderer* r, const crt_scene* scene, const crt_adaptive_options* options,
+                                 int max_bounces, unsigned flags, crt_adaptive_stats* stats_out, void* stream);
+/* crt_renderer_resolve with each pixel's own scale, 1.f / (float)(the samples its tile holds): a tile at n samples gets
+ * the bytes crt_renderer_resolve(1.f / n) gives a uniform n-spp frame.  After an adaptive render (or plan self-test). */
+int crt_renderer_resolve_adaptive(crt_renderer* r, void* stream);
+/* The per-tile state, tiles_y x tiles_x row-major: samples held, and the last error estimate (0 for a tile no plan
+ * looked at).  crt_renderer_read_adaptive_prev: the W*H*3 half-buffer sums.  CRT_ERR_INVALID_ARGUMENT before the
+ * renderer's first adaptive call.  They wait for the device. */
+int crt_renderer_read_tile_spp(crt_renderer* r, int32_t* host_out);
+int crt_renderer_read_tile_error(crt_renderer* r, float* host_out);
+int crt_renderer_read_adaptive_prev(crt_renderer* r, float* host_out);
+/* Self-test of one plan step (like crt_selftest_tile_schedule: no camera or scene): uploads sum (W*H*3, into the
+ * renderer's own linear buffer), prev (W*H*3) and tile_spp (tiles) into the renderer's buffers and runs the host
+ * function the loop calls with (n, next, tolerance).  list_out (capacity: tiles) gets the listed tiles, largest error
+ * first, *n_listed_out their number; tile errors, tile samples and prev are read with the three readers. */
+int crt_selftest_adaptive_plan(crt_renderer* r, const float* sum, const float* prev, const int32_t* tile_spp, int n,
+                               int next, float tolerance, uint32_t* list_out, uint32_t* n_listed_out);
 /* Host only, no GPU (like crt_scene_export_identity): the per-material rows the step kernel reads, n_materials x 8
  * floats = (code, 0, 0, 0) (payload): code (int bits) 0 lambertian, 1 metal, 2 dielectric, 3 light, 4 unknown type
  * (emits 0); payload (albedo.xyz, 0), (albedo.xyz, min(roughness, 1)), (ior, 1 / ior, r0(1 / ior), r0(ior)) with

@@ -626,6 +626,91 @@ class Renderer:
               "selftest_pixel_order")
         return self.schedule_buffer("order")
 
+    # ---- adaptive sampling (crt_hip.h crt_renderer_render_adaptive ff.)
+    def _tiles(self):
+        return (self.height + 7) // 8, (self.width + 7) // 8
+
+    def render_adaptive(self, scene: Scene, spp_min: int, spp_max: int, tolerance: float, max_bounces: int = 20,
+                        list_by_error: bool = False, critical_tiles: bool = False, stream=None) -> dict:
+        """A frame whose 8x8 tiles stop receiving samples once their error estimate is <= tolerance
+        (crt_renderer_render_adaptive): spp_min samples (even, >= 2) everywhere, then passes that double the samples
+        of the unconverged tiles up to spp_max.  A tile that ends at n samples holds render(n)'s sums and RNG state bit
+        for bit; tile_spp() says which n, resolve_adaptive() scales each tile by its own.  tolerance: +inf refines
+        nothing, a negative one everything; there is no default, and the result is biased (the rule looks at the samples
+        it stops).  Measurements only, no result depends on them: list_by_error True lists a pass's tiles largest error
+        first instead of in tile order, critical_tiles True runs a pass's first tiles at set_critical_tiles' threshold.
+        Synchronous.  Returns
+        {"samples", "passes", "tiles_refined", "tiles_at_max", "ms", "mean_spp"}."""
+        if not isinstance(scene, Scene):
+            raise ValueError("render_adaptive: scene must be a Scene")
+        for name, v in (("spp_min", spp_min), ("spp_max", spp_max), ("max_bounces", max_bounces)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"render_adaptive: {name} must be an int")
+        if spp_min < 2 or spp_min % 2:
+            raise ValueError("render_adaptive: spp_min must be even and >= 2")
+        if spp_max < spp_min or spp_max >= 1 << 31:
+            raise ValueError("render_adaptive: spp_max must be in [spp_min, 2^31)")
+        if max_bounces < 1:
+            raise ValueError("render_adaptive: max_bounces must be >= 1")
+        try:
+            tol = float(tolerance)
+        except (TypeError, ValueError):
+            raise ValueError("render_adaptive: tolerance must be a number") from None
+        if tol != tol:
+            raise ValueError("render_adaptive: tolerance is NaN")
+        if scene.device != self.device:
+            raise ValueError("render_adaptive: scene and renderer are on different devices")
+        o = _lib.AdaptiveOptions(int(spp_min), int(spp_max), tol, (1 if list_by_error else 0) | (2 if critical_tiles else 0))
+        s = _lib.AdaptiveStats()
+        check(_lib.require("crt_renderer_render_adaptive")(self.h, scene.h, C.byref(o), int(max_bounces), 0, C.byref(s),
+                                                           stream), "render_adaptive")
+        return {"samples": int(s.samples), "passes": int(s.passes), "tiles_refined": int(s.tiles_refined),
+                "tiles_at_max": int(s.tiles_at_max), "ms": float(s.ms),
+                "mean_spp": int(s.samples) / (self.width * self.height)}
+
+    def resolve_adaptive(self, stream=None):
+        """resolve() with each pixel's own scale, 1 / the samples its tile holds (crt_renderer_resolve_adaptive)."""
+        check(_lib.require("crt_renderer_resolve_adaptive")(self.h, stream), "resolve_adaptive")
+
+    def tile_spp(self) -> np.ndarray:
+        """Samples held per 8x8 tile, int32 [tiles_y, tiles_x], after an adaptive render."""
+        out = np.zeros(self._tiles(), np.int32)
+        check(_lib.require("crt_renderer_read_tile_spp")(self.h, _p(out)), "read_tile_spp")
+        return out
+
+    def tile_error(self) -> np.ndarray:
+        """The last error estimate per 8x8 tile, float32 [tiles_y, tiles_x], after an adaptive render."""
+        out = np.zeros(self._tiles(), np.float32)
+        check(_lib.require("crt_renderer_read_tile_error")(self.h, _p(out)), "read_tile_error")
+        return out
+
+    def adaptive_prev(self) -> np.ndarray:
+        """The half-buffer sums of the adaptive state, float32 [height, width, 3]."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        check(_lib.require("crt_renderer_read_adaptive_prev")(self.h, _p(out)), "read_adaptive_prev")
+        return out
+
+    def selftest_adaptive_plan(self, sum, prev, tile_spp, n: int, next: int, tolerance: float):
+        """One plan step on caller-supplied buffers (crt_selftest_adaptive_plan): sum and prev [height, width, 3]
+        float32, tile_spp [tiles_y, tiles_x] int32.  Returns the listed tiles, largest error first; tile_error(),
+        tile_spp(), adaptive_prev() and linear() hold the rest."""
+        ty, tx = self._tiles()
+        s, p = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (sum, prev))
+        t = np.ascontiguousarray(tile_spp, np.int32).reshape(-1)
+        if s.size != self.width * self.height * 3 or p.size != s.size:
+            raise ValueError("selftest_adaptive_plan: sum and prev must hold height * width * 3 floats")
+        if t.size != ty * tx:
+            raise ValueError("selftest_adaptive_plan: tile_spp must hold tiles_y * tiles_x entries")
+        if n < 2 or n % 2 or next < n:
+            raise ValueError("selftest_adaptive_plan: n must be even and >= 2, next >= n")
+        if float(tolerance) != float(tolerance):
+            raise ValueError("selftest_adaptive_plan: tolerance is NaN")
+        lst, cnt = np.zeros(ty * tx, np.uint32), C.c_uint32(0)
+        check(_lib.require("crt_selftest_adaptive_plan")(self.h, _p(s), _p(p), _p(t), int(n), int(next),
+                                                         C.c_float(float(tolerance)), _p(lst), C.byref(cnt)),
+              "selftest_adaptive_plan")
+        return lst[:cnt.value].copy()
+
     def set_leaf_carry(self, lanes: int, max_pairs: int):
         """Variant 8's leaf-pair carry: measured and removed in round 5; the library reports
         CRT_ERR_UNSUPPORTED, so this raises CrtError (profiles/r04c/leaf_carry.patch restores the kernels)."""

@@ -127,6 +127,15 @@ PATH_ACTIVE, PATH_ENDED = 0, 1       # crt_path.status
 class WavefrontStats(C.Structure):   # crt_hip.h crt_wavefront_stats
     _fields_ = [("rays", C.c_uint64), ("iterations", C.c_uint32), ("ms", C.c_float)]
 
+
+class AdaptiveOptions(C.Structure):  # crt_hip.h crt_adaptive_options
+    _fields_ = [("spp_min", C.c_int32), ("spp_max", C.c_int32), ("tolerance", C.c_float), ("reserved", C.c_int32)]
+
+
+class AdaptiveStats(C.Structure):    # crt_hip.h crt_adaptive_stats
+    _fields_ = [("samples", C.c_uint64), ("passes", C.c_uint32), ("tiles_refined", C.c_uint32),
+                ("tiles_at_max", C.c_uint32), ("ms", C.c_float)]
+
 # exported symbol lists (checked by tests against include/*.h)
 HIP_SYMBOLS = [
     "crt_abi_version", "crt_build_flags", "crt_last_error", "crt_device_count", "crt_scene_create", "crt_scene_create_ex", "crt_scene_get_stats", "crt_scene_compare", "crt_scene_compare_dump", "crt_scene_export",
@@ -152,9 +161,11 @@ HIP_SYMBOLS = [
     "crt_scene_trace_indirect_device", "crt_scene_path_advance_indirect_device", "crt_renderer_render_wavefront_queued",
     "crt_scene_path_finish_device", "crt_renderer_render_wavefront_finish",
     "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer",
+    "crt_renderer_render_adaptive", "crt_renderer_resolve_adaptive", "crt_renderer_read_tile_spp",
+    "crt_renderer_read_tile_error", "crt_renderer_read_adaptive_prev", "crt_selftest_adaptive_plan",
 ]
 # Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, the
-# schedule self-tests, then the path finish): bound when the loaded
+# schedule self-tests, the path finish, then adaptive sampling): bound when the loaded
 # library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
 # require() otherwise.
 OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
@@ -162,7 +173,9 @@ OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_devi
                     "crt_scene_trace_indirect_device", "crt_scene_path_advance_indirect_device",
                     "crt_renderer_render_wavefront_queued",
                     "crt_scene_path_finish_device", "crt_renderer_render_wavefront_finish",
-                    "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer")
+                    "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer",
+                    "crt_renderer_render_adaptive", "crt_renderer_resolve_adaptive", "crt_renderer_read_tile_spp",
+                    "crt_renderer_read_tile_error", "crt_renderer_read_adaptive_prev", "crt_selftest_adaptive_plan")
 
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
@@ -264,6 +277,11 @@ def hip():
             "crt_selftest_tile_schedule": ([P, P, i32, i32, i32, i32, i32, P], i32),
             "crt_selftest_pixel_order": ([P, i32, P, i32, i32], i32),
             "crt_selftest_schedule_buffer": ([P, i32, P, C.c_int64, P], i32),
+            "crt_renderer_render_adaptive": ([P, P, P, i32, C.c_uint, P, P], i32),
+            "crt_renderer_resolve_adaptive": ([P, P], i32),
+            "crt_renderer_read_tile_spp": ([P, P], i32), "crt_renderer_read_tile_error": ([P, P], i32),
+            "crt_renderer_read_adaptive_prev": ([P, P], i32),
+            "crt_selftest_adaptive_plan": ([P, P, P, P, i32, i32, f32, P, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):

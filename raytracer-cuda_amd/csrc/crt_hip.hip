@@ -3217,8 +3217,10 @@ struct crt_renderer {
     float rcp_w = 1.f, rcp_h = 1.f; // RN(1 / width), RN(1 / height)
     int fast_uv = 0;               // next_ray divides by uv_div (verified for this size at creation, uv_div_mismatches)
     struct WavefrontScratch* wavefront = nullptr;   // crt_renderer_render_wavefront: batches of the handle, allocated on first use (crt_paths.h)
+    struct AdaptiveState* adaptive = nullptr;       // crt_renderer_render_adaptive: per-tile state of the handle, allocated on first use (crt_adaptive.h)
 };
 void crtx_free_wavefront_scratch(crt_renderer* R);
+void crtx_free_adaptive_state(crt_renderer* R);
 
 namespace {
 int use_device(int dev) {
@@ -3674,6 +3676,7 @@ void crt_renderer_destroy(crt_renderer* R) {
     if (R->d_tile_order) (void)hipFree(R->d_tile_order);
     if (R->d_rng_cache) (void)hipFree(R->d_rng_cache);
     crtx_free_wavefront_scratch(R);
+    crtx_free_adaptive_state(R);
     for (auto& slot : R->ring)
         for (hipEvent_t& ev : slot)
             if (ev) (void)hipEventDestroy(ev);
@@ -4722,3 +4725,4 @@ int crt_selftest_schedule_buffer(crt_renderer* R, int which, uint32_t* out, int6
 // because they instantiate the traversal's device functions above (traverse_step4, trace, trace4, ray_spheres).
 #include "crt_trace.h"
 #include "crt_paths.h"
+#include "crt_adaptive.h"

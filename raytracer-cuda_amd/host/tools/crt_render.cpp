@@ -3,7 +3,12 @@
 // write it as PNG or binary PPM by extension (rows flipped like WindowManager::drawFrame's flipVertically).
 //
 //   crt_render [-w W] [-h H] [-spp N] [-seed S] [-o out.ppm] [-pos x y z] [-fov deg] [-bvh reference|rebuilt]
-//              [-leaf N] [-sbvh] [-aov depth|normal|object] model.obj...   (-sbvh: rebuilt tree with spatial splits)
+//              [-leaf N] [-sbvh] [-aov depth|normal|object] [-adaptive TOL [-spp-min N]] model.obj...
+//   (-sbvh: rebuilt tree with spatial splits)
+//
+// -adaptive TOL: adaptive sampling (crt_renderer_render_adaptive): every pixel gets -spp-min samples (default 16, even),
+// then only the 8x8 tiles whose error estimate exceeds TOL are refined, up to -spp samples; the JSON line gains samples,
+// passes, tiles_at_max and mean_spp (samples per pixel of the frame).
 //
 // -aov: instead of a frame, one ray per pixel through the pixel centre (CRT::RayQuery::centreRays: Camera::getRay with
 // u = (x + 0.5) / W, v = (y + 0.5) / H, lens offset 0) and an RGBA8 image of the closest hit, rows as for frames:
@@ -47,7 +52,9 @@ static std::vector<uint8_t> aovImage(const std::string& aov, const std::vector<c
 
 int main(int argc, char** argv) {
     try {
-        int W = 2560, spp = 1;
+        int W = 2560, spp = 1, sppMin = 16;
+        bool adaptive = false;
+        float tolerance = 0.f;
         int H = -1;
         unsigned long long seed = 41;
         float fov = 80.0f, aperture = 0.000001f;
@@ -62,6 +69,8 @@ int main(int argc, char** argv) {
             if (a == "-w") { need(1); W = std::atoi(argv[++i]); }
             else if (a == "-h") { need(1); H = std::atoi(argv[++i]); }
             else if (a == "-spp") { need(1); spp = std::atoi(argv[++i]); }
+            else if (a == "-spp-min") { need(1); sppMin = std::atoi(argv[++i]); }
+            else if (a == "-adaptive") { need(1); adaptive = true; tolerance = (float)std::atof(argv[++i]); }
             else if (a == "-seed") { need(1); seed = std::strtoull(argv[++i], nullptr, 10); }
             else if (a == "-o") { need(1); out = argv[++i]; }
             else if (a == "-fov") { need(1); fov = (float)std::atof(argv[++i]); }
@@ -112,6 +121,23 @@ int main(int argc, char** argv) {
         scene.initializeScene(config, renderer.getRandState());
         auto t1 = std::chrono::steady_clock::now();
         renderer.updateCamera(camera);
+        if (adaptive) {
+            const crt_adaptive_options ao{sppMin, spp, tolerance, 0};
+            crt_adaptive_stats as{};
+            CRT_CHECK(crt_renderer_render_adaptive(renderer.handle(), scene.getBVHNodes(), &ao, 20, 0u, &as, nullptr));
+            CRT_CHECK(crt_renderer_resolve_adaptive(renderer.handle(), nullptr));
+            CRT_CHECK(crt_renderer_synchronize(renderer.handle(), nullptr));
+            auto t2 = std::chrono::steady_clock::now();
+            std::vector<uint8_t> img = renderer.readImage();
+            CRT::writeImage(out, img.data(), W, H, true);
+            std::printf("{\"width\": %d, \"height\": %d, \"spp\": %d, \"spp_min\": %d, \"tolerance\": %g, \"samples\": %llu, "
+                        "\"passes\": %u, \"tiles_at_max\": %u, \"mean_spp\": %.4f, \"setup_s\": %.4f, \"frame_s\": %.4f, "
+                        "\"adaptive_ms\": %.3f, \"out\": \"%s\"}\n",
+                        W, H, spp, sppMin, (double)tolerance, (unsigned long long)as.samples, as.passes, as.tiles_at_max,
+                        (double)as.samples / ((double)W * H), std::chrono::duration<double>(t1 - t0).count(),
+                        std::chrono::duration<double>(t2 - t1).count(), as.ms, out.c_str());
+            return EXIT_SUCCESS;
+        }
         renderer.render(scene.getBVHNodes(), scene.getWorld());
         auto t2 = std::chrono::steady_clock::now();
         crt_work_counters c{};
