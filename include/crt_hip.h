@@ -467,6 +467,80 @@ int crt_renderer_read_adaptive_prev(crt_renderer* r, float* host_out);
  * first, *n_listed_out their number; tile errors, tile samples and prev are read with the three readers. */
 int crt_selftest_adaptive_plan(crt_renderer* r, const float* sum, const float* prev, const int32_t* tile_spp, int n,
                                int next, float tolerance, uint32_t* list_out, uint32_t* n_listed_out);
+/* ---- denoiser (no reference counterpart; DESIGN.md "Denoiser") ----
+ * The edge-avoiding a-trous wavelet filter of Dammertz, Sewtz, Hanika and Lensch (HPG 2010), guided by first-hit buffers.
+ *
+ * crt_renderer_compute_guides: one record of 8 floats per pixel of the renderer's frame, (normal.xyz, t) (position.xyz,
+ * key), from three steps on `stream`: a kernel writes the pixel-centre rays (CRT::RayQuery::centreRays' operations:
+ * u = ((float)x + 0.5f) / (float)W, v = ((float)y + 0.5f) / (float)H, dir = ((lower_left + u * horizontal) + v *
+ * vertical) - origin, the camera's origin, lens offset 0, tmax = +inf); crt_scene_trace_device traces them with
+ * trace_opts (NULL = defaults) into a hit buffer of the handle; a pack kernel fills the records: normal and t are the
+ * crt_hit's own (the outward geometric normal, not flipped), position = o + t * d (a multiply, then an add), key = object
+ * as int bits; a miss is t = -1, normal and position 0, key = 0x7fffffff.  No RNG state is consumed and no sum is touched.
+ * The guides stay valid until the camera, the scene or the frame size changes; that is the caller's duty.  Asynchronous.
+ * Before any device work, CRT_ERR_INVALID_ARGUMENT: null handles, scene and renderer on different devices, no camera;
+ * CRT_ERR_UNSUPPORTED: a pixel shard other than (0, 1).
+ *
+ * crt_renderer_denoise: c_0 = scale * sum per channel (CRT_DENOISE_TILE_SCALE: scale = 1.f / (float)tile_spp[tile] as
+ * crt_renderer_resolve_adaptive forms it, `scale` is ignored; without adaptive state CRT_ERR_INVALID_ARGUMENT).  Iteration
+ * i = 0 .. iterations - 1 has stride s = 1 << i and maps c_i to c_{i+1}; the last one is the handle's `denoised` buffer
+ * (W*H*3 floats).  The sums, the RNG state and the RGBA8 buffer are not touched.  Everything is f32, uncontracted, division
+ * correctly rounded:
+ *   h = (1/16, 1/4, 3/8, 1/4, 1/16), k(dy, dx) = h[dy + 2] * h[dx + 2] (exact constants).
+ *   Host side, per call: inv_n = 1.f / (sigma_normal * sigma_normal), inv_x likewise from sigma_position, inv_c likewise
+ *   from sigma_color for iteration 0, then inv_c = inv_c * 4.f after every iteration.  A term whose sigma is +inf is off:
+ *   it is not computed and contributes +0.
+ *   Per pixel p the taps q = (x + dx s, y + dy s), dy = -2 .. 2 outer, dx = -2 .. 2 inner; the centre in its place with
+ *   w = 1 and nothing computed.  Any other tap is skipped if it lies outside the frame, if key(q) != key(p), or if
+ *   !(X < 80.f); else w = exp_neg(X).  X = (dc * inv_c + dn * inv_n) + dx_ * inv_x with each d = ((a.x - b.x)^2 +
+ *   (a.y - b.y)^2) + (a.z - b.z)^2 over c_i(p), c_i(q) / the normals / the positions.  Per tap kw = k * w;
+ *   acc.c = acc.c + kw * q.c per channel; sw = sw + kw.  c_{i+1}(p) = acc / sw per channel (sw >= 9/64).  A skipped tap is
+ *   not multiplied in: with the colour term on, a NaN or infinite neighbour (X is NaN or inf) never spreads and a NaN
+ *   centre stays a NaN of that pixel alone.
+ *   exp_neg(X), 0 <= X < 80: k = rintf(X * 0x1.715476p+0f); r = (X - k * 0.693359375f) - k * -0x1.bd0106p-13f; t = -r;
+ *   p = ((((((C6 t + C5) t + C4) t + C3) t + 0.5f) t + 1.f) t + 1.f, C6 = 0x1.6c16c2p-10f, C5 = 0x1.111112p-7f,
+ *   C4 = 0x1.555556p-5f, C3 = 0x1.555556p-3f, every * and + a separate operation; the result is the float whose bits
+ *   are bits(p) - ((int)k << 23).  exp_neg(0) = 1; the relative error against exp is at most 2.5e-7.
+ * There are no default sigmas: their scale depends on the scene.  flags bit 31 (CRT_DENOISE_DIRECT_ONLY) is a measurement
+ * switch: every iteration through the direct kernel (one lane per pixel, taps from global memory) instead of the tiled
+ * one (rows staged in LDS) at the strides where that one is used; the bits are the same.
+ * stats_out (optional): guides_ms = HIP events round the last crt_renderer_compute_guides, filter_ms = round this call's
+ * launches, iterations = those run, pixels_hit = the pixels whose guide is a hit (0 after crt_selftest_denoise's upload).
+ * With stats_out the call waits for its last launch; without, it is asynchronous.  Before any device work,
+ * CRT_ERR_INVALID_ARGUMENT: a null handle or options, iterations outside 0..8, a sigma that is NaN, <= 0, or outside
+ * [2^-50, 2^50] and not +inf, unknown flag bits, reserved != 0, a scale that is NaN or <= 0 when no tile scale is asked
+ * for, no guides computed yet; CRT_ERR_UNSUPPORTED: a pixel shard other than (0, 1).
+ * The state belongs to the renderer handle, is allocated by the first crt_renderer_compute_guides (or self-test) and
+ * freed with the handle: 140 bytes per pixel (rays 32, hits 32, guides 32, two colour buffers of 16-byte rows 32, denoised
+ * 12) and one word per 64 pixels.  These entries joined ABI version 3 after its first release. */
+#define CRT_DENOISE_TILE_SCALE 1u
+#define CRT_DENOISE_DIRECT_ONLY 0x80000000u
+typedef struct crt_denoise_options {
+    int32_t iterations;                 /* 1..8; 0 = 5 */
+    float sigma_color, sigma_normal, sigma_position;   /* each in [2^-50, 2^50], or +inf = that term off */
+    uint32_t flags;                     /* CRT_DENOISE_TILE_SCALE 1u; bit 31: measurement switch */
+    int32_t reserved;
+} crt_denoise_options;
+typedef struct crt_denoise_stats { float guides_ms, filter_ms; uint32_t iterations, pixels_hit; } crt_denoise_stats;
+int crt_renderer_compute_guides(crt_renderer* r, const crt_scene* scene, const crt_trace_options* trace_opts, void* stream);
+int crt_renderer_denoise(crt_renderer* r, const crt_denoise_options* o, float scale, crt_denoise_stats* stats_out, void* stream);
+/* writeColor of the denoised buffer with scale 1 into the RGBA8 buffer (crt_renderer_resolve's kernel). */
+int crt_renderer_resolve_denoised(crt_renderer* r, void* stream);
+/* W*H*3 floats / W*H*8 floats; they wait for the device.  CRT_ERR_INVALID_ARGUMENT before the first denoise / guides. */
+int crt_renderer_read_denoised(crt_renderer* r, float* host_out);
+int crt_renderer_read_guides(crt_renderer* r, float* host_out);
+/* Per launch of the last crt_renderer_denoise that had a stats pointer (it records an event after every launch; without
+ * one it records none): out9[0] = the kernel that forms c_0, out9[1 + i] = iteration i, 0 for iterations not run.
+ * Waits for that call's last launch.  CRT_ERR_INVALID_ARGUMENT when there was no such call. */
+int crt_renderer_denoise_iteration_ms(crt_renderer* r, float* out9);
+/* The denoised buffer on the device (W*H*3 floats), NULL before the handle's denoiser state exists. */
+float* crt_renderer_denoised_device_ptr(crt_renderer* r);
+/* Self-test of the filter (like crt_selftest_adaptive_plan: no camera or scene): uploads color (W*H*3, into the
+ * renderer's own linear buffer, taken with scale 1) and guides (W*H*8) into the renderer's buffers, runs the host
+ * function crt_renderer_denoise calls on the null stream and reads the result into out (W*H*3).  The tile scale flag is
+ * CRT_ERR_INVALID_ARGUMENT here. */
+int crt_selftest_denoise(crt_renderer* r, const float* color, const float* guides, const crt_denoise_options* options,
+                         float* out);
 /* Host only, no GPU (like crt_scene_export_identity): the per-material rows the step kernel reads, n_materials x 8
  * floats = (code, 0, 0, 0) (payload): code (int bits) 0 lambertian, 1 metal, 2 dielectric, 3 light, 4 unknown type
  * (emits 0); payload (albedo.xyz, 0), (albedo.xyz, min(roughness, 1)), (ior, 1 / ior, r0(1 / ior), r0(ior)) with

@@ -711,6 +711,110 @@ class Renderer:
               "selftest_adaptive_plan")
         return lst[:cnt.value].copy()
 
+    # ---- denoiser (crt_hip.h crt_renderer_compute_guides ff.)
+    def compute_guides(self, scene: Scene, stream=None, **trace_options):
+        """The first-hit guide buffers of this renderer's camera over `scene` (crt_renderer_compute_guides): pixel-centre
+        rays, Scene.trace's closest hits, and one record (normal.xyz, t, position.xyz, key) per pixel on the device.
+        trace_options: keywords of Scene.trace (mode, grid_waves, stack_lds, refill_threshold).  Consumes no RNG state,
+        touches no sums; valid until the camera, the scene or the frame size changes.  Asynchronous."""
+        if not isinstance(scene, Scene):
+            raise ValueError("compute_guides: scene must be a Scene")
+        if scene.device != self.device:
+            raise ValueError("compute_guides: scene and renderer are on different devices")
+        unknown = set(trace_options) - {"mode", "grid_waves", "stack_lds", "refill_threshold"}
+        if unknown:
+            raise ValueError(f"compute_guides: unknown trace option {sorted(unknown)[0]}")
+        o = Scene._trace_options(**dict(dict(mode=0, grid_waves=0, stack_lds=0, refill_threshold=0), **trace_options))
+        check(_lib.require("crt_renderer_compute_guides")(self.h, scene.h, C.byref(o), stream), "compute_guides")
+
+    def guides(self) -> np.ndarray:
+        """The guide records, float32 [height, width, 8]: normal.xyz, t (-1: a miss), position.xyz, key (the object
+        index as int bits, 0x7fffffff for a miss: read it through .view(np.int32))."""
+        out = np.zeros((self.height, self.width, 8), np.float32)
+        check(_lib.require("crt_renderer_read_guides")(self.h, _p(out)), "read_guides")
+        return out
+
+    @staticmethod
+    def _denoise_options(who, sigma_color, sigma_normal, sigma_position, iterations, tile_scale, direct_only):
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations <= 8:
+            raise ValueError(f"{who}: iterations must be an int in 1..8")
+        sig = []
+        for name, v in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_position", sigma_position)):
+            try:
+                f = float(np.float32(v))
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: {name} must be a number") from None
+            if not (f == float("inf") or 2.0 ** -50 <= f <= 2.0 ** 50):
+                raise ValueError(f"{who}: {name} must be in [2^-50, 2^50] or +inf (that term off)")
+            sig.append(f)
+        flags = (_lib.DENOISE_TILE_SCALE if tile_scale else 0) | (_lib.DENOISE_DIRECT_ONLY if direct_only else 0)
+        return _lib.DenoiseOptions(int(iterations), sig[0], sig[1], sig[2], flags, 0)
+
+    def denoise(self, sigma_color, sigma_normal, sigma_position, iterations: int = 5, scale=None, tile_scale: bool = False,
+                direct_only: bool = False, stream=None) -> dict:
+        """The edge-avoiding a-trous filter over scale * the sums, guided by compute_guides' buffers
+        (crt_renderer_denoise; crt_hip.h states every operation).  The sigmas have no defaults: their scale depends on
+        the scene; float("inf") switches a term off.  scale: what resolve() would take, e.g. pixel_sample_scale(spp);
+        tile_scale True (after render_adaptive) takes 1 / each tile's own sample count instead.  The result is
+        denoised(); the sums, the RNG state and rgba8() are untouched.  direct_only: a measurement switch, the same
+        bits through the direct kernel alone.  Synchronous.
+        Returns {"guides_ms", "filter_ms", "iterations", "pixels_hit"}."""
+        o = self._denoise_options("denoise", sigma_color, sigma_normal, sigma_position, iterations, tile_scale, direct_only)
+        if tile_scale:
+            if scale is not None:
+                raise ValueError("denoise: scale and tile_scale exclude each other")
+            sc = 1.0
+        else:
+            try:
+                sc = float(np.float32(scale))
+            except (TypeError, ValueError):
+                raise ValueError("denoise: scale must be a number (or tile_scale=True)") from None
+            if not sc > 0:
+                raise ValueError("denoise: scale must be > 0")
+        s = _lib.DenoiseStats()
+        check(_lib.require("crt_renderer_denoise")(self.h, C.byref(o), C.c_float(sc), C.byref(s), stream), "denoise")
+        return {"guides_ms": float(s.guides_ms), "filter_ms": float(s.filter_ms), "iterations": int(s.iterations),
+                "pixels_hit": int(s.pixels_hit)}
+
+    def denoise_iteration_ms(self) -> dict:
+        """The last denoise()'s launches, timed one by one (crt_renderer_denoise_iteration_ms): {"input_ms": the kernel
+        that forms scale * sums, "iteration_ms": [one per iteration run, stride 1 << i]}."""
+        out = np.zeros(9, np.float32)
+        check(_lib.require("crt_renderer_denoise_iteration_ms")(self.h, _p(out)), "denoise_iteration_ms")
+        n = int(np.flatnonzero(out[1:] > 0).max(initial=-1)) + 1
+        return {"input_ms": float(out[0]), "iteration_ms": [float(v) for v in out[1:1 + n]]}
+
+    def denoised(self) -> np.ndarray:
+        """The last denoise()'s frame, float32 [height, width, 3], linear."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        check(_lib.require("crt_renderer_read_denoised")(self.h, _p(out)), "read_denoised")
+        return out
+
+    def resolve_denoised(self, stream=None):
+        """resolve(1.0) of the denoised frame into rgba8() (crt_renderer_resolve_denoised)."""
+        check(_lib.require("crt_renderer_resolve_denoised")(self.h, stream), "resolve_denoised")
+
+    def denoised_device_ptr(self) -> int:
+        """The denoised frame on the device (height * width * 3 floats) for torch interop; 0 before compute_guides."""
+        fn = _lib.require("crt_renderer_denoised_device_ptr")
+        return fn(self.h) or 0
+
+    def selftest_denoise(self, color, guides, sigma_color, sigma_normal, sigma_position, iterations: int = 5,
+                         direct_only: bool = False) -> np.ndarray:
+        """The filter on caller-supplied buffers (crt_selftest_denoise): color [height, width, 3] float32 (it replaces
+        the sums), guides [height, width, 8] float32 (key as int bits).  Returns the filtered frame."""
+        o = self._denoise_options("selftest_denoise", sigma_color, sigma_normal, sigma_position, iterations, False,
+                                  direct_only)
+        c = np.ascontiguousarray(color, np.float32).reshape(-1)
+        g = np.ascontiguousarray(guides, np.float32).reshape(-1)
+        if c.size != self.width * self.height * 3:
+            raise ValueError("selftest_denoise: color must hold height * width * 3 floats")
+        if g.size != self.width * self.height * 8:
+            raise ValueError("selftest_denoise: guides must hold height * width * 8 floats")
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        check(_lib.require("crt_selftest_denoise")(self.h, _p(c), _p(g), C.byref(o), _p(out)), "selftest_denoise")
+        return out
+
     def set_leaf_carry(self, lanes: int, max_pairs: int):
         """Variant 8's leaf-pair carry: measured and removed in round 5; the library reports
         CRT_ERR_UNSUPPORTED, so this raises CrtError (profiles/r04c/leaf_carry.patch restores the kernels)."""

@@ -136,6 +136,20 @@ class AdaptiveStats(C.Structure):    # crt_hip.h crt_adaptive_stats
     _fields_ = [("samples", C.c_uint64), ("passes", C.c_uint32), ("tiles_refined", C.c_uint32),
                 ("tiles_at_max", C.c_uint32), ("ms", C.c_float)]
 
+
+class DenoiseOptions(C.Structure):   # crt_hip.h crt_denoise_options
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class DenoiseStats(C.Structure):     # crt_hip.h crt_denoise_stats
+    _fields_ = [("guides_ms", C.c_float), ("filter_ms", C.c_float), ("iterations", C.c_uint32),
+                ("pixels_hit", C.c_uint32)]
+
+
+DENOISE_TILE_SCALE = 1               # crt_denoise_options.flags
+DENOISE_DIRECT_ONLY = 0x80000000     # measurement switch: every iteration through the direct kernel
+
 # exported symbol lists (checked by tests against include/*.h)
 HIP_SYMBOLS = [
     "crt_abi_version", "crt_build_flags", "crt_last_error", "crt_device_count", "crt_scene_create", "crt_scene_create_ex", "crt_scene_get_stats", "crt_scene_compare", "crt_scene_compare_dump", "crt_scene_export",
@@ -163,9 +177,12 @@ HIP_SYMBOLS = [
     "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer",
     "crt_renderer_render_adaptive", "crt_renderer_resolve_adaptive", "crt_renderer_read_tile_spp",
     "crt_renderer_read_tile_error", "crt_renderer_read_adaptive_prev", "crt_selftest_adaptive_plan",
+    "crt_renderer_compute_guides", "crt_renderer_denoise", "crt_renderer_resolve_denoised",
+    "crt_renderer_read_denoised", "crt_renderer_read_guides", "crt_renderer_denoised_device_ptr", "crt_selftest_denoise",
+    "crt_renderer_denoise_iteration_ms",
 ]
 # Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, the
-# schedule self-tests, the path finish, then adaptive sampling): bound when the loaded
+# schedule self-tests, the path finish, adaptive sampling, then the denoiser): bound when the loaded
 # library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
 # require() otherwise.
 OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
@@ -175,7 +192,10 @@ OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_devi
                     "crt_scene_path_finish_device", "crt_renderer_render_wavefront_finish",
                     "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer",
                     "crt_renderer_render_adaptive", "crt_renderer_resolve_adaptive", "crt_renderer_read_tile_spp",
-                    "crt_renderer_read_tile_error", "crt_renderer_read_adaptive_prev", "crt_selftest_adaptive_plan")
+                    "crt_renderer_read_tile_error", "crt_renderer_read_adaptive_prev", "crt_selftest_adaptive_plan",
+                    "crt_renderer_compute_guides", "crt_renderer_denoise", "crt_renderer_resolve_denoised",
+                    "crt_renderer_read_denoised", "crt_renderer_read_guides", "crt_renderer_denoised_device_ptr",
+                    "crt_selftest_denoise", "crt_renderer_denoise_iteration_ms")
 
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
@@ -282,6 +302,13 @@ def hip():
             "crt_renderer_read_tile_spp": ([P, P], i32), "crt_renderer_read_tile_error": ([P, P], i32),
             "crt_renderer_read_adaptive_prev": ([P, P], i32),
             "crt_selftest_adaptive_plan": ([P, P, P, P, i32, i32, f32, P, P], i32),
+            "crt_renderer_compute_guides": ([P, P, P, P], i32),
+            "crt_renderer_denoise": ([P, P, f32, P, P], i32),
+            "crt_renderer_resolve_denoised": ([P, P], i32),
+            "crt_renderer_read_denoised": ([P, P], i32), "crt_renderer_read_guides": ([P, P], i32),
+            "crt_renderer_denoised_device_ptr": ([P], P),
+            "crt_selftest_denoise": ([P, P, P, P, P], i32),
+            "crt_renderer_denoise_iteration_ms": ([P, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):

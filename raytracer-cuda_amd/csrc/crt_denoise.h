@@ -1,0 +1,465 @@
+// Edge-avoiding a-trous denoiser (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) guided by first-hit
+// buffers.  Included by crt_hip.hip after crt_adaptive.h.  Nothing here is used by a render kernel.
+//
+// Guides: one record of two 16-B rows per pixel, (normal.xyz, t) (position.xyz, key), from the pixel-centre rays
+// (RayQuery::centreRays' operations), crt_scene_trace_device and a pack kernel.  The filter: one launch per iteration
+// i with stride 1 << i over colours kept as one 16-B row per pixel, ping-ponging between two buffers; the last
+// iteration writes the W*H*3 `denoised` buffer.  Every operation is f32 and uncontracted and in the order the header
+// states, so tests/helpers/denoise_model.py reproduces the bits.  Two kernels share one tap loop (denoise_taps): the
+// direct one loads every tap from global memory, the tiled one from rows staged in LDS.
+#pragma once
+
+// The renderer's denoiser state: allocated by the first guides / self-test call, freed with the handle.
+// Bytes per pixel: rays 32 + hits 32 (compute_guides only) + guides 32 + two colour buffers 2 x 16 + denoised 12 = 140,
+// plus one word per 64 pixels (the hit counts).
+struct DenoiseState {
+    float4* rays = nullptr;         // 2 rows per pixel: the pixel-centre rays (crt_ray)
+    float4* hits = nullptr;         // 2 rows per pixel: their closest hits (crt_hit)
+    float4* guides = nullptr;       // 2 rows per pixel: (normal.xyz, t) (position.xyz, key)
+    float4* col[2] = {nullptr, nullptr};   // 1 row per pixel: (c.xyz, 0)
+    float* denoised = nullptr;      // W*H*3
+    uint32_t* wave_hits = nullptr;  // per 64 pixels: how many of them hit something
+    bool have_guides = false;       // guides hold a compute_guides or self-test result
+    bool counted = false;           // wave_hits belongs to the guides (compute_guides; not the self-test's upload)
+    bool have_denoised = false;
+    bool timed_guides = false;
+    hipEvent_t g0 = nullptr, g1 = nullptr, f0 = nullptr, f1 = nullptr;
+    hipEvent_t it[9] = {};          // a timed run: after the input kernel, then after every iteration
+    bool lds_raised = false;        // the tiled kernel's dynamic LDS limit was raised for this device
+    int timed_iterations = 0;       // iterations of the last timed run (crt_renderer_denoise_iteration_ms), 0: none
+};
+
+constexpr int DENOISE_MISS_KEY = 0x7fffffff;
+
+struct GuideRayParams {
+    crt_camera_desc cam;
+    int width, height;
+    float4* __restrict__ rays;
+};
+
+// RayQuery::centreRays on the device, operation for operation: u = ((float)x + 0.5f) / (float)W, v likewise (the
+// build's correctly rounded division), dir = ((lower_left + u * horizontal) + v * vertical) - origin, lens offset 0.
+__global__ __launch_bounds__(256) void crt_guide_rays_kernel(GuideRayParams G) {
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= G.width * G.height) return;
+    const int x = pix % G.width, y = pix / G.width;
+    const float u = ((float)x + 0.5f) / (float)G.width, v = ((float)y + 0.5f) / (float)G.height;
+    float d[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        d[a] = ((G.cam.lower_left[a] + u * G.cam.horizontal[a]) + v * G.cam.vertical[a]) - G.cam.origin[a];
+    G.rays[2 * (size_t)pix] = make_float4(G.cam.origin[0], G.cam.origin[1], G.cam.origin[2], __builtin_inff());
+    G.rays[2 * (size_t)pix + 1] = make_float4(d[0], d[1], d[2], 0.f);
+}
+
+// The guide record of every pixel from its ray and its crt_hit: the hit's own (geometric, unflipped) normal and t,
+// position = o + t * d (V3's operators: a multiply, then an add), key = object; a miss is (0, 0, 0, -1) (0, 0, 0,
+// DENOISE_MISS_KEY).  Lane 0 of every wave stores how many of its pixels hit (no atomics).
+__global__ __launch_bounds__(256) void crt_guide_pack_kernel(const float4* __restrict__ rays, const float4* __restrict__ hits,
+                                                             float4* __restrict__ guides, uint32_t* __restrict__ wave_hits,
+                                                             int n_pix) {
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    bool hit = false;
+    if (pix < n_pix) {
+        const float4 ha = hits[2 * (size_t)pix], hb = hits[2 * (size_t)pix + 1];
+        float4 g0 = make_float4(0.f, 0.f, 0.f, -1.f), g1 = make_float4(0.f, 0.f, 0.f, __int_as_float(DENOISE_MISS_KEY));
+        hit = !(ha.x < 0.f);
+        if (hit) {
+            const float4 ra = rays[2 * (size_t)pix], rb = rays[2 * (size_t)pix + 1];
+            const V3 p = v3(ra.x, ra.y, ra.z) + ha.x * v3(rb.x, rb.y, rb.z);
+            g0 = make_float4(hb.x, hb.y, hb.z, ha.x);
+            g1 = make_float4(p.x, p.y, p.z, ha.y);      // ha.y: the object index as int bits
+        }
+        guides[2 * (size_t)pix] = g0;
+        guides[2 * (size_t)pix + 1] = g1;
+    }
+    const unsigned long long m = __ballot(hit);
+    if ((threadIdx.x & 63) == 0 && pix < n_pix) wave_hits[pix >> 6] = (uint32_t)__popcll(m);   // pix: the wave's first
+}
+
+// c0 = scale * sum per channel, as a 16-B row; tile_spp non-null: scale = 1.f / (float)tile_spp[tile], as
+// crt_resolve_adaptive_kernel forms it.
+__global__ __launch_bounds__(256) void crt_denoise_input_kernel(const float* __restrict__ sum, float4* __restrict__ col,
+                                                                const int32_t* __restrict__ tile_spp, int width, int n_pix,
+                                                                int tiles_x, float scale) {
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= n_pix) return;
+    if (tile_spp) {
+        const int x = pix % width, y = pix / width;
+        scale = 1.f / (float)tile_spp[(y >> 3) * tiles_x + (x >> 3)];
+    }
+    col[pix] = make_float4(scale * sum[3 * (size_t)pix], scale * sum[3 * (size_t)pix + 1], scale * sum[3 * (size_t)pix + 2], 0.f);
+}
+
+struct DenoiseParams {
+    const float4* __restrict__ in;      // c_i, 1 row per pixel
+    const float4* __restrict__ guides;  // 2 rows per pixel
+    float4* __restrict__ out;           // c_{i+1} as rows, or null on the last iteration
+    float* __restrict__ out3;           // the last iteration's output, 3 floats per pixel
+    int width, height, stride;
+    float inv_c, inv_n, inv_x;          // 1 / sigma^2 of this iteration
+    int on_c, on_n, on_x;               // 0: the term is off (sigma = +inf), never computed
+};
+
+// exp(-X) for 0 <= X < 80 (crt_hip.h has the steps): k = rint(X * log2 e); r = X - k ln 2 in two parts, the first
+// product exact; a degree-6 polynomial in t = -r; 2^-k by an integer subtraction from the exponent field.
+__device__ __forceinline__ float denoise_exp_neg(float X) {
+    const float k = rintf(X * 0x1.715476p+0f);
+    const float r = (X - k * 0.693359375f) - k * -0x1.bd0106p-13f;
+    const float t = -r;
+    float p = 0x1.6c16c2p-10f * t + 0x1.111112p-7f;
+    p = p * t + 0x1.555556p-5f;
+    p = p * t + 0x1.555556p-3f;
+    p = p * t + 0.5f;
+    p = p * t + 1.f;
+    p = p * t + 1.f;
+    return __int_as_float(__float_as_int(p) - ((int)k << 23));
+}
+
+__device__ __forceinline__ float denoise_dist2(float4 a, float4 b) {
+    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// The tap loop both kernels share.  Pixel (x, y) with its own rows (c, g0, g1); fetch(dy, dx, qx, qy, which) returns
+// row `which` (0 colour, 1 guide row 0, 2 guide row 1) of tap q = (x + dx s, y + dy s), and is only called for a q
+// inside the frame.  dy outer, dx inner, the centre in its place with w = 1; a tap outside the frame, with another
+// key, or with !(X < 80) is skipped.
+template <class Fetch>
+__device__ __forceinline__ float4 denoise_taps(const DenoiseParams& D, int x, int y, float4 c, float4 g0, float4 g1,
+                                               Fetch fetch) {
+    constexpr float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    const int key = __float_as_int(g1.w);
+    float ax = 0.f, ay = 0.f, az = 0.f, sw = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const float k = h[dy + 2] * h[dx + 2];
+            if (dy == 0 && dx == 0) {
+                ax = ax + k * c.x; ay = ay + k * c.y; az = az + k * c.z;
+                sw = sw + k;
+                continue;
+            }
+            const int qx = x + dx * D.stride, qy = y + dy * D.stride;
+            if (qx < 0 || qx >= D.width || qy < 0 || qy >= D.height) continue;
+            const float4 q1 = fetch(dy, dx, qx, qy, 2);
+            if (__float_as_int(q1.w) != key) continue;
+            const float4 qc = fetch(dy, dx, qx, qy, 0);
+            float xc = 0.f, xn = 0.f, xx = 0.f;
+            if (D.on_c) xc = denoise_dist2(c, qc) * D.inv_c;
+            if (D.on_n) xn = denoise_dist2(g0, fetch(dy, dx, qx, qy, 1)) * D.inv_n;
+            if (D.on_x) xx = denoise_dist2(g1, q1) * D.inv_x;
+            const float X = (xc + xn) + xx;
+            if (!(X < 80.f)) continue;
+            const float kw = k * denoise_exp_neg(X);
+            ax = ax + kw * qc.x; ay = ay + kw * qc.y; az = az + kw * qc.z;
+            sw = sw + kw;
+        }
+    }
+    return make_float4(ax / sw, ay / sw, az / sw, 0.f);
+}
+
+__device__ __forceinline__ void denoise_store(const DenoiseParams& D, size_t pix, float4 o) {
+    if (D.out3) { D.out3[3 * pix] = o.x; D.out3[3 * pix + 1] = o.y; D.out3[3 * pix + 2] = o.z; }
+    else D.out[pix] = o;
+}
+
+// The direct kernel: one lane per pixel, every tap from global memory.  The yardstick; any stride.
+constexpr int DENOISE_BX = 64, DENOISE_DIRECT_BY = 4;
+__global__ __launch_bounds__(DENOISE_BX * DENOISE_DIRECT_BY) void crt_denoise_direct_kernel(DenoiseParams D) {
+    const int x = blockIdx.x * DENOISE_BX + threadIdx.x, y = blockIdx.y * DENOISE_DIRECT_BY + threadIdx.y;
+    if (x >= D.width || y >= D.height) return;
+    const size_t pix = (size_t)y * D.width + x;
+    const float4 c = D.in[pix], g0 = D.guides[2 * pix], g1 = D.guides[2 * pix + 1];
+    const float4 o = denoise_taps(D, x, y, c, g0, g1, [&](int, int, int qx, int qy, int which) {
+        const size_t q = (size_t)qy * D.width + qx;      // inside the frame: the tap loop checked
+        return which == 0 ? D.in[q] : D.guides[2 * q + (which - 1)];
+    });
+    denoise_store(D, pix, o);
+}
+
+// The tiled kernel: a workgroup of 64 x 8 lanes filters the pixels x0 .. x0 + 63 of the 8 rows y = r + s (8 g + j),
+// j = 0 .. 7, of one residue class r of y modulo the stride s: in an a-trous pass only those rows interact.  It stages
+// the 12 rows j = -2 .. 9 over x0 - 2 s .. x0 + 63 + 2 s in LDS, as three arrays of 16-B rows (colour, guide row 0,
+// guide row 1) with coalesced 16-B loads along x, then runs the shared tap loop out of LDS.  LDS: 12 (64 + 4 s) 48 B,
+// dynamic: 39,168 B at s = 1, 55,296 B at s = 8 and 73,728 B at s = 16, the largest stride it is launched with
+// (DENOISE_TILED_MAX_STRIDE: measured faster than the direct kernel at s = 1 .. 16 and slower at s = 32, where a block
+// fetches 12 x 192 rows for 512 pixels).  Above 64 KiB the host raises the kernel's dynamic LDS limit once.
+// Entries outside the frame are never written and never read (the tap loop's frame test comes before the fetch).
+constexpr int DENOISE_TY = 8, DENOISE_ROWS = DENOISE_TY + 4;
+constexpr int DENOISE_TILED_MAX_STRIDE = 16;
+__global__ __launch_bounds__(DENOISE_BX * DENOISE_TY) void crt_denoise_tiled_kernel(DenoiseParams D, int groups) {
+    extern __shared__ float4 denoise_lds[];
+    const int s = D.stride, cols = DENOISE_BX + 4 * s, n = DENOISE_ROWS * cols;
+    float4* l_c = denoise_lds;
+    float4* l_g0 = denoise_lds + n;
+    float4* l_g1 = denoise_lds + 2 * n;
+    const int r = blockIdx.y / groups, g = blockIdx.y % groups;     // blockIdx.y < s * groups
+    const int x0 = blockIdx.x * DENOISE_BX, j0 = g * DENOISE_TY;
+    const int tid = threadIdx.y * DENOISE_BX + threadIdx.x;
+    for (int i = tid; i < n; i += DENOISE_BX * DENOISE_TY) {
+        const int row = i / cols, col = i - row * cols;
+        const int qx = x0 - 2 * s + col, qy = r + s * (j0 + row - 2);
+        if (qx >= 0 && qx < D.width && qy >= 0 && qy < D.height) {
+            const size_t q = (size_t)qy * D.width + qx;
+            l_c[i] = D.in[q];
+            l_g0[i] = D.guides[2 * q];
+            l_g1[i] = D.guides[2 * q + 1];
+        }
+    }
+    __syncthreads();
+    const int x = x0 + threadIdx.x, y = r + s * (j0 + threadIdx.y);
+    if (x >= D.width || y >= D.height) return;
+    const int at = (threadIdx.y + 2) * cols + threadIdx.x + 2 * s;
+    const float4 o = denoise_taps(D, x, y, l_c[at], l_g0[at], l_g1[at], [&](int dy, int dx, int, int, int which) {
+        const int q = at + dy * cols + dx * s;           // row j + dy, column x + dx s of the staged block
+        return which == 0 ? l_c[q] : which == 1 ? l_g0[q] : l_g1[q];
+    });
+    denoise_store(D, (size_t)y * D.width + x, o);
+}
+
+void crtx_free_denoise_state(crt_renderer* R) {
+    DenoiseState* N = R->denoise;
+    if (!N) return;
+    if (N->rays) (void)hipFree(N->rays);
+    if (N->hits) (void)hipFree(N->hits);
+    if (N->guides) (void)hipFree(N->guides);
+    if (N->col[0]) (void)hipFree(N->col[0]);
+    if (N->col[1]) (void)hipFree(N->col[1]);
+    if (N->denoised) (void)hipFree(N->denoised);
+    if (N->wave_hits) (void)hipFree(N->wave_hits);
+    for (hipEvent_t e : {N->g0, N->g1, N->f0, N->f1})
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : N->it)
+        if (e) (void)hipEventDestroy(e);
+    delete N;
+    R->denoise = nullptr;
+}
+
+namespace {
+
+int denoise_state(crt_renderer* R, DenoiseState** out) {
+    if (!R->denoise) {
+        DenoiseState* N = new (std::nothrow) DenoiseState;
+        if (!N) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+        R->denoise = N;   // whatever is allocated below is freed with the handle
+        const size_t n_pix = (size_t)R->width * R->height;
+        HIP_TRY(hipMalloc((void**)&N->rays, n_pix * 32));
+        HIP_TRY(hipMalloc((void**)&N->hits, n_pix * 32));
+        HIP_TRY(hipMalloc((void**)&N->guides, n_pix * 32));
+        HIP_TRY(hipMalloc((void**)&N->col[0], n_pix * 16));
+        HIP_TRY(hipMalloc((void**)&N->col[1], n_pix * 16));
+        HIP_TRY(hipMalloc((void**)&N->denoised, n_pix * 12));
+        HIP_TRY(hipMalloc((void**)&N->wave_hits, ((n_pix + 63) / 64) * 4));
+        HIP_TRY(hipMemset(N->denoised, 0, n_pix * 12));
+        HIP_TRY(hipEventCreate(&N->g0));
+        HIP_TRY(hipEventCreate(&N->g1));
+        HIP_TRY(hipEventCreate(&N->f0));
+        HIP_TRY(hipEventCreate(&N->f1));
+        for (hipEvent_t& e : N->it) HIP_TRY(hipEventCreate(&e));
+    }
+    DenoiseState* N = R->denoise;
+    if (!N->rays || !N->hits || !N->guides || !N->col[0] || !N->col[1] || !N->denoised || !N->wave_hits || !N->it[8])
+        return set_error(CRT_ERR_OUT_OF_MEMORY, "the denoiser state of this renderer could not be allocated");
+    *out = N;
+    return CRT_OK;
+}
+
+// The checks of the options alone (no handle, no device).
+int denoise_check_options(const crt_denoise_options* o, const char* who) {
+    const std::string w = who;
+    if (!o) return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": null options");
+    if (o->iterations < 0 || o->iterations > 8) return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": iterations must be 0..8 (0 = 5)");
+    const float sig[3] = {o->sigma_color, o->sigma_normal, o->sigma_position};
+    const char* name[3] = {"sigma_color", "sigma_normal", "sigma_position"};
+    for (int k = 0; k < 3; ++k)
+        if (!(sig[k] == __builtin_inff() || (sig[k] >= 0x1p-50f && sig[k] <= 0x1p50f)))
+            return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": " + name[k] + " must be in [2^-50, 2^50] or +inf (that term off)");
+    if (o->flags & ~(CRT_DENOISE_TILE_SCALE | CRT_DENOISE_DIRECT_ONLY))
+        return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": unknown flag bits");
+    if (o->reserved != 0) return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": reserved must be 0");
+    return CRT_OK;
+}
+
+// The filter on `st`: c0 from the sums, then one launch per iteration.  The handle's guides and options were checked.
+// timed: an event after every launch (crt_renderer_denoise_iteration_ms); the caller waits for f1 before reading them.
+int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, float scale, hipStream_t st, bool timed) {
+    const int W = R->width, H = R->height, n_pix = W * H;
+    const int iterations = o->iterations ? o->iterations : 5;
+    const bool tile_scale = (o->flags & CRT_DENOISE_TILE_SCALE) != 0, direct_only = (o->flags & CRT_DENOISE_DIRECT_ONLY) != 0;
+    HIP_TRY(hipEventRecord(N->f0, st));
+    hipLaunchKernelGGL(crt_denoise_input_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, R->d_sum, N->col[0],
+                       tile_scale ? R->adaptive->tile_spp : nullptr, W, n_pix, (W + 7) / 8, scale);
+    N->timed_iterations = 0;
+    if (timed) HIP_TRY(hipEventRecord(N->it[0], st));
+    DenoiseParams D{};
+    D.guides = N->guides;
+    D.width = W; D.height = H;
+    const float inf = __builtin_inff();
+    D.on_c = o->sigma_color != inf; D.on_n = o->sigma_normal != inf; D.on_x = o->sigma_position != inf;
+    D.inv_c = D.on_c ? 1.f / (o->sigma_color * o->sigma_color) : 0.f;
+    D.inv_n = D.on_n ? 1.f / (o->sigma_normal * o->sigma_normal) : 0.f;
+    D.inv_x = D.on_x ? 1.f / (o->sigma_position * o->sigma_position) : 0.f;
+    for (int i = 0; i < iterations; ++i) {
+        const bool last = i == iterations - 1;
+        D.in = N->col[i & 1];
+        D.out = last ? nullptr : N->col[(i + 1) & 1];
+        D.out3 = last ? N->denoised : nullptr;
+        D.stride = 1 << i;
+        if (!direct_only && D.stride <= DENOISE_TILED_MAX_STRIDE) {
+            const int s = D.stride, rows = (H + s - 1) / s;                   // the rows of residue class 0, the longest
+            const int groups = (rows + DENOISE_TY - 1) / DENOISE_TY;
+            const size_t lds = (size_t)DENOISE_ROWS * (DENOISE_BX + 4 * s) * 48;
+            if (lds > 65536 && !N->lds_raised) {
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(crt_denoise_tiled_kernel),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            DENOISE_ROWS * (DENOISE_BX + 4 * DENOISE_TILED_MAX_STRIDE) * 48));
+                N->lds_raised = true;
+            }
+            hipLaunchKernelGGL(crt_denoise_tiled_kernel, dim3((W + DENOISE_BX - 1) / DENOISE_BX, s * groups),
+                               dim3(DENOISE_BX, DENOISE_TY), lds, st, D, groups);
+        } else {
+            hipLaunchKernelGGL(crt_denoise_direct_kernel,
+                               dim3((W + DENOISE_BX - 1) / DENOISE_BX, (H + DENOISE_DIRECT_BY - 1) / DENOISE_DIRECT_BY),
+                               dim3(DENOISE_BX, DENOISE_DIRECT_BY), 0, st, D);
+        }
+        if (D.on_c) D.inv_c = D.inv_c * 4.f;             // the colour sigma halves per level
+        if (timed) HIP_TRY(hipEventRecord(N->it[i + 1], st));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(N->f1, st));
+    if (timed) N->timed_iterations = iterations;
+    N->have_denoised = true;
+    return CRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crt_renderer_compute_guides(crt_renderer* R, const crt_scene* S, const crt_trace_options* opts, void* stream) {
+    if (!R || !S) return set_error(CRT_ERR_INVALID_ARGUMENT, "compute guides: null argument");
+    if (S->device != R->device)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "compute guides: scene and renderer on different devices");
+    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, "compute guides: camera not set");
+    if (R->tile_shards > 1) return set_error(CRT_ERR_UNSUPPORTED, "compute guides: a pixel shard other than (0, 1)");
+    HIP_TRY(hipSetDevice(R->device));
+    hipStream_t st = (hipStream_t)stream;
+    DenoiseState* N = nullptr;
+    if (int rc = denoise_state(R, &N)) return rc;
+    const int n_pix = R->width * R->height;
+    N->have_guides = N->counted = false;
+    HIP_TRY(hipEventRecord(N->g0, st));
+    GuideRayParams G{};
+    G.cam = R->cam; G.width = R->width; G.height = R->height; G.rays = N->rays;
+    hipLaunchKernelGGL(crt_guide_rays_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, G);
+    HIP_TRY(hipGetLastError());
+    if (int rc = crt_scene_trace_device(S, reinterpret_cast<const crt_ray*>(N->rays), n_pix, opts,
+                                        reinterpret_cast<crt_hit*>(N->hits), nullptr, 0u, stream))
+        return rc;
+    hipLaunchKernelGGL(crt_guide_pack_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, N->rays, N->hits, N->guides,
+                       N->wave_hits, n_pix);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(N->g1, st));
+    N->have_guides = N->counted = N->timed_guides = true;
+    return CRT_OK;
+}
+
+int crt_renderer_denoise(crt_renderer* R, const crt_denoise_options* o, float scale, crt_denoise_stats* stats_out,
+                         void* stream) {
+    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "denoise: null renderer");
+    if (int rc = denoise_check_options(o, "denoise")) return rc;
+    const bool tile_scale = (o->flags & CRT_DENOISE_TILE_SCALE) != 0;
+    if (!tile_scale && !(scale > 0.f)) return set_error(CRT_ERR_INVALID_ARGUMENT, "denoise: scale must be > 0");
+    if (tile_scale && (!R->adaptive || !R->adaptive->tile_spp))
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "denoise: the tile scale needs an adaptive render on this renderer");
+    if (R->tile_shards > 1) return set_error(CRT_ERR_UNSUPPORTED, "denoise: a pixel shard other than (0, 1)");
+    if (!R->denoise || !R->denoise->have_guides)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "denoise: no guides computed yet (crt_renderer_compute_guides)");
+    HIP_TRY(hipSetDevice(R->device));
+    DenoiseState* N = nullptr;
+    if (int rc = denoise_state(R, &N)) return rc;
+    if (int rc = denoise_run(R, N, o, scale, (hipStream_t)stream, stats_out != nullptr)) return rc;
+    if (stats_out) {
+        crt_denoise_stats s{};
+        s.iterations = (uint32_t)(o->iterations ? o->iterations : 5);
+        HIP_TRY(hipEventSynchronize(N->f1));
+        HIP_TRY(hipEventElapsedTime(&s.filter_ms, N->f0, N->f1));
+        if (N->timed_guides) {
+            HIP_TRY(hipEventSynchronize(N->g1));
+            HIP_TRY(hipEventElapsedTime(&s.guides_ms, N->g0, N->g1));
+        }
+        if (N->counted) {
+            std::vector<uint32_t> w(((size_t)R->width * R->height + 63) / 64);
+            HIP_TRY(hipMemcpy(w.data(), N->wave_hits, w.size() * 4, hipMemcpyDeviceToHost));
+            for (uint32_t c : w) s.pixels_hit += c;
+        }
+        *stats_out = s;
+    }
+    return CRT_OK;
+}
+
+int crt_renderer_resolve_denoised(crt_renderer* R, void* stream) {
+    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "null renderer");
+    if (!R->denoise || !R->denoise->have_denoised)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "resolve denoised: no denoised frame on this renderer yet");
+    HIP_TRY(hipSetDevice(R->device));
+    const int n = R->width * R->height;
+    hipLaunchKernelGGL(crt_resolve_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, R->denoise->denoised,
+                       R->d_rgba, n, 1.f);
+    HIP_TRY(hipGetLastError());
+    return CRT_OK;
+}
+
+int crt_renderer_read_denoised(crt_renderer* R, float* out) {
+    if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "read denoised: null argument");
+    if (!R->denoise || !R->denoise->have_denoised)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "read denoised: no denoised frame on this renderer yet");
+    return read_dev(R, out, R->denoise->denoised, (size_t)R->width * R->height * 12);
+}
+
+int crt_renderer_read_guides(crt_renderer* R, float* out) {
+    if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "read guides: null argument");
+    if (!R->denoise || !R->denoise->have_guides)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "read guides: no guides computed yet (crt_renderer_compute_guides)");
+    return read_dev(R, out, R->denoise->guides, (size_t)R->width * R->height * 32);
+}
+
+int crt_renderer_denoise_iteration_ms(crt_renderer* R, float* out9) {
+    if (!R || !out9) return set_error(CRT_ERR_INVALID_ARGUMENT, "denoise iteration ms: null argument");
+    if (!R->denoise || !R->denoise->timed_iterations)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "denoise iteration ms: no denoise with a stats pointer on this renderer yet");
+    DenoiseState* N = R->denoise;
+    HIP_TRY(hipSetDevice(R->device));
+    HIP_TRY(hipEventSynchronize(N->f1));
+    for (int k = 0; k < 9; ++k) out9[k] = 0.f;
+    HIP_TRY(hipEventElapsedTime(&out9[0], N->f0, N->it[0]));
+    for (int i = 0; i < N->timed_iterations; ++i) HIP_TRY(hipEventElapsedTime(&out9[i + 1], N->it[i], N->it[i + 1]));
+    return CRT_OK;
+}
+
+float* crt_renderer_denoised_device_ptr(crt_renderer* R) { return R && R->denoise ? R->denoise->denoised : nullptr; }
+
+// The filter on caller-supplied buffers: the renderer's own state and the host function crt_renderer_denoise calls, on
+// the null stream.  The colours go into the renderer's linear buffer and are taken with scale 1 (1.f * c = c).
+int crt_selftest_denoise(crt_renderer* R, const float* color, const float* guides, const crt_denoise_options* o, float* out) {
+    if (!R || !color || !guides || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "selftest denoise: null argument");
+    if (int rc = denoise_check_options(o, "selftest denoise")) return rc;
+    if (o->flags & CRT_DENOISE_TILE_SCALE)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, "selftest denoise: takes the colours as they are (no tile scale)");
+    HIP_TRY(hipSetDevice(R->device));
+    DenoiseState* N = nullptr;
+    if (int rc = denoise_state(R, &N)) return rc;
+    const size_t n_pix = (size_t)R->width * R->height;
+    HIP_TRY(hipMemcpy(R->d_sum, color, n_pix * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->guides, guides, n_pix * 32, hipMemcpyHostToDevice));
+    N->have_guides = true;
+    N->counted = N->timed_guides = false;
+    if (int rc = denoise_run(R, N, o, 1.f, 0, false)) return rc;
+    HIP_TRY(hipStreamSynchronize(0));
+    HIP_TRY(hipMemcpy(out, N->denoised, n_pix * 12, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+}  // extern "C"

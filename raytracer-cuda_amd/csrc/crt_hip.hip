@@ -3218,9 +3218,11 @@ struct crt_renderer {
     int fast_uv = 0;               // next_ray divides by uv_div (verified for this size at creation, uv_div_mismatches)
     struct WavefrontScratch* wavefront = nullptr;   // crt_renderer_render_wavefront: batches of the handle, allocated on first use (crt_paths.h)
     struct AdaptiveState* adaptive = nullptr;       // crt_renderer_render_adaptive: per-tile state of the handle, allocated on first use (crt_adaptive.h)
+    struct DenoiseState* denoise = nullptr;         // crt_renderer_compute_guides / crt_renderer_denoise: guides and colour buffers of the handle, allocated on first use (crt_denoise.h)
 };
 void crtx_free_wavefront_scratch(crt_renderer* R);
 void crtx_free_adaptive_state(crt_renderer* R);
+void crtx_free_denoise_state(crt_renderer* R);
 
 namespace {
 int use_device(int dev) {
@@ -3677,6 +3679,7 @@ void crt_renderer_destroy(crt_renderer* R) {
     if (R->d_rng_cache) (void)hipFree(R->d_rng_cache);
     crtx_free_wavefront_scratch(R);
     crtx_free_adaptive_state(R);
+    crtx_free_denoise_state(R);
     for (auto& slot : R->ring)
         for (hipEvent_t& ev : slot)
             if (ev) (void)hipEventDestroy(ev);
@@ -4726,3 +4729,4 @@ int crt_selftest_schedule_buffer(crt_renderer* R, int which, uint32_t* out, int6
 #include "crt_trace.h"
 #include "crt_paths.h"
 #include "crt_adaptive.h"
+#include "crt_denoise.h"

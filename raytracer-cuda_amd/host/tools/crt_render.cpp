@@ -3,12 +3,18 @@
 // write it as PNG or binary PPM by extension (rows flipped like WindowManager::drawFrame's flipVertically).
 //
 //   crt_render [-w W] [-h H] [-spp N] [-seed S] [-o out.ppm] [-pos x y z] [-fov deg] [-bvh reference|rebuilt]
-//              [-leaf N] [-sbvh] [-aov depth|normal|object] [-adaptive TOL [-spp-min N]] model.obj...
+//              [-leaf N] [-sbvh] [-aov depth|normal|object] [-adaptive TOL [-spp-min N]]
+//              [-denoise SC:SN:SX [-denoise-iters N]] model.obj...
 //   (-sbvh: rebuilt tree with spatial splits)
 //
 // -adaptive TOL: adaptive sampling (crt_renderer_render_adaptive): every pixel gets -spp-min samples (default 16, even),
 // then only the 8x8 tiles whose error estimate exceeds TOL are refined, up to -spp samples; the JSON line gains samples,
 // passes, tiles_at_max and mean_spp (samples per pixel of the frame).
+//
+// -denoise SC:SN:SX: the frame through the edge-avoiding a-trous filter (crt_renderer_compute_guides,
+// crt_renderer_denoise, crt_renderer_resolve_denoised) with the colour, normal and position sigmas given (`inf` switches a
+// term off; there are no defaults), -denoise-iters iterations (default 5).  With -adaptive the filter takes each tile's own
+// scale.  The JSON line gains guides_ms and filter_ms.
 //
 // -aov: instead of a frame, one ray per pixel through the pixel centre (CRT::RayQuery::centreRays: Camera::getRay with
 // u = (x + 0.5) / W, v = (y + 0.5) / H, lens offset 0) and an RGBA8 image of the closest hit, rows as for frames:
@@ -26,6 +32,30 @@
 #include "crt/ImageIO.h"
 #include "crt/RayQuery.h"
 #include "crt/SceneManager.h"
+
+// "SC:SN:SX" -> three sigmas; "inf" is +infinity.
+static bool parseSigmas(const char* text, float out[3]) {
+    const char* p = text;
+    for (int k = 0; k < 3; ++k) {
+        char* end = nullptr;
+        out[k] = std::strtof(p, &end);
+        if (end == p || *end != (k < 2 ? ':' : '\0')) return false;
+        p = end + 1;
+    }
+    return true;
+}
+
+// The frame in the renderer's RGBA8 buffer becomes the denoised one; returns the stats.
+static crt_denoise_stats denoiseFrame(crt_renderer* r, const crt_scene* scene, const float sigma[3], int iterations,
+                                      bool tileScale, float scale) {
+    const crt_denoise_options o{iterations, sigma[0], sigma[1], sigma[2], tileScale ? CRT_DENOISE_TILE_SCALE : 0u, 0};
+    crt_denoise_stats s{};
+    CRT_CHECK(crt_renderer_compute_guides(r, scene, nullptr, nullptr));
+    CRT_CHECK(crt_renderer_denoise(r, &o, scale, &s, nullptr));
+    CRT_CHECK(crt_renderer_resolve_denoised(r, nullptr));
+    CRT_CHECK(crt_renderer_synchronize(r, nullptr));
+    return s;
+}
 
 static uint8_t aovByte(float c) { return (uint8_t)(int)(255.0f * c + 0.5f); }
 
@@ -55,6 +85,9 @@ int main(int argc, char** argv) {
         int W = 2560, spp = 1, sppMin = 16;
         bool adaptive = false;
         float tolerance = 0.f;
+        bool denoise = false;
+        float sigma[3] = {0.f, 0.f, 0.f};
+        int denoiseIters = 5;
         int H = -1;
         unsigned long long seed = 41;
         float fov = 80.0f, aperture = 0.000001f;
@@ -71,6 +104,15 @@ int main(int argc, char** argv) {
             else if (a == "-spp") { need(1); spp = std::atoi(argv[++i]); }
             else if (a == "-spp-min") { need(1); sppMin = std::atoi(argv[++i]); }
             else if (a == "-adaptive") { need(1); adaptive = true; tolerance = (float)std::atof(argv[++i]); }
+            else if (a == "-denoise") {
+                need(1);
+                denoise = true;
+                if (!parseSigmas(argv[++i], sigma)) {
+                    std::fprintf(stderr, "-denoise takes SC:SN:SX (numbers or inf)\n");
+                    return 2;
+                }
+            }
+            else if (a == "-denoise-iters") { need(1); denoiseIters = std::atoi(argv[++i]); }
             else if (a == "-seed") { need(1); seed = std::strtoull(argv[++i], nullptr, 10); }
             else if (a == "-o") { need(1); out = argv[++i]; }
             else if (a == "-fov") { need(1); fov = (float)std::atof(argv[++i]); }
@@ -127,18 +169,26 @@ int main(int argc, char** argv) {
             CRT_CHECK(crt_renderer_render_adaptive(renderer.handle(), scene.getBVHNodes(), &ao, 20, 0u, &as, nullptr));
             CRT_CHECK(crt_renderer_resolve_adaptive(renderer.handle(), nullptr));
             CRT_CHECK(crt_renderer_synchronize(renderer.handle(), nullptr));
+            crt_denoise_stats ds{};
+            if (denoise) ds = denoiseFrame(renderer.handle(), scene.getBVHNodes(), sigma, denoiseIters, true, 1.f);
             auto t2 = std::chrono::steady_clock::now();
             std::vector<uint8_t> img = renderer.readImage();
             CRT::writeImage(out, img.data(), W, H, true);
             std::printf("{\"width\": %d, \"height\": %d, \"spp\": %d, \"spp_min\": %d, \"tolerance\": %g, \"samples\": %llu, "
                         "\"passes\": %u, \"tiles_at_max\": %u, \"mean_spp\": %.4f, \"setup_s\": %.4f, \"frame_s\": %.4f, "
-                        "\"adaptive_ms\": %.3f, \"out\": \"%s\"}\n",
+                        "\"adaptive_ms\": %.3f, ",
                         W, H, spp, sppMin, (double)tolerance, (unsigned long long)as.samples, as.passes, as.tiles_at_max,
                         (double)as.samples / ((double)W * H), std::chrono::duration<double>(t1 - t0).count(),
-                        std::chrono::duration<double>(t2 - t1).count(), as.ms, out.c_str());
+                        std::chrono::duration<double>(t2 - t1).count(), as.ms);
+            if (denoise) std::printf("\"guides_ms\": %.3f, \"filter_ms\": %.3f, ", ds.guides_ms, ds.filter_ms);
+            std::printf("\"out\": \"%s\"}\n", out.c_str());
             return EXIT_SUCCESS;
         }
         renderer.render(scene.getBVHNodes(), scene.getWorld());
+        crt_denoise_stats ds{};
+        if (denoise)
+            ds = denoiseFrame(renderer.handle(), scene.getBVHNodes(), sigma, denoiseIters, false,
+                              camera.toDesc().pixel_sample_scale);
         auto t2 = std::chrono::steady_clock::now();
         crt_work_counters c{};
         CRT_CHECK(crt_renderer_get_counters(renderer.handle(), &c));
@@ -147,9 +197,11 @@ int main(int argc, char** argv) {
         double setup = std::chrono::duration<double>(t1 - t0).count();
         double frame = std::chrono::duration<double>(t2 - t1).count();
         std::printf("{\"width\": %d, \"height\": %d, \"spp\": %d, \"rays\": %llu, \"setup_s\": %.4f, \"frame_s\": %.4f, "
-                    "\"kernel_ms\": %.3f, \"mrays_per_s\": %.2f, \"out\": \"%s\"}\n",
+                    "\"kernel_ms\": %.3f, \"mrays_per_s\": %.2f, ",
                     W, H, spp, (unsigned long long)c.rays, setup, frame, crt_renderer_last_kernel_ms(renderer.handle()),
-                    c.rays / frame / 1e6, out.c_str());
+                    c.rays / frame / 1e6);
+        if (denoise) std::printf("\"guides_ms\": %.3f, \"filter_ms\": %.3f, ", ds.guides_ms, ds.filter_ms);
+        std::printf("\"out\": \"%s\"}\n", out.c_str());
         return EXIT_SUCCESS;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "Error: %s\n", e.what());
