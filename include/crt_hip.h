@@ -547,6 +547,10 @@ int crt_selftest_denoise(crt_renderer* r, const float* color, const float* guide
  * Schlick's r0(ri) = ((1 - ri) / (1 + ri))^2, (emission.xyz, 0), zeros -- the payloads of the render kernels' shading
  * records, from the same host function.  out == NULL: only *n_materials is set. */
 int crt_scene_export_shade_rows(const crt_scene_desc* desc, float* out, int64_t* n_materials);
+/* Debugging aid, no GPU needed: the device and pinned-host buffers the library holds in this process right now, over all
+ * handles and devices, and their bytes.  Equal values before and after a sequence of calls that ends with its handles
+ * destroyed mean the sequence released what it allocated, whatever other processes do on the device. */
+int crt_debug_live_allocations(int64_t* buffers, int64_t* bytes);
 
 /* ---- renderer (CUDARenderer) ---- */
 int  crt_renderer_create(int width, int height, int device, crt_renderer** out);

@@ -6,20 +6,6 @@
 // samples holds the sum and the RNG state of a uniform n-spp frame whatever schedule gave it those samples.
 #pragma once
 
-// The renderer's adaptive state: allocated by the first adaptive call, freed with the handle.
-struct AdaptiveState {
-    float* prev = nullptr;          // W*H*3: the sums after the first half of the samples a candidate tile holds
-    int32_t* tile_spp = nullptr;    // per tile: samples every pixel of the tile has received
-    float* tile_error = nullptr;    // per tile: the last error estimate
-    uint32_t* key = nullptr;        // per tile: 0 = not listed, else the error as an ordered integer
-    uint32_t* ctile = nullptr;      // the unconverged tiles of the last plan in tile order, n_tiles entries
-    uint32_t* ckey = nullptr;       // their keys
-    uint32_t* list = nullptr;       // the same tiles, largest error first
-    uint32_t* d_count = nullptr;    // their number
-    uint32_t* h_count = nullptr;    // pinned
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-};
-
 // One wave per tile, four tiles per workgroup.  Tiles with tile_spp != n are left alone (their key is 0).  Per pixel the
 // term of Dammertz et al.'s stopping condition from the two half buffers P = prev and Q = sum - prev, every operation f32,
 // uncontracted, the divisions and the square root correctly rounded (the build's flags); the tile's error is the xor
@@ -142,55 +128,37 @@ __global__ __launch_bounds__(256) void crt_resolve_adaptive_kernel(const float* 
     reinterpret_cast<uchar4*>(rgba)[pix] = o;
 }
 
-void crtx_free_adaptive_state(crt_renderer* R) {
-    AdaptiveState* A = R->adaptive;
-    if (!A) return;
-    if (A->prev) (void)hipFree(A->prev);
-    if (A->tile_spp) (void)hipFree(A->tile_spp);
-    if (A->tile_error) (void)hipFree(A->tile_error);
-    if (A->key) (void)hipFree(A->key);
-    if (A->ctile) (void)hipFree(A->ctile);
-    if (A->ckey) (void)hipFree(A->ckey);
-    if (A->list) (void)hipFree(A->list);
-    if (A->d_count) (void)hipFree(A->d_count);
-    if (A->h_count) (void)hipHostFree(A->h_count);
-    if (A->ev0) (void)hipEventDestroy(A->ev0);
-    if (A->ev1) (void)hipEventDestroy(A->ev1);
-    delete A;
-    R->adaptive = nullptr;
-}
-
 namespace {
 
 int adaptive_tiles(const crt_renderer* R) { return ((R->width + 7) / 8) * ((R->height + 7) / 8); }
 
 int adaptive_state(crt_renderer* R, AdaptiveState** out) {
     if (!R->adaptive) {
-        AdaptiveState* A = new (std::nothrow) AdaptiveState;
+        R->adaptive.reset(new (std::nothrow) AdaptiveState);   // whatever is allocated below is freed with the handle
+        AdaptiveState* A = R->adaptive.get();
         if (!A) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-        R->adaptive = A;   // whatever is allocated below is freed with the handle
         const size_t n_pix = (size_t)R->width * R->height, n_tiles = (size_t)adaptive_tiles(R);
-        HIP_TRY(hipMalloc((void**)&A->prev, n_pix * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&A->tile_spp, n_tiles * 4));
-        HIP_TRY(hipMalloc((void**)&A->tile_error, n_tiles * 4));
-        HIP_TRY(hipMalloc((void**)&A->key, n_tiles * 4));
-        HIP_TRY(hipMalloc((void**)&A->ctile, n_tiles * 4));
-        HIP_TRY(hipMalloc((void**)&A->ckey, n_tiles * 4));
-        HIP_TRY(hipMalloc((void**)&A->list, n_tiles * 4));
-        HIP_TRY(hipMalloc((void**)&A->d_count, 4));
-        HIP_TRY(hipHostMalloc((void**)&A->h_count, 4));
-        HIP_TRY(hipMemset(A->prev, 0, n_pix * 3 * sizeof(float)));
-        HIP_TRY(hipMemset(A->tile_spp, 0, n_tiles * 4));
-        HIP_TRY(hipMemset(A->tile_error, 0, n_tiles * 4));
-        HIP_TRY(hipMemset(A->list, 0xff, n_tiles * 4));
-        HIP_TRY(hipMemset(A->d_count, 0, 4));
-        HIP_TRY(hipEventCreate(&A->ev0));
-        HIP_TRY(hipEventCreate(&A->ev1));
+        HIP_TRY(A->prev.alloc(n_pix * 3));
+        HIP_TRY(A->tile_spp.alloc(n_tiles));
+        HIP_TRY(A->tile_error.alloc(n_tiles));
+        HIP_TRY(A->key.alloc(n_tiles));
+        HIP_TRY(A->ctile.alloc(n_tiles));
+        HIP_TRY(A->ckey.alloc(n_tiles));
+        HIP_TRY(A->list.alloc(n_tiles));
+        HIP_TRY(A->d_count.alloc(1));
+        HIP_TRY(A->h_count.alloc(1));
+        HIP_TRY(hipMemset(A->prev.get(), 0, n_pix * 3 * sizeof(float)));
+        HIP_TRY(hipMemset(A->tile_spp.get(), 0, n_tiles * 4));
+        HIP_TRY(hipMemset(A->tile_error.get(), 0, n_tiles * 4));
+        HIP_TRY(hipMemset(A->list.get(), 0xff, n_tiles * 4));
+        HIP_TRY(hipMemset(A->d_count.get(), 0, 4));
+        HIP_TRY(A->ev0.create());
+        HIP_TRY(A->ev1.create());
+        A->ready = true;
     }
-    AdaptiveState* A = R->adaptive;
-    if (!A->prev || !A->tile_spp || !A->tile_error || !A->key || !A->ctile || !A->ckey || !A->list || !A->d_count || !A->h_count || !A->ev1)
+    if (!R->adaptive->ready)
         return set_error(CRT_ERR_OUT_OF_MEMORY, "the adaptive state of this renderer could not be allocated");
-    *out = A;
+    *out = R->adaptive.get();
     return CRT_OK;
 }
 
@@ -199,15 +167,15 @@ int adaptive_state(crt_renderer* R, AdaptiveState** out) {
 int adaptive_plan(crt_renderer* R, AdaptiveState* A, hipStream_t st, int n, int next, float tolerance, bool by_error,
                   const uint32_t** list) {
     const int tiles_x = (R->width + 7) / 8, n_tiles = adaptive_tiles(R);
-    hipLaunchKernelGGL(crt_adaptive_plan_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, st, R->d_sum, A->prev, A->tile_spp,
-                       A->tile_error, A->key, R->width, R->height, tiles_x, n_tiles, n, next, tolerance);
-    hipLaunchKernelGGL(crt_adaptive_compact_kernel, dim3(1), dim3(ADAPT_COMPACT_THREADS), 0, st, A->key, n_tiles, A->ctile,
-                       A->ckey, A->d_count);
+    hipLaunchKernelGGL(crt_adaptive_plan_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, st, R->d_sum, A->prev.get(), A->tile_spp.get(),
+                       A->tile_error.get(), A->key.get(), R->width, R->height, tiles_x, n_tiles, n, next, tolerance);
+    hipLaunchKernelGGL(crt_adaptive_compact_kernel, dim3(1), dim3(ADAPT_COMPACT_THREADS), 0, st, A->key.get(), n_tiles, A->ctile.get(),
+                       A->ckey.get(), A->d_count.get());
     if (by_error)
-        hipLaunchKernelGGL(crt_adaptive_rank_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, A->ctile, A->ckey,
-                           A->d_count, n_tiles, A->list);
+        hipLaunchKernelGGL(crt_adaptive_rank_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, A->ctile.get(), A->ckey.get(),
+                           A->d_count.get(), n_tiles, A->list.get());
     HIP_TRY(hipGetLastError());
-    *list = by_error ? A->list : A->ctile;
+    *list = by_error ? A->list.get() : A->ctile.get();
     return CRT_OK;
 }
 
@@ -230,8 +198,8 @@ int adaptive_pass(crt_renderer* R, const crt_scene* S, hipStream_t st, const uin
         P.crit_threshold = R->crit_threshold;
     }
     {   // the render's slot of the timing ring, as crt_renderer_render takes it
-        hipEvent_t* slot = R->ring[R->n_timed % (CRT_TIMING_RING + 1)];
-        R->ev0 = slot[0]; R->ev_main = slot[1]; R->ev1 = slot[2];
+        const DevEvent* slot = R->ring[R->n_timed % (CRT_TIMING_RING + 1)];
+        R->ev0 = slot[0].get(); R->ev_main = slot[1].get(); R->ev1 = slot[2].get();
     }
     HIP_TRY(hipEventRecord(R->ev0, st));
     R->last_schedule[0] = R->last_schedule[2] = R->last_schedule[3] = 0.f;
@@ -271,30 +239,30 @@ int crt_renderer_render_adaptive(crt_renderer* R, const crt_scene* S, const crt_
     const int tiles_x = (R->width + 7) / 8, n_tiles = adaptive_tiles(R);
     if (!R->n_cus) HIP_TRY(hipDeviceGetAttribute(&R->n_cus, hipDeviceAttributeMultiprocessorCount, R->device));
     crt_adaptive_stats stats{};
-    HIP_TRY(hipEventRecord(A->ev0, st));
+    HIP_TRY(hipEventRecord(A->ev0.get(), st));
     // the first spp_min samples in two halves, so that prev holds the first half's sums
     if (int rc = crt_renderer_render(R, S, o->spp_min / 2, max_bounces, 0u, stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(A->prev, R->d_sum, n_pix * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(A->prev.get(), R->d_sum, n_pix * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (int rc = crt_renderer_render(R, S, o->spp_min / 2, max_bounces, CRT_RENDER_ACCUMULATE, stream)) return rc;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)A->tile_spp, o->spp_min, (size_t)n_tiles, st));
-    HIP_TRY(hipMemsetAsync(A->tile_error, 0, (size_t)n_tiles * 4, st));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)A->tile_spp.get(), o->spp_min, (size_t)n_tiles, st));
+    HIP_TRY(hipMemsetAsync(A->tile_error.get(), 0, (size_t)n_tiles * 4, st));
     for (int64_t n = o->spp_min; n < o->spp_max; n *= 2) {
         const int next = (int)std::min<int64_t>(2 * n, o->spp_max);
         const uint32_t* list = nullptr;
         if (int rc = adaptive_plan(R, A, st, (int)n, next, o->tolerance, (o->reserved & 1) != 0, &list)) return rc;
-        HIP_TRY(hipMemcpyAsync(A->h_count, A->d_count, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(A->h_count.get(), A->d_count.get(), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));      // the pass's one host wait
-        const int m = (int)std::min<uint32_t>(A->h_count[0], (uint32_t)n_tiles);
+        const int m = (int)std::min<uint32_t>(A->h_count.get()[0], (uint32_t)n_tiles);
         if (m == 0) break;
         if (int rc = adaptive_pass(R, S, st, list, m, next - (int)n, max_bounces, (o->reserved & 2) != 0)) return rc;
         ++stats.passes;
     }
-    HIP_TRY(hipEventRecord(A->ev1, st));
+    HIP_TRY(hipEventRecord(A->ev1.get(), st));
     std::vector<int32_t> spp((size_t)n_tiles);
-    HIP_TRY(hipMemcpyAsync(spp.data(), A->tile_spp, (size_t)n_tiles * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventSynchronize(A->ev1));
+    HIP_TRY(hipMemcpyAsync(spp.data(), A->tile_spp.get(), (size_t)n_tiles * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventSynchronize(A->ev1.get()));
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&stats.ms, A->ev0, A->ev1));
+    HIP_TRY(hipEventElapsedTime(&stats.ms, A->ev0.get(), A->ev1.get()));
     for (int t = 0; t < n_tiles; ++t) {
         const int w = std::min(8, R->width - (t % tiles_x) * 8), h = std::min(8, R->height - (t / tiles_x) * 8);
         stats.samples += (uint64_t)(w * h) * (uint64_t)spp[(size_t)t];
@@ -312,7 +280,7 @@ int crt_renderer_resolve_adaptive(crt_renderer* R, void* stream) {
     HIP_TRY(hipSetDevice(R->device));
     const int n = R->width * R->height;
     hipLaunchKernelGGL(crt_resolve_adaptive_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, R->d_sum,
-                       R->d_rgba, R->adaptive->tile_spp, R->width, n, (R->width + 7) / 8);
+                       R->d_rgba.get(), R->adaptive->tile_spp.get(), R->width, n, (R->width + 7) / 8);
     HIP_TRY(hipGetLastError());
     return CRT_OK;
 }
@@ -320,17 +288,17 @@ int crt_renderer_resolve_adaptive(crt_renderer* R, void* stream) {
 int crt_renderer_read_tile_spp(crt_renderer* R, int32_t* out) {
     if (!R || !R->adaptive || !R->adaptive->tile_spp)
         return set_error(CRT_ERR_INVALID_ARGUMENT, "read tile spp: no adaptive render on this renderer yet");
-    return read_dev(R, out, R->adaptive->tile_spp, (size_t)adaptive_tiles(R) * 4);
+    return read_dev(R, out, R->adaptive->tile_spp.get(), (size_t)adaptive_tiles(R) * 4);
 }
 int crt_renderer_read_tile_error(crt_renderer* R, float* out) {
     if (!R || !R->adaptive || !R->adaptive->tile_error)
         return set_error(CRT_ERR_INVALID_ARGUMENT, "read tile error: no adaptive render on this renderer yet");
-    return read_dev(R, out, R->adaptive->tile_error, (size_t)adaptive_tiles(R) * 4);
+    return read_dev(R, out, R->adaptive->tile_error.get(), (size_t)adaptive_tiles(R) * 4);
 }
 int crt_renderer_read_adaptive_prev(crt_renderer* R, float* out) {
     if (!R || !R->adaptive || !R->adaptive->prev)
         return set_error(CRT_ERR_INVALID_ARGUMENT, "read adaptive prev: no adaptive render on this renderer yet");
-    return read_dev(R, out, R->adaptive->prev, (size_t)R->width * R->height * 12);
+    return read_dev(R, out, R->adaptive->prev.get(), (size_t)R->width * R->height * 12);
 }
 
 // The plan on caller-supplied buffers: the renderer's own state and the host function the loop calls, on the null stream.
@@ -345,13 +313,13 @@ int crt_selftest_adaptive_plan(crt_renderer* R, const float* sum, const float* p
     if (int rc = adaptive_state(R, &A)) return rc;
     const size_t n_pix = (size_t)R->width * R->height, n_tiles = (size_t)adaptive_tiles(R);
     HIP_TRY(hipMemcpy(R->d_sum, sum, n_pix * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(A->prev, prev, n_pix * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(A->tile_spp, tile_spp, n_tiles * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(A->list, 0xff, n_tiles * 4));
+    HIP_TRY(hipMemcpy(A->prev.get(), prev, n_pix * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(A->tile_spp.get(), tile_spp, n_tiles * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(A->list.get(), 0xff, n_tiles * 4));
     const uint32_t* list = nullptr;
     if (int rc = adaptive_plan(R, A, 0, n, next, tolerance, true, &list)) return rc;
     HIP_TRY(hipStreamSynchronize(0));
-    HIP_TRY(hipMemcpy(n_listed_out, A->d_count, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_listed_out, A->d_count.get(), 4, hipMemcpyDeviceToHost));
     const size_t m = std::min<size_t>(*n_listed_out, n_tiles);
     if (m) HIP_TRY(hipMemcpy(list_out, list, m * 4, hipMemcpyDeviceToHost));
     return CRT_OK;

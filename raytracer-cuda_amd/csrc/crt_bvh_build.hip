@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "crt_hip.h"
+#include "crt_devmem.h"
 
 int crtx_set_error(int code, const std::string& msg);   // crt_hip.hip
 
@@ -643,14 +644,15 @@ __global__ void k_iota(uint32_t* __restrict__ perm, int* __restrict__ seg, int n
 
 inline unsigned blocks(size_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
 
-// RAII for the build's device allocations
-struct DeviceArena {
-    std::vector<void*> ptrs;
-    ~DeviceArena() { for (void* p : ptrs) (void)hipFree(p); }
+// The device arrays of one build: the kernels' argument structs and the ping-pong swaps hold plain pointers, the
+// buffers behind them live until the build returns.
+struct BuildArrays {
+    std::vector<DevBuf<char>> bufs;
     template <class T>
     hipError_t alloc(T** p, size_t count) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
+        bufs.emplace_back();
+        const hipError_t e = bufs.back().alloc(std::max<size_t>(count, 1) * sizeof(T));
+        *p = reinterpret_cast<T*>(bufs.back().get());
         return e;
     }
 };
@@ -678,12 +680,11 @@ extern "C" int crt_build_mesh_bvh(int device, const float* positions, uint32_t v
     BTRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return crtx_set_error(CRT_ERR_INVALID_ARGUMENT, "device ordinal out of range");
     BTRY(hipSetDevice(device));
-    DeviceArena A;
+    BuildArrays A;
     hipStream_t st = nullptr;
-    hipEvent_t e0, e1;
-    BTRY(hipEventCreate(&e0));
-    BTRY(hipEventCreate(&e1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
+    DevEvent e0, e1;
+    BTRY(e0.create());
+    BTRY(e1.create());
 
     // Mesh ctor box (unpadded expand over every slot; AABB() when there are none)
     float* d_v = nullptr;
@@ -691,7 +692,7 @@ extern "C" int crt_build_mesh_bvh(int device, const float* positions, uint32_t v
     if (vertex_count) BTRY(hipMemcpy(d_v, positions, (size_t)vertex_count * 12, hipMemcpyHostToDevice));
     uint32_t* d_box6 = nullptr;
     BTRY(A.alloc(&d_box6, 6));
-    BTRY(hipEventRecord(e0, st));
+    BTRY(hipEventRecord(e0.get(), st));
     {
         const uint32_t init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
         BTRY(hipMemcpyAsync(d_box6, init, sizeof init, hipMemcpyHostToDevice, st));
@@ -826,7 +827,7 @@ extern "C" int crt_build_mesh_bvh(int device, const float* positions, uint32_t v
     hipLaunchKernelGGL(k_emit, dim3(blocks(total)), dim3(256), 0, st, N, total, index_count, d_out);
     hipLaunchKernelGGL(k_permute, dim3(blocks(n)), dim3(256), 0, st, d_perm, d_idx, d_fm, d_idx_out, d_fm_out, n);
     BTRY(hipGetLastError());
-    BTRY(hipEventRecord(e1, st));
+    BTRY(hipEventRecord(e1.get(), st));
     uint32_t b6[6];
     BTRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
     BTRY(hipMemcpyAsync(b6, d_box6, sizeof b6, hipMemcpyDeviceToHost, st));
@@ -846,7 +847,7 @@ extern "C" int crt_build_mesh_bvh(int device, const float* positions, uint32_t v
                                    : (k < 3 ? INFINITY : -INFINITY);
     }
     *node_count = total;
-    if (build_ms) BTRY(hipEventElapsedTime(build_ms, e0, e1));
+    if (build_ms) BTRY(hipEventElapsedTime(build_ms, e0.get(), e1.get()));
     return CRT_OK;
 }
 
@@ -1341,7 +1342,7 @@ int crtx_build_sah_gpu(int device, const std::vector<crt_sah::Item>& items, int 
     BTRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return crtx_set_error(CRT_ERR_INVALID_ARGUMENT, "device ordinal out of range");
     BTRY(hipSetDevice(device));
-    DeviceArena A;
+    BuildArrays A;
     hipStream_t st = nullptr;
     std::vector<float> h(9 * (size_t)n);
     std::vector<int> hs((size_t)n);

@@ -9,26 +9,6 @@
 // direct one loads every tap from global memory, the tiled one from rows staged in LDS.
 #pragma once
 
-// The renderer's denoiser state: allocated by the first guides / self-test call, freed with the handle.
-// Bytes per pixel: rays 32 + hits 32 (compute_guides only) + guides 32 + two colour buffers 2 x 16 + denoised 12 = 140,
-// plus one word per 64 pixels (the hit counts).
-struct DenoiseState {
-    float4* rays = nullptr;         // 2 rows per pixel: the pixel-centre rays (crt_ray)
-    float4* hits = nullptr;         // 2 rows per pixel: their closest hits (crt_hit)
-    float4* guides = nullptr;       // 2 rows per pixel: (normal.xyz, t) (position.xyz, key)
-    float4* col[2] = {nullptr, nullptr};   // 1 row per pixel: (c.xyz, 0)
-    float* denoised = nullptr;      // W*H*3
-    uint32_t* wave_hits = nullptr;  // per 64 pixels: how many of them hit something
-    bool have_guides = false;       // guides hold a compute_guides or self-test result
-    bool counted = false;           // wave_hits belongs to the guides (compute_guides; not the self-test's upload)
-    bool have_denoised = false;
-    bool timed_guides = false;
-    hipEvent_t g0 = nullptr, g1 = nullptr, f0 = nullptr, f1 = nullptr;
-    hipEvent_t it[9] = {};          // a timed run: after the input kernel, then after every iteration
-    bool lds_raised = false;        // the tiled kernel's dynamic LDS limit was raised for this device
-    int timed_iterations = 0;       // iterations of the last timed run (crt_renderer_denoise_iteration_ms), 0: none
-};
-
 constexpr int DENOISE_MISS_KEY = 0x7fffffff;
 
 struct GuideRayParams {
@@ -219,50 +199,29 @@ __global__ __launch_bounds__(DENOISE_BX * DENOISE_TY) void crt_denoise_tiled_ker
     denoise_store(D, (size_t)y * D.width + x, o);
 }
 
-void crtx_free_denoise_state(crt_renderer* R) {
-    DenoiseState* N = R->denoise;
-    if (!N) return;
-    if (N->rays) (void)hipFree(N->rays);
-    if (N->hits) (void)hipFree(N->hits);
-    if (N->guides) (void)hipFree(N->guides);
-    if (N->col[0]) (void)hipFree(N->col[0]);
-    if (N->col[1]) (void)hipFree(N->col[1]);
-    if (N->denoised) (void)hipFree(N->denoised);
-    if (N->wave_hits) (void)hipFree(N->wave_hits);
-    for (hipEvent_t e : {N->g0, N->g1, N->f0, N->f1})
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : N->it)
-        if (e) (void)hipEventDestroy(e);
-    delete N;
-    R->denoise = nullptr;
-}
-
 namespace {
 
 int denoise_state(crt_renderer* R, DenoiseState** out) {
     if (!R->denoise) {
-        DenoiseState* N = new (std::nothrow) DenoiseState;
+        R->denoise.reset(new (std::nothrow) DenoiseState);   // whatever is allocated below is freed with the handle
+        DenoiseState* N = R->denoise.get();
         if (!N) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-        R->denoise = N;   // whatever is allocated below is freed with the handle
         const size_t n_pix = (size_t)R->width * R->height;
-        HIP_TRY(hipMalloc((void**)&N->rays, n_pix * 32));
-        HIP_TRY(hipMalloc((void**)&N->hits, n_pix * 32));
-        HIP_TRY(hipMalloc((void**)&N->guides, n_pix * 32));
-        HIP_TRY(hipMalloc((void**)&N->col[0], n_pix * 16));
-        HIP_TRY(hipMalloc((void**)&N->col[1], n_pix * 16));
-        HIP_TRY(hipMalloc((void**)&N->denoised, n_pix * 12));
-        HIP_TRY(hipMalloc((void**)&N->wave_hits, ((n_pix + 63) / 64) * 4));
-        HIP_TRY(hipMemset(N->denoised, 0, n_pix * 12));
-        HIP_TRY(hipEventCreate(&N->g0));
-        HIP_TRY(hipEventCreate(&N->g1));
-        HIP_TRY(hipEventCreate(&N->f0));
-        HIP_TRY(hipEventCreate(&N->f1));
-        for (hipEvent_t& e : N->it) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(N->rays.alloc(n_pix * 2));
+        HIP_TRY(N->hits.alloc(n_pix * 2));
+        HIP_TRY(N->guides.alloc(n_pix * 2));
+        HIP_TRY(N->col[0].alloc(n_pix));
+        HIP_TRY(N->col[1].alloc(n_pix));
+        HIP_TRY(N->denoised.alloc(n_pix * 3));
+        HIP_TRY(N->wave_hits.alloc((n_pix + 63) / 64));
+        HIP_TRY(hipMemset(N->denoised.get(), 0, n_pix * 12));
+        for (DevEvent* e : {&N->g0, &N->g1, &N->f0, &N->f1}) HIP_TRY(e->create());
+        for (DevEvent& e : N->it) HIP_TRY(e.create());
+        N->ready = true;
     }
-    DenoiseState* N = R->denoise;
-    if (!N->rays || !N->hits || !N->guides || !N->col[0] || !N->col[1] || !N->denoised || !N->wave_hits || !N->it[8])
+    if (!R->denoise->ready)
         return set_error(CRT_ERR_OUT_OF_MEMORY, "the denoiser state of this renderer could not be allocated");
-    *out = N;
+    *out = R->denoise.get();
     return CRT_OK;
 }
 
@@ -288,13 +247,13 @@ int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, 
     const int W = R->width, H = R->height, n_pix = W * H;
     const int iterations = o->iterations ? o->iterations : 5;
     const bool tile_scale = (o->flags & CRT_DENOISE_TILE_SCALE) != 0, direct_only = (o->flags & CRT_DENOISE_DIRECT_ONLY) != 0;
-    HIP_TRY(hipEventRecord(N->f0, st));
-    hipLaunchKernelGGL(crt_denoise_input_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, R->d_sum, N->col[0],
-                       tile_scale ? R->adaptive->tile_spp : nullptr, W, n_pix, (W + 7) / 8, scale);
+    HIP_TRY(hipEventRecord(N->f0.get(), st));
+    hipLaunchKernelGGL(crt_denoise_input_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, R->d_sum, N->col[0].get(),
+                       tile_scale ? R->adaptive->tile_spp.get() : nullptr, W, n_pix, (W + 7) / 8, scale);
     N->timed_iterations = 0;
-    if (timed) HIP_TRY(hipEventRecord(N->it[0], st));
+    if (timed) HIP_TRY(hipEventRecord(N->it[0].get(), st));
     DenoiseParams D{};
-    D.guides = N->guides;
+    D.guides = N->guides.get();
     D.width = W; D.height = H;
     const float inf = __builtin_inff();
     D.on_c = o->sigma_color != inf; D.on_n = o->sigma_normal != inf; D.on_x = o->sigma_position != inf;
@@ -303,9 +262,9 @@ int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, 
     D.inv_x = D.on_x ? 1.f / (o->sigma_position * o->sigma_position) : 0.f;
     for (int i = 0; i < iterations; ++i) {
         const bool last = i == iterations - 1;
-        D.in = N->col[i & 1];
-        D.out = last ? nullptr : N->col[(i + 1) & 1];
-        D.out3 = last ? N->denoised : nullptr;
+        D.in = N->col[i & 1].get();
+        D.out = last ? nullptr : N->col[(i + 1) & 1].get();
+        D.out3 = last ? N->denoised.get() : nullptr;
         D.stride = 1 << i;
         if (!direct_only && D.stride <= DENOISE_TILED_MAX_STRIDE) {
             const int s = D.stride, rows = (H + s - 1) / s;                   // the rows of residue class 0, the longest
@@ -325,10 +284,10 @@ int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, 
                                dim3(DENOISE_BX, DENOISE_DIRECT_BY), 0, st, D);
         }
         if (D.on_c) D.inv_c = D.inv_c * 4.f;             // the colour sigma halves per level
-        if (timed) HIP_TRY(hipEventRecord(N->it[i + 1], st));
+        if (timed) HIP_TRY(hipEventRecord(N->it[i + 1].get(), st));
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(N->f1, st));
+    HIP_TRY(hipEventRecord(N->f1.get(), st));
     if (timed) N->timed_iterations = iterations;
     N->have_denoised = true;
     return CRT_OK;
@@ -350,18 +309,18 @@ int crt_renderer_compute_guides(crt_renderer* R, const crt_scene* S, const crt_t
     if (int rc = denoise_state(R, &N)) return rc;
     const int n_pix = R->width * R->height;
     N->have_guides = N->counted = false;
-    HIP_TRY(hipEventRecord(N->g0, st));
+    HIP_TRY(hipEventRecord(N->g0.get(), st));
     GuideRayParams G{};
-    G.cam = R->cam; G.width = R->width; G.height = R->height; G.rays = N->rays;
+    G.cam = R->cam; G.width = R->width; G.height = R->height; G.rays = N->rays.get();
     hipLaunchKernelGGL(crt_guide_rays_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, G);
     HIP_TRY(hipGetLastError());
-    if (int rc = crt_scene_trace_device(S, reinterpret_cast<const crt_ray*>(N->rays), n_pix, opts,
-                                        reinterpret_cast<crt_hit*>(N->hits), nullptr, 0u, stream))
+    if (int rc = crt_scene_trace_device(S, reinterpret_cast<const crt_ray*>(N->rays.get()), n_pix, opts,
+                                        reinterpret_cast<crt_hit*>(N->hits.get()), nullptr, 0u, stream))
         return rc;
-    hipLaunchKernelGGL(crt_guide_pack_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, N->rays, N->hits, N->guides,
-                       N->wave_hits, n_pix);
+    hipLaunchKernelGGL(crt_guide_pack_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, N->rays.get(), N->hits.get(), N->guides.get(),
+                       N->wave_hits.get(), n_pix);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(N->g1, st));
+    HIP_TRY(hipEventRecord(N->g1.get(), st));
     N->have_guides = N->counted = N->timed_guides = true;
     return CRT_OK;
 }
@@ -384,15 +343,15 @@ int crt_renderer_denoise(crt_renderer* R, const crt_denoise_options* o, float sc
     if (stats_out) {
         crt_denoise_stats s{};
         s.iterations = (uint32_t)(o->iterations ? o->iterations : 5);
-        HIP_TRY(hipEventSynchronize(N->f1));
-        HIP_TRY(hipEventElapsedTime(&s.filter_ms, N->f0, N->f1));
+        HIP_TRY(hipEventSynchronize(N->f1.get()));
+        HIP_TRY(hipEventElapsedTime(&s.filter_ms, N->f0.get(), N->f1.get()));
         if (N->timed_guides) {
-            HIP_TRY(hipEventSynchronize(N->g1));
-            HIP_TRY(hipEventElapsedTime(&s.guides_ms, N->g0, N->g1));
+            HIP_TRY(hipEventSynchronize(N->g1.get()));
+            HIP_TRY(hipEventElapsedTime(&s.guides_ms, N->g0.get(), N->g1.get()));
         }
         if (N->counted) {
             std::vector<uint32_t> w(((size_t)R->width * R->height + 63) / 64);
-            HIP_TRY(hipMemcpy(w.data(), N->wave_hits, w.size() * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(w.data(), N->wave_hits.get(), w.size() * 4, hipMemcpyDeviceToHost));
             for (uint32_t c : w) s.pixels_hit += c;
         }
         *stats_out = s;
@@ -406,8 +365,8 @@ int crt_renderer_resolve_denoised(crt_renderer* R, void* stream) {
         return set_error(CRT_ERR_INVALID_ARGUMENT, "resolve denoised: no denoised frame on this renderer yet");
     HIP_TRY(hipSetDevice(R->device));
     const int n = R->width * R->height;
-    hipLaunchKernelGGL(crt_resolve_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, R->denoise->denoised,
-                       R->d_rgba, n, 1.f);
+    hipLaunchKernelGGL(crt_resolve_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, R->denoise->denoised.get(),
+                       R->d_rgba.get(), n, 1.f);
     HIP_TRY(hipGetLastError());
     return CRT_OK;
 }
@@ -416,30 +375,30 @@ int crt_renderer_read_denoised(crt_renderer* R, float* out) {
     if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "read denoised: null argument");
     if (!R->denoise || !R->denoise->have_denoised)
         return set_error(CRT_ERR_INVALID_ARGUMENT, "read denoised: no denoised frame on this renderer yet");
-    return read_dev(R, out, R->denoise->denoised, (size_t)R->width * R->height * 12);
+    return read_dev(R, out, R->denoise->denoised.get(), (size_t)R->width * R->height * 12);
 }
 
 int crt_renderer_read_guides(crt_renderer* R, float* out) {
     if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "read guides: null argument");
     if (!R->denoise || !R->denoise->have_guides)
         return set_error(CRT_ERR_INVALID_ARGUMENT, "read guides: no guides computed yet (crt_renderer_compute_guides)");
-    return read_dev(R, out, R->denoise->guides, (size_t)R->width * R->height * 32);
+    return read_dev(R, out, R->denoise->guides.get(), (size_t)R->width * R->height * 32);
 }
 
 int crt_renderer_denoise_iteration_ms(crt_renderer* R, float* out9) {
     if (!R || !out9) return set_error(CRT_ERR_INVALID_ARGUMENT, "denoise iteration ms: null argument");
     if (!R->denoise || !R->denoise->timed_iterations)
         return set_error(CRT_ERR_INVALID_ARGUMENT, "denoise iteration ms: no denoise with a stats pointer on this renderer yet");
-    DenoiseState* N = R->denoise;
+    DenoiseState* N = R->denoise.get();
     HIP_TRY(hipSetDevice(R->device));
-    HIP_TRY(hipEventSynchronize(N->f1));
+    HIP_TRY(hipEventSynchronize(N->f1.get()));
     for (int k = 0; k < 9; ++k) out9[k] = 0.f;
-    HIP_TRY(hipEventElapsedTime(&out9[0], N->f0, N->it[0]));
-    for (int i = 0; i < N->timed_iterations; ++i) HIP_TRY(hipEventElapsedTime(&out9[i + 1], N->it[i], N->it[i + 1]));
+    HIP_TRY(hipEventElapsedTime(&out9[0], N->f0.get(), N->it[0].get()));
+    for (int i = 0; i < N->timed_iterations; ++i) HIP_TRY(hipEventElapsedTime(&out9[i + 1], N->it[i].get(), N->it[i + 1].get()));
     return CRT_OK;
 }
 
-float* crt_renderer_denoised_device_ptr(crt_renderer* R) { return R && R->denoise ? R->denoise->denoised : nullptr; }
+float* crt_renderer_denoised_device_ptr(crt_renderer* R) { return R && R->denoise ? R->denoise->denoised.get() : nullptr; }
 
 // The filter on caller-supplied buffers: the renderer's own state and the host function crt_renderer_denoise calls, on
 // the null stream.  The colours go into the renderer's linear buffer and are taken with scale 1 (1.f * c = c).
@@ -453,12 +412,12 @@ int crt_selftest_denoise(crt_renderer* R, const float* color, const float* guide
     if (int rc = denoise_state(R, &N)) return rc;
     const size_t n_pix = (size_t)R->width * R->height;
     HIP_TRY(hipMemcpy(R->d_sum, color, n_pix * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->guides, guides, n_pix * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->guides.get(), guides, n_pix * 32, hipMemcpyHostToDevice));
     N->have_guides = true;
     N->counted = N->timed_guides = false;
     if (int rc = denoise_run(R, N, o, 1.f, 0, false)) return rc;
     HIP_TRY(hipStreamSynchronize(0));
-    HIP_TRY(hipMemcpy(out, N->denoised, n_pix * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, N->denoised.get(), n_pix * 12, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 

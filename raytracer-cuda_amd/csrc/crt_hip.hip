@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -25,6 +26,7 @@
 
 #include "crt_hip.h"
 #include "crt_device.h"
+#include "crt_devmem.h"
 #include "crt_sah.h"
 #include "crt/ParallelFor.h"
 
@@ -3127,14 +3129,80 @@ private:
 
 }  // namespace
 
+// The per-handle states of the later entries, each allocated by the first call that needs it and freed with its handle.
+// `ready` is set once everything in the state is allocated: a state that is not ready could not be allocated.
+
+// Ray queries (crt_trace.h).
+struct TraceScratch {
+    DevBuf<uint32_t> d_next;
+    DevBuf<unsigned long long> d_stats;
+    DevBuf<uint32_t> d_ovf;                  // stack entries beyond the LDS part, per grid lane
+    DevBuf<crt_ray> d_rays;                  // staging of the host-pointer entries
+    DevBuf<crt_hit> d_hits;
+    DevBuf<uint8_t> d_occ;
+    DevEvent ev0, ev1;
+    bool ready = false;
+    bool traced = false;
+    int n_cus = 0, wg_per_cu = 0;
+};
+
+// The wavefront loop's scratch (crt_paths.h).
+struct WavefrontScratch {
+    DevBuf<crt_ray> rays[2];
+    DevBuf<crt_path> paths[2];
+    DevBuf<crt_hit> hits;
+    DevBuf<int32_t> remaining;
+    DevBuf<uint32_t> d_count;
+    PinnedBuf<uint32_t> h_count;            // [0] the count, [2..3] the trace error word
+    // the queued loop (crt_renderer_render_wavefront_queued): 8 device words and their pinned copy
+    DevBuf<uint32_t> d_queue;               // [0], [1] the ping-pong counts, [2] the sticky error word, [4..7] the totals
+    PinnedBuf<uint32_t> h_queue;
+    DevEvent ev0, ev1;
+    bool ready = false;
+};
+
+// The renderer's adaptive state (crt_adaptive.h).
+struct AdaptiveState {
+    DevBuf<float> prev;             // W*H*3: the sums after the first half of the samples a candidate tile holds
+    DevBuf<int32_t> tile_spp;       // per tile: samples every pixel of the tile has received
+    DevBuf<float> tile_error;       // per tile: the last error estimate
+    DevBuf<uint32_t> key;           // per tile: 0 = not listed, else the error as an ordered integer
+    DevBuf<uint32_t> ctile;         // the unconverged tiles of the last plan in tile order, n_tiles entries
+    DevBuf<uint32_t> ckey;          // their keys
+    DevBuf<uint32_t> list;          // the same tiles, largest error first
+    DevBuf<uint32_t> d_count;       // their number
+    PinnedBuf<uint32_t> h_count;
+    DevEvent ev0, ev1;
+    bool ready = false;
+};
+
+// The renderer's denoiser state (crt_denoise.h).
+// Bytes per pixel: rays 32 + hits 32 (compute_guides only) + guides 32 + two colour buffers 2 x 16 + denoised 12 = 140,
+// plus one word per 64 pixels (the hit counts).
+struct DenoiseState {
+    DevBuf<float4> rays;            // 2 rows per pixel: the pixel-centre rays (crt_ray)
+    DevBuf<float4> hits;            // 2 rows per pixel: their closest hits (crt_hit)
+    DevBuf<float4> guides;          // 2 rows per pixel: (normal.xyz, t) (position.xyz, key)
+    DevBuf<float4> col[2];          // 1 row per pixel: (c.xyz, 0)
+    DevBuf<float> denoised;         // W*H*3
+    DevBuf<uint32_t> wave_hits;     // per 64 pixels: how many of them hit something
+    bool ready = false;
+    bool have_guides = false;       // guides hold a compute_guides or self-test result
+    bool counted = false;           // wave_hits belongs to the guides (compute_guides; not the self-test's upload)
+    bool have_denoised = false;
+    bool timed_guides = false;
+    DevEvent g0, g1, f0, f1;
+    DevEvent it[9];                 // a timed run: after the input kernel, then after every iteration
+    bool lds_raised = false;        // the tiled kernel's dynamic LDS limit was raised for this device
+    int timed_iterations = 0;       // iterations of the last timed run (crt_renderer_denoise_iteration_ms), 0: none
+};
+
 struct crt_scene {
     int device = 0;
-    float4* d_nodes = nullptr;
-    float4* d_prims = nullptr;
-    float4* d_mats = nullptr;
-    float4* d_chain = nullptr;     // width 4: reference scene-level boxes on the per-ray spheres' paths
+    DevBuf<float4> d_nodes, d_prims, d_mats;
+    DevBuf<float4> d_chain;        // width 4: reference scene-level boxes on the per-ray spheres' paths
     int n_chain = 0;
-    float4* d_shade = nullptr;     // shading record per rank (crt_device.h)
+    DevBuf<float4> d_shade;        // shading record per rank (crt_device.h)
     int n_nodes = 0, n_prims = 0, n_mats = 0, n_ranks = 0;   // n_nodes per layout
     int max_depth = 0;
     int bvh = CRT_BVH_REFERENCE, layouts = 1;
@@ -3146,22 +3214,21 @@ struct crt_scene {
     float sph2[2][12] = {};                    // width 4 with exactly two per-ray spheres: their kernel-argument copy
     int tree_spheres = 1;                      // width 4: some leaf holds a sphere
     long excluded = 0;
-    int4* d_ident = nullptr;       // ray queries: per rank (object, primitive, material, 0), see identity_table
-    struct TraceScratch* trace = nullptr;   // ray queries: scratch of the handle, allocated on first use (crt_trace.h)
-    float4* d_mat_rows = nullptr;  // path steps: per material (code, 0, 0, 0) (payload), see material_shade_rows
+    DevBuf<int4> d_ident;          // ray queries: per rank (object, primitive, material, 0), see identity_table
+    std::unique_ptr<TraceScratch> trace;    // ray queries: scratch of the handle, allocated on first use (crt_trace.h)
+    DevBuf<float4> d_mat_rows;     // path steps: per material (code, 0, 0, 0) (payload), see material_shade_rows
 };
-void crtx_free_trace_scratch(crt_scene* S);
 
 constexpr int ERR_WORD = 15;      // d_counters word of the device error flags (RenderParams::err)
 
 struct crt_renderer {
     int device = 0, width = 0, height = 0;
-    uint32_t* d_rng = nullptr;
+    DevBuf<uint32_t> d_rng;
     float* d_sum = nullptr;       // active linear framebuffer (own or attached)
-    float* d_sum_own = nullptr;
-    uint8_t* d_rgba = nullptr;
-    uint32_t* d_seq = nullptr;
-    unsigned long long* d_counters = nullptr;
+    DevBuf<float> d_sum_own;
+    DevBuf<uint8_t> d_rgba;
+    DevBuf<uint32_t> d_seq;
+    DevBuf<unsigned long long> d_counters;
     crt_camera_desc cam{};
     bool has_camera = false;
     // HIP events of the current render: ev0 before the cost probe, ev_main just before the main render kernel (after
@@ -3172,19 +3239,18 @@ struct crt_renderer {
     // fails after its first event (an allocation, the overflow-region check) leaves every readable slot intact.
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_main = nullptr;
-    hipEvent_t ring[CRT_TIMING_RING + 1][3] = {};
+    DevEvent ring[CRT_TIMING_RING + 1][3];
     unsigned long long n_timed = 0;   // renders whose three events were all recorded
     char kernel_name[64] = "";     // instantiation of the last render launch, rocprof's spelling
     // variant 7: pixel order, slot queue, probe costs, sort scratch (allocated on first use)
-    uint32_t* d_order = nullptr;
-    uint32_t* d_queue = nullptr;
-    uint32_t* d_tile_cost = nullptr;   // per-pixel probe costs
-    uint32_t* d_order_hist = nullptr;
-    uint32_t* d_tile_key = nullptr;    // variant 8: per-tile keys
-    unsigned long long* d_probe_stats = nullptr;   // crt_tile_cost_kernel's stats: largest tile work, total work
-    unsigned long long* h_probe_stats = nullptr;   // their pinned host copy
+    DevBuf<uint32_t> d_order, d_queue;
+    DevBuf<uint32_t> d_tile_cost;      // per-pixel probe costs
+    DevBuf<uint32_t> d_order_hist;
+    DevBuf<uint32_t> d_tile_key;       // variant 8: per-tile keys
+    DevBuf<unsigned long long> d_probe_stats;      // crt_tile_cost_kernel's stats: largest tile work, total work
+    PinnedBuf<unsigned long long> h_probe_stats;   // their pinned host copy
     float last_schedule[4] = {0.f, 0.f, 0.f, 0.f};  // crt_renderer_last_schedule
-    uint32_t* d_rng_cache = nullptr;   // curand_init result of (rng_cache_seed, rng_cache_base)
+    DevBuf<uint32_t> d_rng_cache;      // curand_init result of (rng_cache_seed, rng_cache_base)
     unsigned long long rng_cache_seed = 0, rng_cache_base = 0;
     bool rng_cache_valid = false;
     int probe_spp = -1;            // samples per pixel of the cost probe; 0 = no probe (8x8-tile order),
@@ -3206,23 +3272,19 @@ struct crt_renderer {
     int temporal = 0;              // variant 7: tiles ordered by the previous variant-7 frame's rays per pixel
     int drain_threshold = 0;       // variant 7: regeneration threshold once the pixel queue is empty (0 = unchanged)
     int wave_drain = 48;           // variants 4/8: draining waves pass at 48/64 of their live lanes (profiles/r04n)
-    uint32_t* d_pix_rays = nullptr;   // variant 7 with the temporal order: rays per pixel of the last frame
-    uint32_t* d_tile_order = nullptr; // its tiles, most expensive first
+    DevBuf<uint32_t> d_pix_rays;      // variant 7 with the temporal order: rays per pixel of the last frame
+    DevBuf<uint32_t> d_tile_order;    // its tiles, most expensive first
     bool pix_rays_valid = false;
     int min_waves = 0;             // occupancy target (waves/SIMD); 0 = auto: 7 for variant 8 over >= 4 tiles per wave
                                    // slot, 6 for the other 4-wide launches and variants 3 and 10, 5 for variants 0-2
-    uint32_t* d_ovf = nullptr;     // variant 4: stack entries beyond the LDS part, ovf_entries x W*H
-    size_t ovf_entries = 0;
+    DevBuf<uint32_t> d_ovf;        // variant 4: stack entries beyond the LDS part, per pixel
     int stack_lds = STACK_LDS;     // variant 4: per-lane stack entries kept in LDS
     float rcp_w = 1.f, rcp_h = 1.f; // RN(1 / width), RN(1 / height)
     int fast_uv = 0;               // next_ray divides by uv_div (verified for this size at creation, uv_div_mismatches)
-    struct WavefrontScratch* wavefront = nullptr;   // crt_renderer_render_wavefront: batches of the handle, allocated on first use (crt_paths.h)
-    struct AdaptiveState* adaptive = nullptr;       // crt_renderer_render_adaptive: per-tile state of the handle, allocated on first use (crt_adaptive.h)
-    struct DenoiseState* denoise = nullptr;         // crt_renderer_compute_guides / crt_renderer_denoise: guides and colour buffers of the handle, allocated on first use (crt_denoise.h)
+    std::unique_ptr<WavefrontScratch> wavefront;    // crt_renderer_render_wavefront: batches of the handle, allocated on first use (crt_paths.h)
+    std::unique_ptr<AdaptiveState> adaptive;        // crt_renderer_render_adaptive: per-tile state of the handle, allocated on first use (crt_adaptive.h)
+    std::unique_ptr<DenoiseState> denoise;          // crt_renderer_compute_guides / crt_renderer_denoise: guides and colour buffers of the handle, allocated on first use (crt_denoise.h)
 };
-void crtx_free_wavefront_scratch(crt_renderer* R);
-void crtx_free_adaptive_state(crt_renderer* R);
-void crtx_free_denoise_state(crt_renderer* R);
 
 namespace {
 int use_device(int dev) {
@@ -3501,11 +3563,10 @@ int crt_scene_create_ex(const crt_scene_desc* D, int device, const crt_scene_opt
     }
     S->n_chain = rebuilt ? (int)(RB.chain.size() / 2) : 0;
     S->n_ray_spheres = rebuilt ? RB.n_ray_spheres : 0;
-    auto up = [&](float4** dst, const std::vector<float4>& src) -> hipError_t {
-        size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(float4);
-        hipError_t e = hipMalloc((void**)dst, bytes);
-        if (e != hipSuccess) return e;
-        if (!src.empty()) e = hipMemcpy(*dst, src.data(), src.size() * sizeof(float4), hipMemcpyHostToDevice);
+    auto up = [&](DevBuf<float4>& dst, const std::vector<float4>& src) -> hipError_t {
+        hipError_t e = dst.alloc(src.size());
+        if (e == hipSuccess && !src.empty())
+            e = hipMemcpy(dst.get(), src.data(), src.size() * sizeof(float4), hipMemcpyHostToDevice);
         return e;
     };
     const std::vector<int>& rc = rebuilt ? RB.rank_code : F.rank_code;
@@ -3521,14 +3582,14 @@ int crt_scene_create_ex(const crt_scene_desc* D, int device, const crt_scene_opt
     const std::vector<int32_t> ident = identity_table(F);
     const std::vector<float4> mat_rows = material_shade_rows(D);
     hipError_t e;
-    if ((e = up(&S->d_nodes, S->width == 4 ? swizzled : (rebuilt ? RB.nodes : F.nodes))) != hipSuccess ||
-        (e = up(&S->d_prims, rebuilt ? RB.prims : F.prims)) != hipSuccess ||
-        (e = up(&S->d_mats, mats)) != hipSuccess ||
-        (e = up(&S->d_chain, rebuilt ? RB.chain : std::vector<float4>())) != hipSuccess ||
-        (e = up(&S->d_shade, shade)) != hipSuccess ||
-        (e = up(&S->d_mat_rows, mat_rows)) != hipSuccess ||
-        (e = hipMalloc((void**)&S->d_ident, std::max<size_t>(ident.size(), 4) * sizeof(int32_t))) != hipSuccess ||
-        (!ident.empty() && (e = hipMemcpy(S->d_ident, ident.data(), ident.size() * sizeof(int32_t),
+    if ((e = up(S->d_nodes, S->width == 4 ? swizzled : (rebuilt ? RB.nodes : F.nodes))) != hipSuccess ||
+        (e = up(S->d_prims, rebuilt ? RB.prims : F.prims)) != hipSuccess ||
+        (e = up(S->d_mats, mats)) != hipSuccess ||
+        (e = up(S->d_chain, rebuilt ? RB.chain : std::vector<float4>())) != hipSuccess ||
+        (e = up(S->d_shade, shade)) != hipSuccess ||
+        (e = up(S->d_mat_rows, mat_rows)) != hipSuccess ||
+        (e = S->d_ident.alloc(ident.size() / 4)) != hipSuccess ||   // four words per rank
+        (!ident.empty() && (e = hipMemcpy(S->d_ident.get(), ident.data(), ident.size() * sizeof(int32_t),
                                           hipMemcpyHostToDevice)) != hipSuccess)) {
         crt_scene_destroy(S);
         return set_error(CRT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
@@ -3559,14 +3620,6 @@ int crt_scene_get_stats(const crt_scene* S, crt_scene_stats* out) {
 void crt_scene_destroy(crt_scene* S) {
     if (!S) return;
     (void)hipSetDevice(S->device);
-    if (S->d_nodes) (void)hipFree(S->d_nodes);
-    if (S->d_prims) (void)hipFree(S->d_prims);
-    if (S->d_mats) (void)hipFree(S->d_mats);
-    if (S->d_shade) (void)hipFree(S->d_shade);
-    if (S->d_chain) (void)hipFree(S->d_chain);
-    if (S->d_ident) (void)hipFree(S->d_ident);
-    if (S->d_mat_rows) (void)hipFree(S->d_mat_rows);
-    crtx_free_trace_scratch(S);
     delete S;
 }
 
@@ -3578,16 +3631,12 @@ int uv_div_mismatches(int dim, unsigned long long* out) {
     const float b = (float)dim, r = 1.0f / b;
     uint32_t hi;
     std::memcpy(&hi, &b, 4);
-    unsigned long long* d;
-    HIP_TRY(hipMalloc((void**)&d, 8));
-    hipError_t e = hipMemset(d, 0, 8);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(crt_uv_div_check_kernel, dim3(4096), dim3(256), 0, 0, b, r, UV_A_MIN_BITS, hi, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d, 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIP_TRY(e);
+    DevBuf<unsigned long long> d;
+    HIP_TRY(d.alloc(1));
+    HIP_TRY(hipMemset(d.get(), 0, 8));
+    hipLaunchKernelGGL(crt_uv_div_check_kernel, dim3(4096), dim3(256), 0, 0, b, r, UV_A_MIN_BITS, hi, d.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d.get(), 8, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 }  // namespace
@@ -3600,8 +3649,8 @@ int crt_selftest_uv_div(int dim, unsigned long long* mismatches) {
 
 static hipError_t create_timing_ring(crt_renderer* R) {
     for (auto& slot : R->ring)
-        for (hipEvent_t& ev : slot)
-            if (hipError_t e = hipEventCreate(&ev); e != hipSuccess) return e;
+        for (DevEvent& ev : slot)
+            if (hipError_t e = ev.create(); e != hipSuccess) return e;
     return hipSuccess;
 }
 
@@ -3616,21 +3665,21 @@ int crt_renderer_create(int width, int height, int device, crt_renderer** out) {
     const size_t n = (size_t)width * height;
     const auto& tab = seq_tables();
     hipError_t e;
-    if ((e = hipMalloc((void**)&R->d_rng, n * 6 * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&R->d_sum_own, n * 3 * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&R->d_rgba, n * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&R->d_seq, tab.size() * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&R->d_counters, 16 * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemcpy(R->d_seq, tab.data(), tab.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemset(R->d_sum_own, 0, n * 3 * 4)) != hipSuccess ||
-        (e = hipMemset(R->d_rgba, 0, n * 4)) != hipSuccess ||
-        (e = hipMemset(R->d_counters, 0, 16 * sizeof(unsigned long long))) != hipSuccess ||
+    if ((e = R->d_rng.alloc(n * 6)) != hipSuccess ||
+        (e = R->d_sum_own.alloc(n * 3)) != hipSuccess ||
+        (e = R->d_rgba.alloc(n * 4)) != hipSuccess ||
+        (e = R->d_seq.alloc(tab.size())) != hipSuccess ||
+        (e = R->d_counters.alloc(16)) != hipSuccess ||
+        (e = hipMemcpy(R->d_seq.get(), tab.data(), tab.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemset(R->d_sum_own.get(), 0, n * 3 * 4)) != hipSuccess ||
+        (e = hipMemset(R->d_rgba.get(), 0, n * 4)) != hipSuccess ||
+        (e = hipMemset(R->d_counters.get(), 0, 16 * sizeof(unsigned long long))) != hipSuccess ||
         (e = create_timing_ring(R)) != hipSuccess) {
         crt_renderer_destroy(R);
         return set_error(e == hipErrorOutOfMemory ? CRT_ERR_OUT_OF_MEMORY : CRT_ERR_HIP,
                          std::string("renderer allocation: ") + hipGetErrorString(e));
     }
-    R->d_sum = R->d_sum_own;
+    R->d_sum = R->d_sum_own.get();
     // next_ray's image-coordinate divisions: uv_div when it equals the IEEE division for every input of this size
     unsigned long long bad_w = 0, bad_h = 0;
     int rc = uv_div_mismatches(width, &bad_w);
@@ -3654,35 +3703,13 @@ int crt_renderer_attach_linear(crt_renderer* R, float* ptr) {
         if (attr.type != hipMemoryTypeDevice || attr.device != R->device)
             return set_error(CRT_ERR_INVALID_ARGUMENT, "attach_linear: not device memory of the renderer's device");
     }
-    R->d_sum = ptr ? ptr : R->d_sum_own;
+    R->d_sum = ptr ? ptr : R->d_sum_own.get();
     return CRT_OK;
 }
 
 void crt_renderer_destroy(crt_renderer* R) {
     if (!R) return;
     (void)hipSetDevice(R->device);
-    if (R->d_rng) (void)hipFree(R->d_rng);
-    if (R->d_sum_own) (void)hipFree(R->d_sum_own);
-    if (R->d_rgba) (void)hipFree(R->d_rgba);
-    if (R->d_seq) (void)hipFree(R->d_seq);
-    if (R->d_counters) (void)hipFree(R->d_counters);
-    if (R->d_ovf) (void)hipFree(R->d_ovf);
-    if (R->d_order) (void)hipFree(R->d_order);
-    if (R->d_queue) (void)hipFree(R->d_queue);
-    if (R->d_tile_cost) (void)hipFree(R->d_tile_cost);
-    if (R->d_order_hist) (void)hipFree(R->d_order_hist);
-    if (R->d_tile_key) (void)hipFree(R->d_tile_key);
-    if (R->d_probe_stats) (void)hipFree(R->d_probe_stats);
-    if (R->h_probe_stats) (void)hipHostFree(R->h_probe_stats);
-    if (R->d_pix_rays) (void)hipFree(R->d_pix_rays);
-    if (R->d_tile_order) (void)hipFree(R->d_tile_order);
-    if (R->d_rng_cache) (void)hipFree(R->d_rng_cache);
-    crtx_free_wavefront_scratch(R);
-    crtx_free_adaptive_state(R);
-    crtx_free_denoise_state(R);
-    for (auto& slot : R->ring)
-        for (hipEvent_t& ev : slot)
-            if (ev) (void)hipEventDestroy(ev);
     delete R;
 }
 
@@ -3694,22 +3721,21 @@ int crt_renderer_init_rand(crt_renderer* R, unsigned long long seed, unsigned lo
     // curand_init is a pure function of (seed, subsequence): keep the initialised array and copy it back for a
     // repeated (seed, base) — 2.8 ms of GF(2) jumps at 2560x1440 become a 35 us device copy, same bits
     if (R->rng_cache_valid && R->rng_cache_seed == seed && R->rng_cache_base == subseq_base) {
-        HIP_TRY(hipMemcpyAsync(R->d_rng, R->d_rng_cache, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(R->d_rng.get(), R->d_rng_cache.get(), (size_t)n * 24, hipMemcpyDeviceToDevice, st));
         return CRT_OK;
     }
-    hipLaunchKernelGGL(crt_init_rand_kernel, dim3((n + 255) / 256), dim3(256), 0, st, R->d_rng,
-                       R->d_seq, n, seed, subseq_base);
+    hipLaunchKernelGGL(crt_init_rand_kernel, dim3((n + 255) / 256), dim3(256), 0, st, R->d_rng.get(),
+                       R->d_seq.get(), n, seed, subseq_base);
     HIP_TRY(hipGetLastError());
     R->rng_cache_valid = false;
     if (!R->d_rng_cache) {
         HIP_TRY(hipStreamSynchronize(st));
-        if (hipMalloc((void**)&R->d_rng_cache, (size_t)n * 24) != hipSuccess) {   // optional: no cache then
+        if (R->d_rng_cache.alloc((size_t)n * 6) != hipSuccess) {   // optional: no cache then
             (void)hipGetLastError();
-            R->d_rng_cache = nullptr;
             return CRT_OK;
         }
     }
-    HIP_TRY(hipMemcpyAsync(R->d_rng_cache, R->d_rng, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(R->d_rng_cache.get(), R->d_rng.get(), (size_t)n * 24, hipMemcpyDeviceToDevice, st));
     R->rng_cache_seed = seed;
     R->rng_cache_base = subseq_base;
     R->rng_cache_valid = true;
@@ -3860,23 +3886,23 @@ static int ensure_order_buffers(crt_renderer* R, hipStream_t st, size_t n_pix, i
     if (R->d_order && (R->d_tile_key || !want_tile_key)) return CRT_OK;
     HIP_TRY(hipStreamSynchronize(st));
     if (!R->d_order) {
-        HIP_TRY(hipMalloc((void**)&R->d_order, std::max(n_pix, (size_t)n_tiles * 64) * 4));
-        HIP_TRY(hipMalloc((void**)&R->d_queue, 4));
-        HIP_TRY(hipMalloc((void**)&R->d_tile_cost, n_pix * 4));
-        HIP_TRY(hipMalloc((void**)&R->d_order_hist, ORDER_KEYS * 4));
+        HIP_TRY(R->d_order.alloc(std::max(n_pix, (size_t)n_tiles * 64)));
+        HIP_TRY(R->d_queue.alloc(1));
+        HIP_TRY(R->d_tile_cost.alloc(n_pix));
+        HIP_TRY(R->d_order_hist.alloc(ORDER_KEYS));
         HIP_TRY(hipDeviceGetAttribute(&R->n_cus, hipDeviceAttributeMultiprocessorCount, R->device));
     }
-    if (want_tile_key && !R->d_tile_key) HIP_TRY(hipMalloc((void**)&R->d_tile_key, (size_t)n_tiles * 4));
+    if (want_tile_key && !R->d_tile_key) HIP_TRY(R->d_tile_key.alloc((size_t)n_tiles));
     return CRT_OK;
 }
 
 // out = the indices 0..n-1, largest key first (counting sort over ORDER_KEYS buckets).
 static int sort_descending(crt_renderer* R, hipStream_t st, const uint32_t* keys, int n, uint32_t* out) {
     const unsigned ob = (unsigned)((n + ORDER_ITEMS - 1) / ORDER_ITEMS);
-    HIP_TRY(hipMemsetAsync(R->d_order_hist, 0, ORDER_KEYS * 4, st));
-    hipLaunchKernelGGL(crt_order_hist_kernel, dim3(ob), dim3(256), 0, st, keys, n, R->d_order_hist);
-    hipLaunchKernelGGL(crt_order_scan_kernel, dim3(1), dim3(ORDER_KEYS), 0, st, R->d_order_hist);
-    hipLaunchKernelGGL(crt_order_scatter_kernel, dim3(ob), dim3(256), 0, st, keys, n, R->d_order_hist, out, 0u);
+    HIP_TRY(hipMemsetAsync(R->d_order_hist.get(), 0, ORDER_KEYS * 4, st));
+    hipLaunchKernelGGL(crt_order_hist_kernel, dim3(ob), dim3(256), 0, st, keys, n, R->d_order_hist.get());
+    hipLaunchKernelGGL(crt_order_scan_kernel, dim3(1), dim3(ORDER_KEYS), 0, st, R->d_order_hist.get());
+    hipLaunchKernelGGL(crt_order_scatter_kernel, dim3(ob), dim3(256), 0, st, keys, n, R->d_order_hist.get(), out, 0u);
     return CRT_OK;
 }
 
@@ -3889,51 +3915,51 @@ static int order_tiles_by_probe(crt_renderer* R, hipStream_t st, int stride, boo
     const dim3 tgrid((n_tiles + 255) / 256), tblock(256);
     if (stats) {
         if (!R->d_probe_stats) {
-            HIP_TRY(hipMalloc((void**)&R->d_probe_stats, 2 * sizeof(unsigned long long)));
-            HIP_TRY(hipHostMalloc((void**)&R->h_probe_stats, 2 * sizeof(unsigned long long)));
+            HIP_TRY(R->d_probe_stats.alloc(2));
+            HIP_TRY(R->h_probe_stats.alloc(2));
         }
-        HIP_TRY(hipMemsetAsync(R->d_probe_stats, 0, 2 * sizeof(unsigned long long), st));
+        HIP_TRY(hipMemsetAsync(R->d_probe_stats.get(), 0, 2 * sizeof(unsigned long long), st));
     }
-    hipLaunchKernelGGL(crt_tile_cost_kernel, tgrid, tblock, 0, st, R->d_tile_cost, R->width, R->height, tiles_x, n_tiles,
-                       R->d_tile_key, R->tile_key_mode, stride, stats ? R->d_probe_stats : nullptr);
-    if (stats) HIP_TRY(hipMemcpyAsync(R->h_probe_stats, R->d_probe_stats, 2 * sizeof(unsigned long long),
+    hipLaunchKernelGGL(crt_tile_cost_kernel, tgrid, tblock, 0, st, R->d_tile_cost.get(), R->width, R->height, tiles_x, n_tiles,
+                       R->d_tile_key.get(), R->tile_key_mode, stride, stats ? R->d_probe_stats.get() : nullptr);
+    if (stats) HIP_TRY(hipMemcpyAsync(R->h_probe_stats.get(), R->d_probe_stats.get(), 2 * sizeof(unsigned long long),
                                       hipMemcpyDeviceToHost, st));
     if (R->tile_key_mode == 2) {   // per-pixel costs are no longer needed: reuse them for the smoothed keys
-        hipLaunchKernelGGL(crt_tile_neighbour_kernel, tgrid, tblock, 0, st, R->d_tile_key, tiles_x, n_tiles, R->d_tile_cost);
-        HIP_TRY(hipMemcpyAsync(R->d_tile_key, R->d_tile_cost, (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(crt_tile_neighbour_kernel, tgrid, tblock, 0, st, R->d_tile_key.get(), tiles_x, n_tiles, R->d_tile_cost.get());
+        HIP_TRY(hipMemcpyAsync(R->d_tile_key.get(), R->d_tile_cost.get(), (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, st));
     }
     if (shards > 1)
-        hipLaunchKernelGGL(crt_tile_shard_mask_kernel, tgrid, tblock, 0, st, R->d_tile_key, n_tiles, shard, shards);
-    if (int rc = sort_descending(R, st, R->d_tile_key, n_tiles, R->d_order)) return rc;
+        hipLaunchKernelGGL(crt_tile_shard_mask_kernel, tgrid, tblock, 0, st, R->d_tile_key.get(), n_tiles, shard, shards);
+    if (int rc = sort_descending(R, st, R->d_tile_key.get(), n_tiles, R->d_order.get())) return rc;
     // XCD regions: the per-pixel costs are dead by now, so they hold the strips' lists and the pool (9 n_tiles)
     if (R->xcd_regions && shards == 1 && tiles_x <= 2048 && n_pix >= (size_t)9 * n_tiles)
-        hipLaunchKernelGGL(crt_xcd_order_kernel, dim3(1), dim3(1024), 0, st, R->d_order, R->d_tile_key, n_tiles, tiles_x,
-                           R->d_tile_cost, R->d_tile_cost + (size_t)8 * n_tiles);
+        hipLaunchKernelGGL(crt_xcd_order_kernel, dim3(1), dim3(1024), 0, st, R->d_order.get(), R->d_tile_key.get(), n_tiles, tiles_x,
+                           R->d_tile_cost.get(), R->d_tile_cost.get() + (size_t)8 * n_tiles);
     return CRT_OK;
 }
 
 // Pixel sharding without the probe: d_order[k] = this shard's k-th tile in row order.
 static void shard_tiles_in_row_order(crt_renderer* R, hipStream_t st, int n_tiles, int shard, int shards) {
-    hipLaunchKernelGGL(crt_shard_tiles_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_order, n_tiles,
+    hipLaunchKernelGGL(crt_shard_tiles_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_order.get(), n_tiles,
                        shard, shards);
 }
 
 static RenderParams render_params(const crt_renderer* R, const crt_scene* S, int spp, int max_bounces, unsigned flags) {
     RenderParams P{};   // no order, queue, probe costs, overflow stack or ray counts: the schedules set what they use
-    P.nodes = S->d_nodes; P.prims = S->d_prims; P.mats = S->d_mats; P.shade = S->d_shade;
+    P.nodes = S->d_nodes.get(); P.prims = S->d_prims.get(); P.mats = S->d_mats.get(); P.shade = S->d_shade.get();
     P.n_nodes = S->n_nodes; P.n_mats = S->n_mats; P.n_prims = S->n_prims; P.n_layouts = S->layouts;
-    P.err = reinterpret_cast<unsigned*>(R->d_counters + ERR_WORD);
+    P.err = reinterpret_cast<unsigned*>(R->d_counters.get() + ERR_WORD);
     set_camera_frame(P, R);
     P.spp = spp; P.max_bounces = max_bounces;
     P.accumulate = (flags & CRT_RENDER_ACCUMULATE) ? 1 : 0;
-    P.rng = R->d_rng; P.sum = R->d_sum; P.counters = R->d_counters;
+    P.rng = R->d_rng.get(); P.sum = R->d_sum; P.counters = R->d_counters.get();
     P.probe_stride = 1;
     P.crit_threshold = 64;
     P.top_levels = R->top_levels < 0 ? CRT_TOP_LEVELS : R->top_levels;
     P.stack_cap = S->stack_cap;
     P.sphere_first = S->sphere_first;
     P.n_ray_spheres = S->n_ray_spheres;
-    P.sphere_chain = S->d_chain;
+    P.sphere_chain = S->d_chain.get();
     P.n_chain = S->n_chain;
     P.tree_spheres = S->tree_spheres;
     std::memcpy(P.sph2, S->sph2, sizeof P.sph2);
@@ -3994,15 +4020,11 @@ static int ensure_overflow_stack(crt_renderer* R, const crt_scene* S, hipStream_
     const size_t need = (size_t)(S->stack_cap - P.stack_lds);
     if (need * R->width * R->height * 4 >= ((size_t)1 << 32))
         return set_error(CRT_ERR_INVALID_ARGUMENT, "traversal-stack overflow region would exceed 4 GiB");
-    if (need > R->ovf_entries) {         // grow the overflow stack region (rarely needed)
+    if (need * R->width * R->height > R->d_ovf.size()) {   // grow the overflow stack region (rarely needed)
         HIP_TRY(hipStreamSynchronize(st));
-        if (R->d_ovf) (void)hipFree(R->d_ovf);
-        R->d_ovf = nullptr;
-        R->ovf_entries = 0;
-        HIP_TRY(hipMalloc((void**)&R->d_ovf, need * R->width * R->height * 4));
-        R->ovf_entries = need;
+        HIP_TRY(R->d_ovf.grow(need * R->width * R->height));
     }
-    P.ovf = R->d_ovf;
+    P.ovf = R->d_ovf.get();
     return CRT_OK;
 }
 
@@ -4023,7 +4045,7 @@ static int render_tiles(crt_renderer* R, const crt_scene* S, hipStream_t st, Ren
         RenderParams Q = P;
         Q.spp = probe_spp_for(R, spp);
         Q.accumulate = 0;
-        Q.probe_cost = R->d_tile_cost;
+        Q.probe_cost = R->d_tile_cost.get();
         if (variant == 8) {
             // every stride-th pixel in x and y; automatic: 2 below 1000 spp, where the probe is a larger share of the
             // frame (a 250-spp rank share: probe 3.2 -> 1.2 ms, render -0.9 %; at 2000 spp the render is unchanged,
@@ -4038,7 +4060,7 @@ static int render_tiles(crt_renderer* R, const crt_scene* S, hipStream_t st, Ren
             hipLaunchKernelGGL((crt_render_kernel<true, 3, 5>), grid, dim3(256), 0, st, Q);
         }
         if (int rc = order_tiles_by_probe(R, st, Q.probe_stride, auto_small, shard, shards)) return rc;
-        P.order = R->d_order;
+        P.order = R->d_order.get();
         if (variant == 8) {
             P.crit_tiles = R->crit_tiles < 0 ? 4 * R->n_cus : R->crit_tiles;
             P.crit_threshold = R->crit_threshold;
@@ -4051,8 +4073,8 @@ static int render_tiles(crt_renderer* R, const crt_scene* S, hipStream_t st, Ren
             // third of the wave slots (profiles/r06x, r06y: config B rho 2.0, -7.6 %; the plain Cornell box at the
             // same size rho 0.8, +15 % at 4).  One host synchronisation after the sort.
             HIP_TRY(hipStreamSynchronize(st));
-            const double mx = (double)R->h_probe_stats[0];
-            const double mine = (double)R->h_probe_stats[1] / shards;
+            const double mx = (double)R->h_probe_stats.get()[0];
+            const double mine = (double)R->h_probe_stats.get()[1] / shards;
             const double rho = mine > 0 ? mx * (4.0 * R->n_cus * 6) / mine : 0.0;
             if (rho > CRT_CHAIN_RHO) {
                 occ = 4;
@@ -4064,7 +4086,7 @@ static int render_tiles(crt_renderer* R, const crt_scene* S, hipStream_t st, Ren
         }
     } else if (shards > 1) {   // pixel shard without the probe: this shard's tiles in row order
         shard_tiles_in_row_order(R, st, n_tiles, shard, shards);
-        P.order = R->d_order;
+        P.order = R->d_order.get();
     }
     if (P.crit_tiles > 0) P.crit_tiles = (P.crit_tiles + shards - 1) / shards;
     if (variant == 8) R->last_schedule[1] = (float)occ;
@@ -4081,9 +4103,9 @@ static int order_tile_slots(crt_renderer* R, hipStream_t st) {
     const size_t n_tile_slots = (size_t)n_tiles * 64;
     if (R->temporal && !R->d_pix_rays) {
         HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMalloc((void**)&R->d_pix_rays, n_pix * 4));
-        HIP_TRY(hipMalloc((void**)&R->d_tile_order, (size_t)n_tiles * 4));
-        if (!R->d_tile_key) HIP_TRY(hipMalloc((void**)&R->d_tile_key, (size_t)n_tiles * 4));
+        HIP_TRY(R->d_pix_rays.alloc(n_pix));
+        HIP_TRY(R->d_tile_order.alloc((size_t)n_tiles));
+        if (!R->d_tile_key) HIP_TRY(R->d_tile_key.alloc((size_t)n_tiles));
         R->pix_rays_valid = false;
     }
     const dim3 sgrid((unsigned)((n_tile_slots + 255) / 256));
@@ -4092,15 +4114,15 @@ static int order_tile_slots(crt_renderer* R, hipStream_t st) {
         // slowest pixel, raised to 3/4 of the neighbours', as variant 8's probe keys) -> tiles most expensive
         // first, so the long paths start early and the launch does not end with them (profiles/r04i: a 1-spp
         // frame in row order spends its last 31 % draining)
-        hipLaunchKernelGGL(crt_tile_cost_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_pix_rays,
-                           R->width, R->height, tiles_x, n_tiles, R->d_tile_order, 0, 1, nullptr);
+        hipLaunchKernelGGL(crt_tile_cost_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_pix_rays.get(),
+                           R->width, R->height, tiles_x, n_tiles, R->d_tile_order.get(), 0, 1, nullptr);
         hipLaunchKernelGGL(crt_tile_neighbour_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st,
-                           R->d_tile_order, tiles_x, n_tiles, R->d_tile_key);
-        if (int rc = sort_descending(R, st, R->d_tile_key, n_tiles, R->d_tile_order)) return rc;
-        hipLaunchKernelGGL(crt_expand_tile_order_kernel, sgrid, dim3(256), 0, st, R->d_tile_order, R->d_order,
+                           R->d_tile_order.get(), tiles_x, n_tiles, R->d_tile_key.get());
+        if (int rc = sort_descending(R, st, R->d_tile_key.get(), n_tiles, R->d_tile_order.get())) return rc;
+        hipLaunchKernelGGL(crt_expand_tile_order_kernel, sgrid, dim3(256), 0, st, R->d_tile_order.get(), R->d_order.get(),
                            R->width, R->height, (int)n_tile_slots);
     } else {
-        hipLaunchKernelGGL(crt_order_tiles_kernel, sgrid, dim3(256), 0, st, R->d_order, R->width, R->height,
+        hipLaunchKernelGGL(crt_order_tiles_kernel, sgrid, dim3(256), 0, st, R->d_order.get(), R->width, R->height,
                            (int)n_tile_slots);
     }
     return CRT_OK;
@@ -4116,23 +4138,23 @@ static int render_pixel_queue(crt_renderer* R, hipStream_t st, RenderParams& P, 
         RenderParams Q = P;
         Q.spp = probe_spp_for(R, spp);
         Q.accumulate = 0;
-        Q.probe_cost = R->d_tile_cost;
+        Q.probe_cost = R->d_tile_cost.get();
         const dim3 grid((R->width + 15) / 16, (R->height + 15) / 16);
         if (occ >= 6) hipLaunchKernelGGL((crt_render_kernel<false, 4, 6>), grid, dim3(256), 0, st, Q);
         else hipLaunchKernelGGL((crt_render_kernel<false, 4, 5>), grid, dim3(256), 0, st, Q);
-        if (int rc = sort_descending(R, st, R->d_tile_cost, (int)n_pix, R->d_order)) return rc;
+        if (int rc = sort_descending(R, st, R->d_tile_cost.get(), (int)n_pix, R->d_order.get())) return rc;
         P.n_slots = (int)n_pix;
     } else {
         if (int rc = order_tile_slots(R, st)) return rc;
         P.n_slots = (int)n_tile_slots;
         if (R->temporal) {
-            P.pix_rays = R->d_pix_rays;
+            P.pix_rays = R->d_pix_rays.get();
             R->pix_rays_valid = true;
         }
     }
-    HIP_TRY(hipMemsetAsync(R->d_queue, 0, 4, st));
-    P.order = R->d_order;
-    P.queue = R->d_queue;
+    HIP_TRY(hipMemsetAsync(R->d_queue.get(), 0, 4, st));
+    P.order = R->d_order.get();
+    P.queue = R->d_queue.get();
     P.probe_cost = nullptr;
     const RenderRow& row = RENDER_ROWS[render_row(7, cnt, occ)];
     const int per_cu = row.w;        // workgroups of 4 waves resident per CU
@@ -4147,7 +4169,7 @@ int crt_renderer_render(crt_renderer* R, const crt_scene* S, int spp, int max_bo
     if (S->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, "scene and renderer on different devices");
     HIP_TRY(hipSetDevice(R->device));
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(R->d_counters, 0, ERR_WORD * sizeof(unsigned long long), st));   // the error word stays
+    HIP_TRY(hipMemsetAsync(R->d_counters.get(), 0, ERR_WORD * sizeof(unsigned long long), st));   // the error word stays
     RenderParams P = render_params(R, S, spp, max_bounces, flags);
     const bool cnt = (flags & CRT_RENDER_COUNT_WORK) != 0;
     if (R->tile_shards > 1) {
@@ -4160,8 +4182,8 @@ int crt_renderer_render(crt_renderer* R, const crt_scene* S, int spp, int max_bo
         HIP_TRY(hipMemsetAsync(R->d_sum, 0, (size_t)R->width * R->height * 3 * sizeof(float), st));
     }
     {   // this render's slot of the timing ring: the spare slot, which no readable frame occupies (crt_renderer)
-        hipEvent_t* slot = R->ring[R->n_timed % (CRT_TIMING_RING + 1)];
-        R->ev0 = slot[0]; R->ev_main = slot[1]; R->ev1 = slot[2];
+        const DevEvent* slot = R->ring[R->n_timed % (CRT_TIMING_RING + 1)];
+        R->ev0 = slot[0].get(); R->ev_main = slot[1].get(); R->ev1 = slot[2].get();
     }
     HIP_TRY(hipEventRecord(R->ev0, st));
     const int variant = choose_variant(R, S, spp);
@@ -4203,45 +4225,43 @@ int crt_scene_compare_dump(crt_renderer* R, const crt_scene* A, const crt_scene*
     if (A->n_ranks != B->n_ranks) return set_error(CRT_ERR_INVALID_ARGUMENT, "scenes hold different primitive sets");
     if (spp < 0 || max_bounces < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "negative spp / bounces");
     HIP_TRY(hipSetDevice(R->device));
-    HIP_TRY(hipMemset(R->d_counters, 0, ERR_WORD * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(R->d_counters.get(), 0, ERR_WORD * sizeof(unsigned long long)));
     CompareParams Q{};
     RenderParams& P = Q.A;
-    P.nodes = A->d_nodes; P.prims = A->d_prims; P.mats = A->d_mats; P.shade = A->d_shade;
+    P.nodes = A->d_nodes.get(); P.prims = A->d_prims.get(); P.mats = A->d_mats.get(); P.shade = A->d_shade.get();
     P.n_nodes = A->n_nodes; P.n_mats = A->n_mats; P.n_prims = A->n_prims; P.n_layouts = A->layouts;
-    P.err = reinterpret_cast<unsigned*>(R->d_counters + ERR_WORD);
+    P.err = reinterpret_cast<unsigned*>(R->d_counters.get() + ERR_WORD);
     P.width = R->width; P.height = R->height; P.spp = spp; P.max_bounces = max_bounces;
     P.accumulate = 0; P.regen_threshold = 64; P.drain_threshold = 64; P.wave_drain = 64;
-    P.rng = R->d_rng; P.sum = R->d_sum; P.counters = R->d_counters; P.cam = R->cam;
+    P.rng = R->d_rng.get(); P.sum = R->d_sum; P.counters = R->d_counters.get(); P.cam = R->cam;
     P.rcp_w = R->rcp_w; P.rcp_h = R->rcp_h; P.fast_uv = R->fast_uv;
     P.probe_stride = 1;
     P.pix_rays = nullptr;
-    Q.nodes_b = B->d_nodes; Q.prims_b = B->d_prims; Q.n_nodes_b = B->n_nodes; Q.n_layouts_b = B->layouts;
+    Q.nodes_b = B->d_nodes.get(); Q.prims_b = B->d_prims.get(); Q.n_nodes_b = B->n_nodes; Q.n_layouts_b = B->layouts;
     Q.width_a = A->width; Q.width_b = B->width;
     Q.dump = nullptr;
     Q.max_dump = 0;
-    float* d_dump = nullptr;
+    DevBuf<float> d_dump;
     if (dump && max_dump > 0) {
-        HIP_TRY(hipMalloc((void**)&d_dump, (size_t)max_dump * 10 * sizeof(float)));
-        Q.dump = d_dump;
+        HIP_TRY(d_dump.alloc((size_t)max_dump * 10));
+        Q.dump = d_dump.get();
         Q.max_dump = max_dump;
     }
-    P.sphere_first = A->sphere_first; P.n_ray_spheres = A->n_ray_spheres; P.sphere_chain = A->d_chain;
+    P.sphere_first = A->sphere_first; P.n_ray_spheres = A->n_ray_spheres; P.sphere_chain = A->d_chain.get();
     P.n_chain = A->n_chain;
     std::memcpy(P.sph2, A->sph2, sizeof P.sph2);
-    Q.sphere_first_b = B->sphere_first; Q.n_spheres_b = B->n_ray_spheres; Q.chain_b = B->d_chain;
+    Q.sphere_first_b = B->sphere_first; Q.n_spheres_b = B->n_ray_spheres; Q.chain_b = B->d_chain.get();
     Q.n_chain_b = B->n_chain;
     dim3 grid((R->width + 15) / 16, (R->height + 15) / 16), block(256);
     hipLaunchKernelGGL(crt_compare_kernel, grid, block, 0, 0, Q);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     unsigned long long h[8];
-    HIP_TRY(hipMemcpy(h, R->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h, R->d_counters.get(), sizeof h, hipMemcpyDeviceToHost));
     for (int i = 0; i < 5; ++i) out[i] = h[i];
     if (d_dump) {
         const size_t n = std::min<size_t>((size_t)max_dump, (size_t)(h[6] & 0xffffffffu));
-        hipError_t e = n ? hipMemcpy(dump, d_dump, n * 10 * sizeof(float), hipMemcpyDeviceToHost) : hipSuccess;
-        (void)hipFree(d_dump);
-        HIP_TRY(e);
+        if (n) HIP_TRY(hipMemcpy(dump, d_dump.get(), n * 10 * sizeof(float), hipMemcpyDeviceToHost));
     }
     return CRT_OK;
 }
@@ -4251,7 +4271,7 @@ int crt_renderer_resolve(crt_renderer* R, float scale, void* stream) {
     HIP_TRY(hipSetDevice(R->device));
     const int n = R->width * R->height;
     hipLaunchKernelGGL(crt_resolve_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, R->d_sum,
-                       R->d_rgba, n, scale);
+                       R->d_rgba.get(), n, scale);
     HIP_TRY(hipGetLastError());
     return CRT_OK;
 }
@@ -4269,7 +4289,7 @@ int crt_renderer_render_frame(crt_renderer* R, const crt_scene* S, void* stream)
 // fault, at the synchronisation after the launch (CUDARenderer.cuh:59, CUDA_CHECK(cudaDeviceSynchronize())).
 static int take_device_error(crt_renderer* R, unsigned long long word) {
     if (!word) return CRT_OK;
-    HIP_TRY(hipMemset(R->d_counters + ERR_WORD, 0, sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(R->d_counters.get() + ERR_WORD, 0, sizeof(unsigned long long)));
     std::string m = "render kernel reported an internal error:";
     if (word & 1u) m += " primitive index out of range;";
     if (word & 2u) m += " traversal stack deeper than the scene's stack bound (entries dropped);";
@@ -4282,7 +4302,7 @@ int crt_renderer_synchronize(crt_renderer* R, void* stream) {
     HIP_TRY(hipSetDevice(R->device));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     unsigned long long word = 0;
-    HIP_TRY(hipMemcpy(&word, R->d_counters + ERR_WORD, sizeof word, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&word, R->d_counters.get() + ERR_WORD, sizeof word, hipMemcpyDeviceToHost));
     return take_device_error(R, word);
 }
 
@@ -4297,10 +4317,10 @@ int crt_renderer_read_linear(crt_renderer* R, float* out) {
     return R ? read_dev(R, out, R->d_sum, (size_t)R->width * R->height * 12) : set_error(CRT_ERR_INVALID_ARGUMENT, "null");
 }
 int crt_renderer_read_rgba8(crt_renderer* R, uint8_t* out) {
-    return R ? read_dev(R, out, R->d_rgba, (size_t)R->width * R->height * 4) : set_error(CRT_ERR_INVALID_ARGUMENT, "null");
+    return R ? read_dev(R, out, R->d_rgba.get(), (size_t)R->width * R->height * 4) : set_error(CRT_ERR_INVALID_ARGUMENT, "null");
 }
 int crt_renderer_read_rng(crt_renderer* R, uint32_t* out) {
-    return R ? read_dev(R, out, R->d_rng, (size_t)R->width * R->height * 24) : set_error(CRT_ERR_INVALID_ARGUMENT, "null");
+    return R ? read_dev(R, out, R->d_rng.get(), (size_t)R->width * R->height * 24) : set_error(CRT_ERR_INVALID_ARGUMENT, "null");
 }
 int crt_renderer_write_linear(crt_renderer* R, const float* in) {
     if (!R || !in) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
@@ -4311,7 +4331,7 @@ int crt_renderer_write_linear(crt_renderer* R, const float* in) {
 int crt_renderer_get_counters(crt_renderer* R, crt_work_counters* out) {
     if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
     unsigned long long c[16];
-    if (int rc = read_dev(R, c, R->d_counters, sizeof c)) return rc;
+    if (int rc = read_dev(R, c, R->d_counters.get(), sizeof c)) return rc;
     R->diag[0] = c[5]; R->diag[1] = c[6] & ((1ull << 40) - 1); R->diag[2] = c[6] >> 40;
     for (int i = 0; i < 7; ++i) R->prof[i] = c[8 + i];
     R->prof[7] = c[7];
@@ -4335,8 +4355,8 @@ int crt_renderer_get_schedule_stats(crt_renderer* R, unsigned long long* out3) {
 }
 
 float* crt_renderer_linear_device_ptr(crt_renderer* R) { return R ? R->d_sum : nullptr; }
-uint8_t* crt_renderer_rgba_device_ptr(crt_renderer* R) { return R ? R->d_rgba : nullptr; }
-uint32_t* crt_renderer_rng_device_ptr(crt_renderer* R) { return R ? R->d_rng : nullptr; }
+uint8_t* crt_renderer_rgba_device_ptr(crt_renderer* R) { return R ? R->d_rgba.get() : nullptr; }
+uint32_t* crt_renderer_rng_device_ptr(crt_renderer* R) { return R ? R->d_rng.get() : nullptr; }
 
 const char* crt_renderer_last_kernel_name(const crt_renderer* R) { return R ? R->kernel_name : ""; }
 
@@ -4426,12 +4446,12 @@ int crt_renderer_timing_history(crt_renderer* R, int back, float out[3]) {
     if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
     if (back < 0 || back >= CRT_TIMING_RING) return set_error(CRT_ERR_INVALID_ARGUMENT, "back outside [0, CRT_TIMING_RING)");
     if ((unsigned long long)back >= R->n_timed) return set_error(CRT_ERR_INVALID_ARGUMENT, "fewer renders than back + 1");
-    hipEvent_t* slot = R->ring[(R->n_timed - 1 - (unsigned long long)back) % (CRT_TIMING_RING + 1)];
+    const DevEvent* slot = R->ring[(R->n_timed - 1 - (unsigned long long)back) % (CRT_TIMING_RING + 1)];
     HIP_TRY(hipSetDevice(R->device));
-    HIP_TRY(hipEventSynchronize(slot[2]));
-    HIP_TRY(hipEventElapsedTime(&out[0], slot[0], slot[2]));
-    HIP_TRY(hipEventElapsedTime(&out[1], slot[0], slot[1]));
-    HIP_TRY(hipEventElapsedTime(&out[2], slot[1], slot[2]));
+    HIP_TRY(hipEventSynchronize(slot[2].get()));
+    HIP_TRY(hipEventElapsedTime(&out[0], slot[0].get(), slot[2].get()));
+    HIP_TRY(hipEventElapsedTime(&out[1], slot[0].get(), slot[1].get()));
+    HIP_TRY(hipEventElapsedTime(&out[2], slot[1].get(), slot[2].get()));
     return CRT_OK;
 }
 
@@ -4488,88 +4508,79 @@ float crt_renderer_last_kernel_ms(crt_renderer* R) {
     return t[0];
 }
 
+int crt_debug_live_allocations(int64_t* buffers, int64_t* bytes) {
+    if (!buffers || !bytes) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
+    *buffers = g_live_buffers.load();
+    *bytes = g_live_bytes.load();
+    return CRT_OK;
+}
+
 int crt_selftest_math(const float* a, const float* b, int n, float* out, double* out64) {
     if (!a || !b || !out || !out64 || n <= 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (int rc = use_device(0)) return rc;
-    float *da, *db, *dout;
-    double* d64;
-    HIP_TRY(hipMalloc((void**)&da, n * 4));
-    HIP_TRY(hipMalloc((void**)&db, n * 4));
-    HIP_TRY(hipMalloc((void**)&dout, n * 16));
-    HIP_TRY(hipMalloc((void**)&d64, n * 16));
-    HIP_TRY(hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(db, b, n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(crt_selftest_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, da, db, n, dout, d64);
+    DevBuf<float> da, db, dout;
+    DevBuf<double> d64;
+    HIP_TRY(da.alloc(n));
+    HIP_TRY(db.alloc(n));
+    HIP_TRY(dout.alloc(n * 4));
+    HIP_TRY(d64.alloc(n * 2));
+    HIP_TRY(hipMemcpy(da.get(), a, n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(db.get(), b, n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(crt_selftest_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, da.get(), db.get(), n, dout.get(),
+                       d64.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout, n * 16, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out64, d64, n * 16, hipMemcpyDeviceToHost));
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout); (void)hipFree(d64);
+    HIP_TRY(hipMemcpy(out, dout.get(), n * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out64, d64.get(), n * 16, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 
+// crt_selftest_rcp / crt_selftest_sqrt: `kernel` over the f32 bit patterns [lo_bits, hi_bits].
+static int selftest_bit_range(void (*kernel)(uint32_t, uint32_t, unsigned long long*, uint32_t*), uint32_t lo_bits,
+                              uint32_t hi_bits, unsigned long long* mismatches, uint32_t* first_bad) {
+    if (!mismatches || !first_bad) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (int rc = use_device(0)) return rc;
+    DevBuf<unsigned long long> dbad;
+    DevBuf<uint32_t> dfirst;
+    HIP_TRY(dbad.alloc(1));
+    HIP_TRY(dfirst.alloc(1));
+    HIP_TRY(hipMemset(dbad.get(), 0, 8));
+    HIP_TRY(hipMemset(dfirst.get(), 0xff, 4));
+    hipLaunchKernelGGL(kernel, dim3(8192), dim3(256), 0, 0, lo_bits, hi_bits, dbad.get(), dfirst.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(mismatches, dbad.get(), 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(first_bad, dfirst.get(), 4, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
 int crt_selftest_rcp(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* mismatches, uint32_t* first_bad) {
-    if (!mismatches || !first_bad) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    unsigned long long* dbad;
-    uint32_t* dfirst;
-    HIP_TRY(hipMalloc((void**)&dbad, 8));
-    HIP_TRY(hipMalloc((void**)&dfirst, 4));
-    HIP_TRY(hipMemset(dbad, 0, 8));
-    HIP_TRY(hipMemset(dfirst, 0xff, 4));
-    hipLaunchKernelGGL(crt_selftest_rcp_kernel, dim3(8192), dim3(256), 0, 0, lo_bits, hi_bits, dbad, dfirst);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(mismatches, dbad, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(first_bad, dfirst, 4, hipMemcpyDeviceToHost));
-    (void)hipFree(dbad);
-    (void)hipFree(dfirst);
-    return CRT_OK;
+    return selftest_bit_range(crt_selftest_rcp_kernel, lo_bits, hi_bits, mismatches, first_bad);
 }
-
 int crt_selftest_sqrt(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* mismatches, uint32_t* first_bad) {
-    if (!mismatches || !first_bad) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    unsigned long long* dbad;
-    uint32_t* dfirst;
-    HIP_TRY(hipMalloc((void**)&dbad, 8));
-    HIP_TRY(hipMalloc((void**)&dfirst, 4));
-    HIP_TRY(hipMemset(dbad, 0, 8));
-    HIP_TRY(hipMemset(dfirst, 0xff, 4));
-    hipLaunchKernelGGL(crt_selftest_sqrt_kernel, dim3(8192), dim3(256), 0, 0, lo_bits, hi_bits, dbad, dfirst);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(mismatches, dbad, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(first_bad, dfirst, 4, hipMemcpyDeviceToHost));
-    (void)hipFree(dbad);
-    (void)hipFree(dfirst);
-    return CRT_OK;
+    return selftest_bit_range(crt_selftest_sqrt_kernel, lo_bits, hi_bits, mismatches, first_bad);
 }
 
 int crt_selftest_unit(const float* in, int n, float* out) {
     if (!in || !out || n <= 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (int rc = use_device(0)) return rc;
-    float *din, *dout;
-    HIP_TRY(hipMalloc((void**)&din, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void**)&dout, (size_t)n * 12));
-    HIP_TRY(hipMemcpy(din, in, (size_t)n * 12, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(crt_selftest_unit_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, din, n, dout);
+    DevBuf<float> din, dout;
+    HIP_TRY(din.alloc((size_t)n * 3));
+    HIP_TRY(dout.alloc((size_t)n * 3));
+    HIP_TRY(hipMemcpy(din.get(), in, (size_t)n * 12, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(crt_selftest_unit_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, din.get(), n, dout.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 12, hipMemcpyDeviceToHost));
-    (void)hipFree(din);
-    (void)hipFree(dout);
+    HIP_TRY(hipMemcpy(out, dout.get(), (size_t)n * 12, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 
 int crt_selftest_scan(const int* in, int n_waves, int* out) {
     if (!in || !out || n_waves <= 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (int rc = use_device(0)) return rc;
-    int *din, *dout;
-    HIP_TRY(hipMalloc((void**)&din, (size_t)n_waves * 64 * 4));
-    HIP_TRY(hipMalloc((void**)&dout, (size_t)n_waves * 64 * 12));
-    HIP_TRY(hipMemcpy(din, in, (size_t)n_waves * 64 * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(crt_selftest_scan_kernel, dim3(n_waves), dim3(64), 0, 0, din, dout, n_waves);
+    DevBuf<int> din, dout;
+    HIP_TRY(din.alloc((size_t)n_waves * 64));
+    HIP_TRY(dout.alloc((size_t)n_waves * 64 * 3));
+    HIP_TRY(hipMemcpy(din.get(), in, (size_t)n_waves * 64 * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(crt_selftest_scan_kernel, dim3(n_waves), dim3(64), 0, 0, din.get(), dout.get(), n_waves);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout, (size_t)n_waves * 64 * 12, hipMemcpyDeviceToHost));
-    (void)hipFree(din);
-    (void)hipFree(dout);
+    HIP_TRY(hipMemcpy(out, dout.get(), (size_t)n_waves * 64 * 12, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 
@@ -4579,30 +4590,24 @@ int crt_selftest_geometry(int kind, const float* in, int n, const crt_camera_des
     if (kind < 0 || kind > 4 || !in || !out || n <= 0 || (kind == 3 && (!cam || !rng || width <= 0 || height <= 0)))
         return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (int rc = use_device(0)) return rc;
-    float *din, *dout;
-    uint32_t* drng = nullptr;
-    HIP_TRY(hipMalloc((void**)&din, (size_t)n * in_words[kind] * 4));
-    HIP_TRY(hipMalloc((void**)&dout, (size_t)n * out_words[kind] * 4));
-    if (kind == 3) HIP_TRY(hipMalloc((void**)&drng, (size_t)n * 24));
-    hipError_t e = hipMemcpy(din, in, (size_t)n * in_words[kind] * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && kind == 3) e = hipMemcpy(drng, rng, (size_t)n * 24, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        unsigned long long bad_w = 0, bad_h = 0;   // the renderer's choice for this size (crt_renderer_create)
-        if (kind == 3 && (uv_div_mismatches(width, &bad_w) != CRT_OK || uv_div_mismatches(height, &bad_h) != CRT_OK))
-            e = hipErrorUnknown;
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(crt_selftest_geometry_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, kind, din, n, dout,
-                               drng, cam ? *cam : crt_camera_desc{}, width, height, kind == 3 ? 1.0f / (float)width : 1.f,
-                               kind == 3 ? 1.0f / (float)height : 1.f, (int)(kind == 3 && bad_w == 0 && bad_h == 0));
-            e = hipGetLastError();
-        }
+    DevBuf<float> din, dout;
+    DevBuf<uint32_t> drng;
+    HIP_TRY(din.alloc((size_t)n * in_words[kind]));
+    HIP_TRY(dout.alloc((size_t)n * out_words[kind]));
+    if (kind == 3) HIP_TRY(drng.alloc((size_t)n * 6));
+    HIP_TRY(hipMemcpy(din.get(), in, (size_t)n * in_words[kind] * 4, hipMemcpyHostToDevice));
+    unsigned long long bad_w = 0, bad_h = 0;   // the renderer's choice for this size (crt_renderer_create)
+    if (kind == 3) {
+        HIP_TRY(hipMemcpy(drng.get(), rng, (size_t)n * 24, hipMemcpyHostToDevice));
+        if (int rc = uv_div_mismatches(width, &bad_w)) return rc;
+        if (int rc = uv_div_mismatches(height, &bad_h)) return rc;
     }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * out_words[kind] * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && kind == 3) e = hipMemcpy(rng, drng, (size_t)n * 24, hipMemcpyDeviceToHost);
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    if (drng) (void)hipFree(drng);
-    HIP_TRY(e);
+    hipLaunchKernelGGL(crt_selftest_geometry_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, kind, din.get(), n, dout.get(),
+                       drng.get(), cam ? *cam : crt_camera_desc{}, width, height, kind == 3 ? 1.0f / (float)width : 1.f,
+                       kind == 3 ? 1.0f / (float)height : 1.f, (int)(kind == 3 && bad_w == 0 && bad_h == 0));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dout.get(), (size_t)n * out_words[kind] * 4, hipMemcpyDeviceToHost));
+    if (kind == 3) HIP_TRY(hipMemcpy(rng, drng.get(), (size_t)n * 24, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 
@@ -4612,21 +4617,20 @@ int crt_selftest_rng(unsigned long long seed, const unsigned long long* subseq, 
         return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (int rc = use_device(0)) return rc;
     const auto& tab = seq_tables();
-    uint32_t *dseq, *dst;
-    float* du;
-    HIP_TRY(hipMalloc((void**)&dseq, tab.size() * 4));
-    HIP_TRY(hipMalloc((void**)&dst, (size_t)n * 24));
-    HIP_TRY(hipMalloc((void**)&du, (size_t)n * std::max(n_draw, 1) * 4));
-    HIP_TRY(hipMemcpy(dseq, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    DevBuf<uint32_t> dseq, dst;
+    DevBuf<float> du;
+    HIP_TRY(dseq.alloc(tab.size()));
+    HIP_TRY(dst.alloc((size_t)n * 6));
+    HIP_TRY(du.alloc((size_t)n * std::max(n_draw, 1)));
+    HIP_TRY(hipMemcpy(dseq.get(), tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     for (int i = 0; i < n; ++i) {   // one launch per subsequence keeps the kernel identical to the renderer's
-        hipLaunchKernelGGL(crt_init_rand_kernel, dim3(1), dim3(64), 0, 0, dst + 6 * i, dseq, 1, seed, subseq[i]);
+        hipLaunchKernelGGL(crt_init_rand_kernel, dim3(1), dim3(64), 0, 0, dst.get() + 6 * i, dseq.get(), 1, seed, subseq[i]);
     }
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(crt_selftest_rng_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, dst, n, n_draw, du);
+    hipLaunchKernelGGL(crt_selftest_rng_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, dst.get(), n, n_draw, du.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(state_out, dst, (size_t)n * 24, hipMemcpyDeviceToHost));
-    if (n_draw) HIP_TRY(hipMemcpy(uniforms_out, du, (size_t)n * n_draw * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(dseq); (void)hipFree(dst); (void)hipFree(du);
+    HIP_TRY(hipMemcpy(state_out, dst.get(), (size_t)n * 24, hipMemcpyDeviceToHost));
+    if (n_draw) HIP_TRY(hipMemcpy(uniforms_out, du.get(), (size_t)n * n_draw * 4, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 
@@ -4642,8 +4646,8 @@ int crt_selftest_tile_schedule(crt_renderer* R, const uint32_t* pix_cost, int st
     const size_t n_pix = (size_t)R->width * R->height;
     const int n_tiles = ((R->width + 7) / 8) * ((R->height + 7) / 8);
     if (int rc = ensure_order_buffers(R, 0, n_pix, n_tiles, true)) return rc;
-    HIP_TRY(hipMemset(R->d_order, 0xff, std::max(n_pix, (size_t)n_tiles * 64) * 4));
-    HIP_TRY(hipMemcpy(R->d_tile_cost, pix_cost, n_pix * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(R->d_order.get(), 0xff, std::max(n_pix, (size_t)n_tiles * 64) * 4));
+    HIP_TRY(hipMemcpy(R->d_tile_cost.get(), pix_cost, n_pix * 4, hipMemcpyHostToDevice));
     const int mode0 = R->tile_key_mode, xcd0 = R->xcd_regions;
     R->tile_key_mode = key_mode;
     R->xcd_regions = xcd_regions ? 1 : 0;
@@ -4653,7 +4657,7 @@ int crt_selftest_tile_schedule(crt_renderer* R, const uint32_t* pix_cost, int st
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(0));
-    if (stats_out) { stats_out[0] = R->h_probe_stats[0]; stats_out[1] = R->h_probe_stats[1]; }
+    if (stats_out) { stats_out[0] = R->h_probe_stats.get()[0]; stats_out[1] = R->h_probe_stats.get()[1]; }
     return CRT_OK;
 }
 
@@ -4665,11 +4669,11 @@ int crt_selftest_pixel_order(crt_renderer* R, int kind, const uint32_t* in, int 
     const size_t n_pix = (size_t)R->width * R->height;
     const int n_tiles = ((R->width + 7) / 8) * ((R->height + 7) / 8);
     if (int rc = ensure_order_buffers(R, 0, n_pix, n_tiles, kind == 3)) return rc;
-    HIP_TRY(hipMemset(R->d_order, 0xff, std::max(n_pix, (size_t)n_tiles * 64) * 4));
+    HIP_TRY(hipMemset(R->d_order.get(), 0xff, std::max(n_pix, (size_t)n_tiles * 64) * 4));
     int rc = CRT_OK;
     if (kind == 0) {
-        HIP_TRY(hipMemcpy(R->d_tile_cost, in, n_pix * 4, hipMemcpyHostToDevice));
-        rc = sort_descending(R, 0, R->d_tile_cost, (int)n_pix, R->d_order);
+        HIP_TRY(hipMemcpy(R->d_tile_cost.get(), in, n_pix * 4, hipMemcpyHostToDevice));
+        rc = sort_descending(R, 0, R->d_tile_cost.get(), (int)n_pix, R->d_order.get());
     } else if (kind == 3) {
         shard_tiles_in_row_order(R, 0, n_tiles, shard, shards);
     } else {
@@ -4679,8 +4683,8 @@ int crt_selftest_pixel_order(crt_renderer* R, int kind, const uint32_t* in, int 
         if (kind == 1) {
             if (!R->d_pix_rays) rc = order_tile_slots(R, 0);   // allocates the temporal buffers (row order this once)
             if (!rc) {
-                hipError_t e = hipMemcpy(R->d_pix_rays, in, n_pix * 4, hipMemcpyHostToDevice);
-                if (e == hipSuccess) e = hipMemset(R->d_order, 0xff, (size_t)n_tiles * 64 * 4);
+                hipError_t e = hipMemcpy(R->d_pix_rays.get(), in, n_pix * 4, hipMemcpyHostToDevice);
+                if (e == hipSuccess) e = hipMemset(R->d_order.get(), 0xff, (size_t)n_tiles * 64 * 4);
                 if (e != hipSuccess) rc = set_error(CRT_ERR_HIP, hipGetErrorString(e));
             }
             R->pix_rays_valid = true;
@@ -4703,11 +4707,11 @@ int crt_selftest_schedule_buffer(crt_renderer* R, int which, uint32_t* out, int6
     const uint32_t* src;
     size_t n;
     switch (which) {
-        case 0: src = R->d_order; n = std::max(n_pix, n_tiles * 64); break;
-        case 1: src = R->d_tile_key; n = n_tiles; break;
-        case 2: src = R->d_tile_cost; n = n_pix; break;
-        case 3: src = R->d_pix_rays; n = n_pix; break;
-        case 4: src = R->d_tile_order; n = n_tiles; break;
+        case 0: src = R->d_order.get(); n = std::max(n_pix, n_tiles * 64); break;
+        case 1: src = R->d_tile_key.get(); n = n_tiles; break;
+        case 2: src = R->d_tile_cost.get(); n = n_pix; break;
+        case 3: src = R->d_pix_rays.get(); n = n_pix; break;
+        case 4: src = R->d_tile_order.get(); n = n_tiles; break;
         default: return set_error(CRT_ERR_INVALID_ARGUMENT, "unknown schedule buffer");
     }
     if (!src) n = 0;

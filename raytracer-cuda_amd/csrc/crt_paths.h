@@ -487,8 +487,8 @@ int advance_enqueue(const std::string& what, const crt_scene* S, crt_renderer* R
     Q.rays = reinterpret_cast<const float4*>(d_rays);
     Q.hits = reinterpret_cast<const float4*>(d_hits);
     Q.paths = reinterpret_cast<const float4*>(d_paths);
-    Q.rows = S->d_mat_rows;
-    Q.rng = d_rng ? d_rng : R->d_rng;
+    Q.rows = S->d_mat_rows.get();
+    Q.rng = d_rng ? d_rng : R->d_rng.get();
     Q.linear = d_linear ? d_linear : R->d_sum;
     Q.remaining = d_remaining;
     Q.rays_out = reinterpret_cast<float4*>(d_rays_out);
@@ -532,7 +532,7 @@ int crt_renderer_camera_rays_device(crt_renderer* R, const int32_t* d_pixels, in
     set_camera_frame(Q, R);
     Q.pixels = d_pixels;
     Q.n = (uint32_t)n;
-    Q.rng = d_rng ? d_rng : R->d_rng;
+    Q.rng = d_rng ? d_rng : R->d_rng.get();
     Q.rays = reinterpret_cast<float4*>(d_rays);
     Q.paths = reinterpret_cast<float4*>(d_paths);
     hipLaunchKernelGGL(crt_camera_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Q);
@@ -556,7 +556,7 @@ int crt_scene_path_step_device(const crt_scene* S, crt_ray* d_rays, const crt_hi
     Q.rays = reinterpret_cast<float4*>(d_rays);
     Q.hits = reinterpret_cast<const float4*>(d_hits);
     Q.paths = reinterpret_cast<float4*>(d_paths);
-    Q.rows = S->d_mat_rows;
+    Q.rows = S->d_mat_rows.get();
     Q.rng = d_rng;
     Q.linear = d_linear;
     Q.n = (uint32_t)n;
@@ -608,13 +608,13 @@ int crt_scene_path_finish_device(const crt_scene* S, crt_renderer* R, const crt_
     PathFinishParams Q{};
     Q.rays = reinterpret_cast<const float4*>(d_rays);
     Q.paths = reinterpret_cast<const float4*>(d_paths);
-    Q.nodes = S->d_nodes; Q.prims = S->d_prims; Q.chain = S->d_chain; Q.shade = S->d_shade;
-    Q.ident = S->d_ident;
-    Q.rows = S->d_mat_rows;
+    Q.nodes = S->d_nodes.get(); Q.prims = S->d_prims.get(); Q.chain = S->d_chain.get(); Q.shade = S->d_shade.get();
+    Q.ident = S->d_ident.get();
+    Q.rows = S->d_mat_rows.get();
     Q.n_nodes = S->n_nodes; Q.n_layouts = S->layouts; Q.n_chain = S->n_chain;
     Q.sphere_first = S->sphere_first; Q.n_ray_spheres = S->n_ray_spheres;
     Q.scene_width = S->width;
-    Q.rng = d_rng ? d_rng : R->d_rng;
+    Q.rng = d_rng ? d_rng : R->d_rng.get();
     Q.linear = d_linear ? d_linear : R->d_sum;
     Q.remaining = d_remaining;
     Q.d_n = d_n;
@@ -631,20 +631,6 @@ int crt_scene_path_finish_device(const crt_scene* S, crt_renderer* R, const crt_
 
 }  // extern "C"
 
-// The wavefront loop's scratch: owned by the renderer handle, allocated on first use, freed with the handle.
-struct WavefrontScratch {
-    crt_ray* rays[2] = {nullptr, nullptr};
-    crt_path* paths[2] = {nullptr, nullptr};
-    crt_hit* hits = nullptr;
-    int32_t* remaining = nullptr;
-    uint32_t* d_count = nullptr;
-    uint32_t* h_count = nullptr;            // pinned: [0] the count, [2..3] the trace error word
-    // the queued loop (crt_renderer_render_wavefront_queued): 8 device words and their pinned copy
-    uint32_t* d_queue = nullptr;            // [0], [1] the ping-pong counts, [2] the sticky error word, [4..7] the totals
-    uint32_t* h_queue = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-};
-
 constexpr int QUEUE_WORDS = 8, QUEUE_ERR = 2, QUEUE_TOTALS = 4;   // WavefrontScratch::d_queue
 // crt_renderer_render_wavefront_queued's sync_every = 0: iterations enqueued between two host waits
 // (profiles/indirect/path_bench.jsonl)
@@ -654,51 +640,31 @@ constexpr int QUEUE_SYNC_EVERY = 32;
 // 1280x720 frame, the whole frame through the finish kernel (15.5 ms against 27.5 ms at 0).  Larger frames were not measured.
 constexpr int64_t QUEUE_FINISH_BELOW = 921600;
 
-void crtx_free_wavefront_scratch(crt_renderer* R) {
-    WavefrontScratch* X = R->wavefront;
-    if (!X) return;
-    for (int k = 0; k < 2; ++k) {
-        if (X->rays[k]) (void)hipFree(X->rays[k]);
-        if (X->paths[k]) (void)hipFree(X->paths[k]);
-    }
-    if (X->hits) (void)hipFree(X->hits);
-    if (X->remaining) (void)hipFree(X->remaining);
-    if (X->d_count) (void)hipFree(X->d_count);
-    if (X->h_count) (void)hipHostFree(X->h_count);
-    if (X->d_queue) (void)hipFree(X->d_queue);
-    if (X->h_queue) (void)hipHostFree(X->h_queue);
-    if (X->ev0) (void)hipEventDestroy(X->ev0);
-    if (X->ev1) (void)hipEventDestroy(X->ev1);
-    delete X;
-    R->wavefront = nullptr;
-}
-
 namespace {
 
 int wavefront_scratch(crt_renderer* R, WavefrontScratch** out) {
     if (!R->wavefront) {
-        WavefrontScratch* X = new (std::nothrow) WavefrontScratch;
+        R->wavefront.reset(new (std::nothrow) WavefrontScratch);   // whatever is allocated below is freed with the handle
+        WavefrontScratch* X = R->wavefront.get();
         if (!X) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-        R->wavefront = X;   // whatever is allocated below is freed with the handle
         const size_t n_pix = (size_t)R->width * R->height;
         for (int k = 0; k < 2; ++k) {
-            HIP_TRY(hipMalloc((void**)&X->rays[k], n_pix * sizeof(crt_ray)));
-            HIP_TRY(hipMalloc((void**)&X->paths[k], n_pix * sizeof(crt_path)));
+            HIP_TRY(X->rays[k].alloc(n_pix));
+            HIP_TRY(X->paths[k].alloc(n_pix));
         }
-        HIP_TRY(hipMalloc((void**)&X->hits, n_pix * sizeof(crt_hit)));
-        HIP_TRY(hipMalloc((void**)&X->remaining, n_pix * 4));
-        HIP_TRY(hipMalloc((void**)&X->d_count, 4));
-        HIP_TRY(hipHostMalloc((void**)&X->h_count, 16));
-        HIP_TRY(hipMalloc((void**)&X->d_queue, QUEUE_WORDS * 4));
-        HIP_TRY(hipHostMalloc((void**)&X->h_queue, QUEUE_WORDS * 4));
-        HIP_TRY(hipEventCreate(&X->ev0));
-        HIP_TRY(hipEventCreate(&X->ev1));
+        HIP_TRY(X->hits.alloc(n_pix));
+        HIP_TRY(X->remaining.alloc(n_pix));
+        HIP_TRY(X->d_count.alloc(1));
+        HIP_TRY(X->h_count.alloc(4));
+        HIP_TRY(X->d_queue.alloc(QUEUE_WORDS));
+        HIP_TRY(X->h_queue.alloc(QUEUE_WORDS));
+        HIP_TRY(X->ev0.create());
+        HIP_TRY(X->ev1.create());
+        X->ready = true;
     }
-    WavefrontScratch* X = R->wavefront;
-    if (!X->rays[1] || !X->paths[1] || !X->hits || !X->remaining || !X->d_count || !X->h_count || !X->d_queue ||
-        !X->h_queue || !X->ev1)
+    if (!R->wavefront->ready)
         return set_error(CRT_ERR_OUT_OF_MEMORY, "the wavefront scratch of this renderer could not be allocated");
-    *out = X;
+    *out = R->wavefront.get();
     return CRT_OK;
 }
 
@@ -733,34 +699,37 @@ int crt_renderer_render_wavefront(crt_renderer* R, const crt_scene* Sc, int spp,
     }
     WavefrontScratch* X = nullptr;
     if (int rc = wavefront_scratch(R, &X)) return rc;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->remaining, spp - 1, (size_t)n_pix, st));
-    HIP_TRY(hipEventRecord(X->ev0, st));
-    if (int rc = crt_renderer_camera_rays_device(R, nullptr, n_pix, nullptr, X->rays[0], X->paths[0], stream)) return rc;
+    uint32_t* const h_count = X->h_count.get();
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->remaining.get(), spp - 1, (size_t)n_pix, st));
+    HIP_TRY(hipEventRecord(X->ev0.get(), st));
+    if (int rc = crt_renderer_camera_rays_device(R, nullptr, n_pix, nullptr, X->rays[0].get(), X->paths[0].get(), stream))
+        return rc;
     int cur = 0;
     int64_t m = n_pix;
     while (m > 0) {
         stats.rays += (uint64_t)m;
         ++stats.iterations;
-        if (int rc = trace_enqueue(S, X->rays[cur], m, trace_opts, X->hits, nullptr, 0, st)) return rc;
-        if (int rc = crt_scene_path_advance_device(S, R, X->rays[cur], X->hits, X->paths[cur], m, max_bounces, nullptr,
-                                                   nullptr, X->remaining, X->rays[cur ^ 1], X->paths[cur ^ 1],
-                                                   X->d_count, stream))
+        if (int rc = trace_enqueue(S, X->rays[cur].get(), m, trace_opts, X->hits.get(), nullptr, 0, st)) return rc;
+        if (int rc = crt_scene_path_advance_device(S, R, X->rays[cur].get(), X->hits.get(), X->paths[cur].get(), m,
+                                                   max_bounces, nullptr, nullptr, X->remaining.get(),
+                                                   X->rays[cur ^ 1].get(), X->paths[cur ^ 1].get(), X->d_count.get(),
+                                                   stream))
             return rc;
         // the size of the next batch and this query's error word (the next query clears it), then the loop's one host wait
-        HIP_TRY(hipMemcpyAsync(X->h_count, X->d_count, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(X->h_count + 2, S->trace->d_stats + TRACE_ERR_WORD, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_count, X->d_count.get(), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_count + 2, S->trace->d_stats.get() + TRACE_ERR_WORD, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        m = std::min<int64_t>(X->h_count[0], n_pix);
+        m = std::min<int64_t>(h_count[0], n_pix);
         cur ^= 1;
-        if (X->h_count[2] | X->h_count[3]) break;            // reported below, as trace_take_error words it
+        if (h_count[2] | h_count[3]) break;                  // reported below, as trace_take_error words it
     }
-    HIP_TRY(hipEventRecord(X->ev1, st));
-    HIP_TRY(hipEventSynchronize(X->ev1));
-    HIP_TRY(hipEventElapsedTime(&stats.ms, X->ev0, X->ev1));
+    HIP_TRY(hipEventRecord(X->ev1.get(), st));
+    HIP_TRY(hipEventSynchronize(X->ev1.get()));
+    HIP_TRY(hipEventElapsedTime(&stats.ms, X->ev0.get(), X->ev1.get()));
     if (stats_out) *stats_out = stats;
-    if (X->h_count[2] | X->h_count[3])
-        HIP_TRY(hipMemcpy(S->trace->d_stats + TRACE_ERR_WORD, X->h_count + 2, 8, hipMemcpyHostToDevice));
-    return trace_take_error(S->trace);
+    if (h_count[2] | h_count[3])
+        HIP_TRY(hipMemcpy(S->trace->d_stats.get() + TRACE_ERR_WORD, h_count + 2, 8, hipMemcpyHostToDevice));
+    return trace_take_error(S->trace.get());
 }
 
 }  // extern "C"
@@ -804,14 +773,16 @@ int wavefront_queued(crt_renderer* R, const crt_scene* Sc, int spp, int max_boun
     }
     WavefrontScratch* X = nullptr;
     if (int rc = wavefront_scratch(R, &X)) return rc;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->remaining, spp - 1, (size_t)n_pix, st));
+    uint32_t *const d_queue = X->d_queue.get(), *const h_queue = X->h_queue.get();
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->remaining.get(), spp - 1, (size_t)n_pix, st));
     // the error word and the totals are cleared once per call; the first batch is every pixel
-    HIP_TRY(hipMemsetAsync(X->d_queue, 0, QUEUE_WORDS * 4, st));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->d_queue, (int)n_pix, 1, st));
-    HIP_TRY(hipEventRecord(X->ev0, st));
-    if (int rc = crt_renderer_camera_rays_device(R, nullptr, n_pix, nullptr, X->rays[0], X->paths[0], stream)) return rc;
-    unsigned* d_err = X->d_queue + QUEUE_ERR;
-    uint64_t* d_totals = reinterpret_cast<uint64_t*>(X->d_queue + QUEUE_TOTALS);
+    HIP_TRY(hipMemsetAsync(d_queue, 0, QUEUE_WORDS * 4, st));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_queue, (int)n_pix, 1, st));
+    HIP_TRY(hipEventRecord(X->ev0.get(), st));
+    if (int rc = crt_renderer_camera_rays_device(R, nullptr, n_pix, nullptr, X->rays[0].get(), X->paths[0].get(), stream))
+        return rc;
+    unsigned* d_err = d_queue + QUEUE_ERR;
+    uint64_t* d_totals = reinterpret_cast<uint64_t*>(d_queue + QUEUE_TOTALS);
     int cur = 0;
     // A batch is never larger than the one before it (an input entry appends at most one output entry), so the last
     // count the host read bounds every later one: it is the capacity of the whole block.  Iterations enqueued after the
@@ -819,43 +790,45 @@ int wavefront_queued(crt_renderer* R, const crt_scene* Sc, int spp, int max_boun
     int64_t m = n_pix;
     while (m > 0) {
         if (m <= finish_below) {                             // the hand-off: the lanes run their pixels to the end
-            if (int rc = crt_scene_path_finish_device(S, R, X->rays[cur], X->paths[cur], X->d_queue + cur, m, max_bounces,
-                                                      nullptr, nullptr, X->remaining, d_totals, stream))
+            if (int rc = crt_scene_path_finish_device(S, R, X->rays[cur].get(), X->paths[cur].get(), d_queue + cur, m,
+                                                      max_bounces, nullptr, nullptr, X->remaining.get(), d_totals, stream))
                 return rc;
-            HIP_TRY(hipMemcpyAsync(X->h_queue, X->d_queue, QUEUE_WORDS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(h_queue, d_queue, QUEUE_WORDS * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             break;
         }
         for (int k = 0; k < block; ++k) {
-            if (int rc = trace_enqueue(S, X->rays[cur], m, trace_opts, X->hits, nullptr, 0, st, X->d_queue + cur, d_err))
+            if (int rc = trace_enqueue(S, X->rays[cur].get(), m, trace_opts, X->hits.get(), nullptr, 0, st, d_queue + cur,
+                                       d_err))
                 return rc;
-            if (int rc = crt_scene_path_advance_indirect_device(S, R, X->rays[cur], X->hits, X->paths[cur], X->d_queue + cur,
-                                                                m, max_bounces, nullptr, nullptr, X->remaining,
-                                                                X->rays[cur ^ 1], X->paths[cur ^ 1], X->d_queue + (cur ^ 1),
-                                                                d_totals, stream))
+            if (int rc = crt_scene_path_advance_indirect_device(S, R, X->rays[cur].get(), X->hits.get(),
+                                                                X->paths[cur].get(), d_queue + cur, m, max_bounces, nullptr,
+                                                                nullptr, X->remaining.get(), X->rays[cur ^ 1].get(),
+                                                                X->paths[cur ^ 1].get(), d_queue + (cur ^ 1), d_totals,
+                                                                stream))
                 return rc;
             cur ^= 1;
         }
         // the block's one copy (the counts, the error word, the totals) and its one host wait
-        HIP_TRY(hipMemcpyAsync(X->h_queue, X->d_queue, QUEUE_WORDS * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_queue, d_queue, QUEUE_WORDS * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        m = std::min<int64_t>(X->h_queue[cur], m);
-        if (X->h_queue[QUEUE_ERR]) break;                    // reported below, as trace_take_error words it
+        m = std::min<int64_t>(h_queue[cur], m);
+        if (h_queue[QUEUE_ERR]) break;                          // reported below, as trace_take_error words it
     }
-    HIP_TRY(hipEventRecord(X->ev1, st));
-    HIP_TRY(hipEventSynchronize(X->ev1));
-    HIP_TRY(hipEventElapsedTime(&stats.ms, X->ev0, X->ev1));
+    HIP_TRY(hipEventRecord(X->ev1.get(), st));
+    HIP_TRY(hipEventSynchronize(X->ev1.get()));
+    HIP_TRY(hipEventElapsedTime(&stats.ms, X->ev0.get(), X->ev1.get()));
     uint64_t totals[2];
-    std::memcpy(totals, X->h_queue + QUEUE_TOTALS, sizeof totals);
+    std::memcpy(totals, h_queue + QUEUE_TOTALS, sizeof totals);
     stats.rays = totals[0];
     stats.iterations = (uint32_t)totals[1];
     if (stats_out) *stats_out = stats;
-    if (X->h_queue[QUEUE_ERR]) {                             // into the handle's own word, for trace_take_error's report
-        const unsigned long long word = X->h_queue[QUEUE_ERR];
-        HIP_TRY(hipMemcpy(S->trace->d_stats + TRACE_ERR_WORD, &word, 8, hipMemcpyHostToDevice));
+    if (h_queue[QUEUE_ERR]) {                                   // into the handle's own word, for trace_take_error's report
+        const unsigned long long word = h_queue[QUEUE_ERR];
+        HIP_TRY(hipMemcpy(S->trace->d_stats.get() + TRACE_ERR_WORD, &word, 8, hipMemcpyHostToDevice));
     }
     // a frame handed over before its first round ran no query: a scene that was never traced has no scratch to ask
-    return S->trace ? trace_take_error(S->trace) : CRT_OK;
+    return S->trace ? trace_take_error(S->trace.get()) : CRT_OK;
 }
 
 }  // namespace

@@ -122,55 +122,29 @@ constexpr int64_t TRACE_STAGE_RAYS = (int64_t)1 << 20;    // rays per chunk of t
 constexpr int64_t TRACE_STREAM_MIN_RAYS = (int64_t)1 << 20;   // automatic mode: queries from this size take the stream kernel
 constexpr int TRACE4_STACK = 64;             // trace4's per-lane stack (int stack[64] in crt_hip.hip)
 
-struct TraceScratch {
-    uint32_t* d_next = nullptr;
-    unsigned long long* d_stats = nullptr;
-    uint32_t* d_ovf = nullptr;               // stack entries beyond the LDS part, per grid lane
-    size_t ovf_bytes = 0;
-    float4* d_rays = nullptr;                // staging of the host-pointer entries
-    float4* d_hits = nullptr;
-    unsigned char* d_occ = nullptr;
-    int64_t stage_rays = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool traced = false;
-    int n_cus = 0, wg_per_cu = 0;
-};
-
-void crtx_free_trace_scratch(crt_scene* S) {
-    TraceScratch* X = S->trace;
-    if (!X) return;
-    if (X->d_next) (void)hipFree(X->d_next);
-    if (X->d_stats) (void)hipFree(X->d_stats);
-    if (X->d_ovf) (void)hipFree(X->d_ovf);
-    if (X->d_rays) (void)hipFree(X->d_rays);
-    if (X->d_hits) (void)hipFree(X->d_hits);
-    if (X->d_occ) (void)hipFree(X->d_occ);
-    if (X->ev0) (void)hipEventDestroy(X->ev0);
-    if (X->ev1) (void)hipEventDestroy(X->ev1);
-    delete X;
-    S->trace = nullptr;
-}
-
 namespace {
 
 int trace_scratch(crt_scene* S, TraceScratch** out) {
     if (!S->trace) {
-        TraceScratch* X = new (std::nothrow) TraceScratch;
+        S->trace.reset(new (std::nothrow) TraceScratch);   // whatever is allocated below is freed with the handle
+        TraceScratch* X = S->trace.get();
         if (!X) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-        S->trace = X;   // whatever is allocated below is freed with the handle
-        HIP_TRY(hipMalloc((void**)&X->d_next, 4));
-        HIP_TRY(hipMalloc((void**)&X->d_stats, TRACE_STAT_WORDS * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(X->d_stats, 0, TRACE_STAT_WORDS * sizeof(unsigned long long)));
-        HIP_TRY(hipEventCreate(&X->ev0));
-        HIP_TRY(hipEventCreate(&X->ev1));
+        HIP_TRY(X->d_next.alloc(1));
+        HIP_TRY(X->d_stats.alloc(TRACE_STAT_WORDS));
+        HIP_TRY(hipMemset(X->d_stats.get(), 0, TRACE_STAT_WORDS * sizeof(unsigned long long)));
+        HIP_TRY(X->ev0.create());
+        HIP_TRY(X->ev1.create());
         HIP_TRY(hipDeviceGetAttribute(&X->n_cus, hipDeviceAttributeMultiprocessorCount, S->device));
         // the persistent grid fills the device once: CUs x the stream kernel's resident workgroups per CU
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, crt_trace_kernel<false, false>, 64, 0) != hipSuccess || nb <= 0)
             nb = 4 * 6;
         X->wg_per_cu = nb;
+        X->ready = true;
     }
-    *out = S->trace;
+    if (!S->trace->ready)
+        return set_error(CRT_ERR_OUT_OF_MEMORY, "the trace scratch of this scene could not be allocated");
+    *out = S->trace.get();
     return CRT_OK;
 }
 
@@ -210,20 +184,20 @@ int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trac
 
     TraceParams T{};
     RenderParams& P = T.P;
-    P.nodes = S->d_nodes; P.prims = S->d_prims; P.mats = S->d_mats; P.shade = S->d_shade;
+    P.nodes = S->d_nodes.get(); P.prims = S->d_prims.get(); P.mats = S->d_mats.get(); P.shade = S->d_shade.get();
     P.n_nodes = S->n_nodes; P.n_mats = S->n_mats; P.n_prims = S->n_prims; P.n_layouts = S->layouts;
-    P.err = d_err ? d_err : reinterpret_cast<unsigned*>(X->d_stats + TRACE_ERR_WORD);
+    P.err = d_err ? d_err : reinterpret_cast<unsigned*>(X->d_stats.get() + TRACE_ERR_WORD);
     P.top_levels = CRT_TOP_LEVELS;
     P.stack_cap = S->stack_cap;
     P.sphere_first = S->sphere_first;
     P.n_ray_spheres = S->n_ray_spheres;
-    P.sphere_chain = S->d_chain;
+    P.sphere_chain = S->d_chain.get();
     P.n_chain = S->n_chain;
     P.tree_spheres = S->tree_spheres;
     std::memcpy(P.sph2, S->sph2, sizeof P.sph2);
-    T.ident = S->d_ident;
-    T.next = X->d_next;
-    T.stats = X->d_stats;
+    T.ident = S->d_ident.get();
+    T.next = X->d_next.get();
+    T.stats = X->d_stats.get();
     T.refill_threshold = o.refill_threshold ? o.refill_threshold : 44;   // the 4-wide render variants' threshold
     T.width = S->width;
     // the stream kernel's stack split: CRT_STACK6 entries per lane in LDS at the most, the rest per grid lane in HBM
@@ -234,18 +208,14 @@ int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trac
         const size_t need = (size_t)(S->stack_cap - P.stack_lds) * (size_t)full_grid * 64 * 4;
         if (need >= ((size_t)1 << 32))
             return set_error(CRT_ERR_INVALID_ARGUMENT, "traversal-stack overflow region would exceed 4 GiB");
-        if (need > X->ovf_bytes) {
+        if (need / 4 > X->d_ovf.size()) {
             HIP_TRY(hipStreamSynchronize(st));
-            if (X->d_ovf) (void)hipFree(X->d_ovf);
-            X->d_ovf = nullptr;
-            X->ovf_bytes = 0;
-            HIP_TRY(hipMalloc((void**)&X->d_ovf, need));
-            X->ovf_bytes = need;
+            HIP_TRY(X->d_ovf.grow(need / 4));
         }
-        P.ovf = X->d_ovf;
+        P.ovf = X->d_ovf.get();
     }
     // the counts and the error word of this query (crt_scene_trace_last_stats)
-    HIP_TRY(hipMemsetAsync(X->d_stats, 0, TRACE_STAT_WORDS * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(X->d_stats.get(), 0, TRACE_STAT_WORDS * sizeof(unsigned long long), st));
     const bool any = d_hits == nullptr;   // only the occlusion byte is wanted: lanes retire at the first accepted hit
     for (int64_t at = 0; at < n; at += TRACE_LAUNCH_RAYS) {
         const int64_t m = std::min(n - at, TRACE_LAUNCH_RAYS);
@@ -261,8 +231,8 @@ int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trac
             // (measured on 3.7 M primary / bounce rays over the full grid: 128 -> 0.59 / 0.49 ms, 256 -> 0.45 / 0.36,
             // 512 -> 0.38 / 0.34, 1024 -> 0.38 / 0.39, 2048 -> 0.44 / 0.53: larger blocks leave the last waves a tail)
             T.block = 64u * (uint32_t)std::min<int64_t>(8, std::max<int64_t>(1, m / (64 * std::max<int64_t>(waves, 1))));
-            HIP_TRY(hipMemsetAsync(X->d_next, 0, 4, st));
-            if (at == 0) HIP_TRY(hipEventRecord(X->ev0, st));   // kernel_ms: from the first kernel, after the counter's reset
+            HIP_TRY(hipMemsetAsync(X->d_next.get(), 0, 4, st));
+            if (at == 0) HIP_TRY(hipEventRecord(X->ev0.get(), st));   // kernel_ms: from the first kernel, after the counter's reset
             if (d_n) {                           // T.block stays unused: the kernel derives it from the count it reads
                 const TraceIndirectParams I{T, d_n};
                 if (any) {
@@ -281,7 +251,7 @@ int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trac
             }
         } else {
             const dim3 grid((unsigned)((m + 255) / 256)), block(256);
-            if (at == 0) HIP_TRY(hipEventRecord(X->ev0, st));
+            if (at == 0) HIP_TRY(hipEventRecord(X->ev0.get(), st));
             if (d_n) {
                 const TraceIndirectParams I{T, d_n};
                 if (cnt) hipLaunchKernelGGL((crt_trace_lane_indirect_kernel<true>), grid, block, 0, st, I);
@@ -291,16 +261,16 @@ int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trac
         }
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(X->ev1, st));
+    HIP_TRY(hipEventRecord(X->ev1.get(), st));
     X->traced = true;
     return CRT_OK;
 }
 
 int trace_take_error(TraceScratch* X) {
     unsigned long long word = 0;
-    HIP_TRY(hipMemcpy(&word, X->d_stats + TRACE_ERR_WORD, sizeof word, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&word, X->d_stats.get() + TRACE_ERR_WORD, sizeof word, hipMemcpyDeviceToHost));
     if (!word) return CRT_OK;
-    HIP_TRY(hipMemset(X->d_stats + TRACE_ERR_WORD, 0, sizeof word));
+    HIP_TRY(hipMemset(X->d_stats.get() + TRACE_ERR_WORD, 0, sizeof word));
     std::string m = "trace kernel reported an internal error:";
     if (word & 1u) m += " primitive index out of range;";
     if (word & 2u) m += " traversal stack deeper than the scene's stack bound (entries dropped);";
@@ -320,29 +290,22 @@ int trace_host(const crt_scene* Sc, const crt_ray* rays, int64_t n, const crt_tr
     TraceScratch* X = nullptr;
     if (int rc = trace_scratch(S, &X)) return rc;
     const int64_t chunk = std::min(n, TRACE_STAGE_RAYS);
-    if (chunk > X->stage_rays) {
+    const size_t c = (size_t)chunk;
+    if (c > X->d_rays.size() || c > X->d_hits.size() || c > X->d_occ.size()) {   // the three grow together
         HIP_TRY(hipDeviceSynchronize());
-        if (X->d_rays) (void)hipFree(X->d_rays);
-        if (X->d_hits) (void)hipFree(X->d_hits);
-        if (X->d_occ) (void)hipFree(X->d_occ);
-        X->d_rays = X->d_hits = nullptr;
-        X->d_occ = nullptr;
-        X->stage_rays = 0;
-        HIP_TRY(hipMalloc((void**)&X->d_rays, (size_t)chunk * sizeof(crt_ray)));
-        HIP_TRY(hipMalloc((void**)&X->d_hits, (size_t)chunk * sizeof(crt_hit)));
-        HIP_TRY(hipMalloc((void**)&X->d_occ, (size_t)chunk));
-        X->stage_rays = chunk;
+        HIP_TRY(X->d_rays.grow(c));
+        HIP_TRY(X->d_hits.grow(c));
+        HIP_TRY(X->d_occ.grow(c));
     }
     for (int64_t at = 0; at < n; at += chunk) {
         const int64_t m = std::min(n - at, chunk);
-        HIP_TRY(hipMemcpy(X->d_rays, rays + at, (size_t)m * sizeof(crt_ray), hipMemcpyHostToDevice));
-        if (int rc = trace_enqueue(S, reinterpret_cast<const crt_ray*>(X->d_rays), m, opts,
-                                   hits ? reinterpret_cast<crt_hit*>(X->d_hits) : nullptr, occ ? X->d_occ : nullptr, 0,
-                                   nullptr))
+        HIP_TRY(hipMemcpy(X->d_rays.get(), rays + at, (size_t)m * sizeof(crt_ray), hipMemcpyHostToDevice));
+        if (int rc = trace_enqueue(S, X->d_rays.get(), m, opts, hits ? X->d_hits.get() : nullptr,
+                                   occ ? X->d_occ.get() : nullptr, 0, nullptr))
             return rc;
         HIP_TRY(hipStreamSynchronize(nullptr));
-        if (hits) HIP_TRY(hipMemcpy(hits + at, X->d_hits, (size_t)m * sizeof(crt_hit), hipMemcpyDeviceToHost));
-        if (occ) HIP_TRY(hipMemcpy(occ + at, X->d_occ, (size_t)m, hipMemcpyDeviceToHost));
+        if (hits) HIP_TRY(hipMemcpy(hits + at, X->d_hits.get(), (size_t)m * sizeof(crt_hit), hipMemcpyDeviceToHost));
+        if (occ) HIP_TRY(hipMemcpy(occ + at, X->d_occ.get(), (size_t)m, hipMemcpyDeviceToHost));
         if (int rc = trace_take_error(X)) return rc;
     }
     return CRT_OK;
@@ -407,13 +370,13 @@ int crt_scene_trace_indirect_device(const crt_scene* S, const crt_ray* d_rays, c
 int crt_scene_trace_last_stats(const crt_scene* S, crt_trace_stats* out) {
     if (!S || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
     *out = crt_trace_stats{};
-    TraceScratch* X = S->trace;
+    TraceScratch* X = S->trace.get();
     if (!X || !X->traced) return set_error(CRT_ERR_INVALID_ARGUMENT, "no trace on this scene yet");
     HIP_TRY(hipSetDevice(S->device));
-    HIP_TRY(hipEventSynchronize(X->ev1));
-    HIP_TRY(hipEventElapsedTime(&out->kernel_ms, X->ev0, X->ev1));
+    HIP_TRY(hipEventSynchronize(X->ev1.get()));
+    HIP_TRY(hipEventElapsedTime(&out->kernel_ms, X->ev0.get(), X->ev1.get()));
     unsigned long long w[TRACE_STAT_WORDS];
-    HIP_TRY(hipMemcpy(w, X->d_stats, sizeof w, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(w, X->d_stats.get(), sizeof w, hipMemcpyDeviceToHost));
     out->rays = w[0]; out->box_tests = w[1]; out->tri_tests = w[2]; out->sphere_tests = w[3];
     out->step_lane_slots = w[4]; out->step_active_lanes = w[5];
     return trace_take_error(X);
