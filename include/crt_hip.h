@@ -682,6 +682,14 @@ int crt_renderer_timing_history(crt_renderer* r, int back, float out[3]);
 /* Template instantiation of the last render-kernel launch as rocprofv3 names it, e.g.
  * "crt_render_kernel<false, 4, 6>" (empty before the first launch and for variant 5). */
 const char* crt_renderer_last_kernel_name(const crt_renderer* r);
+/* Which twin of that kernel the last render launched.  The plain variant-8 kernels ("crt_render_kernel<false, 8, W>")
+ * exist twice under that one name: a frozen twin, in which the knobs of a default launch are compile-time constants
+ * (every LDS stack entry of W in use, the LDS root step, no spheres in the tree, two per-ray spheres, one layout, no
+ * probe, the default wave_drain and regeneration threshold), and an open twin that reads them per launch.  The
+ * library picks per launch; both give the same bits for the same inputs.  1 = the frozen twin ran; 0 = the open twin,
+ * any other kernel, no launch yet, or r == NULL.  Added within ABI 3: a caller that may load an older library looks
+ * the symbol up first. */
+int crt_renderer_last_launch_frozen(const crt_renderer* r);
 
 /* ---- GPU-parallel mesh BVH build (replaces Mesh::buildBVHMesh <<<1,1>>>, Mesh.cuh:121-264, and the Mesh ctor
  * box, Mesh.cuh:39-47; launched by initMesh, CUDAKernels.h:28-33) ----

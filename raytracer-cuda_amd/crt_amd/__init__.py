@@ -554,6 +554,12 @@ class Renderer:
     def last_kernel_name(self) -> str:
         return (_lib.hip().crt_renderer_last_kernel_name(self.h) or b"").decode()
 
+    def last_launch_frozen(self) -> int:
+        """Which twin of last_kernel_name() the last render launched (crt_renderer_last_launch_frozen): 1 = the frozen
+        twin of a plain variant-8 kernel, 0 = its open twin or any other kernel.  Raises CrtError naming the entry when
+        the loaded library predates it."""
+        return int(_lib.require("crt_renderer_last_launch_frozen")(self.h))
+
     def last_schedule(self) -> dict:
         """The last variant-8 render's occupancy choice (crt_renderer_last_schedule): rho = the probe's largest tile work
         over the mean work per occupancy-6 wave slot (0 without the probe-based choice), the occupancy launched, and the

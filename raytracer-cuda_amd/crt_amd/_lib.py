@@ -179,10 +179,11 @@ HIP_SYMBOLS = [
     "crt_renderer_read_tile_error", "crt_renderer_read_adaptive_prev", "crt_selftest_adaptive_plan",
     "crt_renderer_compute_guides", "crt_renderer_denoise", "crt_renderer_resolve_denoised",
     "crt_renderer_read_denoised", "crt_renderer_read_guides", "crt_renderer_denoised_device_ptr", "crt_selftest_denoise",
-    "crt_renderer_denoise_iteration_ms", "crt_debug_live_allocations",
+    "crt_renderer_denoise_iteration_ms", "crt_debug_live_allocations", "crt_renderer_last_launch_frozen",
 ]
 # Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, the
-# schedule self-tests, the path finish, adaptive sampling, the denoiser, then the live-allocation count): bound when the loaded
+# schedule self-tests, the path finish, adaptive sampling, the denoiser, the live-allocation count, then which twin of a
+# variant-8 kernel ran): bound when the loaded
 # library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
 # require() otherwise.
 OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
@@ -195,7 +196,8 @@ OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_devi
                     "crt_renderer_read_tile_error", "crt_renderer_read_adaptive_prev", "crt_selftest_adaptive_plan",
                     "crt_renderer_compute_guides", "crt_renderer_denoise", "crt_renderer_resolve_denoised",
                     "crt_renderer_read_denoised", "crt_renderer_read_guides", "crt_renderer_denoised_device_ptr",
-                    "crt_selftest_denoise", "crt_renderer_denoise_iteration_ms", "crt_debug_live_allocations")
+                    "crt_selftest_denoise", "crt_renderer_denoise_iteration_ms", "crt_debug_live_allocations",
+                    "crt_renderer_last_launch_frozen")
 
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
@@ -310,6 +312,7 @@ def hip():
             "crt_selftest_denoise": ([P, P, P, P, P], i32),
             "crt_renderer_denoise_iteration_ms": ([P, P], i32),
             "crt_debug_live_allocations": ([P, P], i32),
+            "crt_renderer_last_launch_frozen": ([P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):

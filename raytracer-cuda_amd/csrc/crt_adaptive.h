@@ -205,7 +205,7 @@ int adaptive_pass(crt_renderer* R, const crt_scene* S, hipStream_t st, const uin
     R->last_schedule[0] = R->last_schedule[2] = R->last_schedule[3] = 0.f;
     R->last_schedule[1] = variant == 8 ? (float)occ : 0.f;
     if (int rc = launch_render(R, RENDER_ROWS[render_row(variant, false, occ)], false, dim3((unsigned)count), dim3(64),
-                               st, P))
+                               st, P, S))
         return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(R->ev1, st));

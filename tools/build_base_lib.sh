@@ -9,9 +9,8 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 name=${1:-base}; rev=${2:-HEAD}; patchf=${3:--}; shift $(( $# < 3 ? $# : 3 ))
 src=$(mktemp -d)
 mkdir -p $src/csrc $R/raytracer-cuda_amd/lib_exp/$name
-for f in crt_hip.hip crt_bvh_build.hip crt_device.h crt_sah.h exports.map; do
-  git -C $R show $rev:raytracer-cuda_amd/csrc/$f > $src/csrc/$f
-done
+# every file of csrc/: the headers and the kernel bodies (*.inc) that crt_hip.hip includes
+git -C $R archive $rev raytracer-cuda_amd/csrc | tar -x -C $src --strip-components=1
 git -C $R show $rev:include/crt_hip.h > $src/crt_hip.h
 if [ "$patchf" != "-" ]; then patch -s $src/csrc/crt_hip.hip < $patchf; fi
 cd $R/raytracer-cuda_amd

@@ -29,6 +29,7 @@ PKG = REPO / "raytracer-cuda_amd"
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
+BODY = "crt_render_body.inc"     # the render kernels' body, included by crt_hip.hip
 UNITS = ["VALU", "SALU", "branch", "LDS", "VMEM", "SMEM", "wait/nop", "other"]
 
 
@@ -139,8 +140,17 @@ def census(pkg: Path = PKG, kernel: str = "<false, 8, 7>", defines=(), purposes:
     files.update({int(n): f for n, f in re.findall(r'^\s*\.file\s+(\d+)\s+"([^"]+)"\s*$', asm, re.M)})
     heads = {"crt_hip.hip": heads_of(src_path), "crt_device.h": heads_of(dev_path)}
     src_lines = src_path.read_text().splitlines()
+    # the render kernels' body as an include (csrc/crt_render_body.inc): its lines belong to crt_render_kernel, and the
+    # kernel's anchors and line ranges are searched and numbered in that file (older trees hold the body in crt_hip.hip)
+    body_path = pkg / "csrc" / BODY
+    body_lines = body_path.read_text().splitlines() if body_path.exists() else None
+
+    def in_kernel_file(fname: str) -> bool:
+        return Path(fname).name == (BODY if body_lines is not None else "crt_hip.hip")
 
     def func_of(fname: str, line_no: int) -> str:
+        if Path(fname).name == BODY:
+            return "crt_render_kernel"
         name = "?"
         for i, n in heads.get(Path(fname).name, []):
             if i <= line_no:
@@ -152,9 +162,12 @@ def census(pkg: Path = PKG, kernel: str = "<false, 8, 7>", defines=(), purposes:
     def src_line(pattern: str, start_fn: str, after: int = 0) -> int:
         """The first line after the head of `start_fn` (and after line `after`) containing `pattern` (the line ranges
         are anchored on code, not on line numbers)."""
-        start = max(after, next(i for i, n in heads["crt_hip.hip"] if n == start_fn))
-        for i in range(start, len(src_lines)):
-            if pattern in src_lines[i - 1]:
+        if start_fn == "crt_render_kernel" and body_lines is not None:
+            start, lines = max(after, 1), body_lines
+        else:
+            start, lines = max(after, next(i for i, n in heads["crt_hip.hip"] if n == start_fn)), src_lines
+        for i in range(start, len(lines) + 1):
+            if pattern in lines[i - 1]:
                 return i
         raise SystemExit(f"census anchor not found: {pattern!r} after {start_fn}")
 
@@ -180,21 +193,25 @@ def census(pkg: Path = PKG, kernel: str = "<false, 8, 7>", defines=(), purposes:
         ("pass: live mask + ray count", ("crt_render_kernel", "live_mask = wave_ballot(has_result);",
                                          "first_pass = false;")),
     ]
-    PURPOSES = [(name, rng(*a)) for name, a in purpose_ranges] if purposes else []
+    # (purpose, the file its range is numbered in, range)
+    PURPOSES = [(name, BODY if a[0] == "crt_render_kernel" and body_lines is not None else "crt_hip.hip", rng(*a))
+                for name, a in purpose_ranges] if purposes else []
     kernel_pass = rng("crt_render_kernel", "const uint64_t parked_mask = live_mask & wave_ballot", "first_pass = false;")
     kernel_wide = rng("crt_render_kernel", "} else if constexpr (WIDE) {", "} else if constexpr (VARIANT == 2 || VARIANT == 3")
 
     def purpose_of(fname: str, line: int) -> str:
         if Path(fname).name == "crt_device.h":
             return f"crt_device.h: {func_of(fname, line)}"
-        if Path(fname).name != "crt_hip.hip":
+        if Path(fname).name not in ("crt_hip.hip", BODY):
             return f"{Path(fname).name}"
         fn = func_of(fname, line)
-        for name, (lo, hi) in PURPOSES:
-            if lo <= line <= hi:
+        for name, where, (lo, hi) in PURPOSES:
+            if where == Path(fname).name and lo <= line <= hi:
                 return name
         if fn in FUNC_PURPOSE:
             return FUNC_PURPOSE[fn]
+        if fn == "crt_render_kernel" and not in_kernel_file(fname):
+            return "kernel prologue / epilogue"      # the kernel's own lines round the included body
         if fn == "crt_render_kernel":
             if kernel_pass[0] <= line <= kernel_pass[1]:
                 return "pass: other"
@@ -220,9 +237,11 @@ def census(pkg: Path = PKG, kernel: str = "<false, 8, 7>", defines=(), purposes:
             ln = int(mm.group(2))
             if ln:   # line 0: compiler-made code, keep the last real line
                 cur_file, cur_line = files.get(int(mm.group(1)), ""), ln
-                fn = func_of(cur_file, cur_line) if Path(cur_file).name == "crt_hip.hip" else "crt_device.h"
+                fn = func_of(cur_file, cur_line) if Path(cur_file).name in ("crt_hip.hip", BODY) else "crt_device.h"
                 if fn in SECTION_OF_FUNC:
                     owner = SECTION_OF_FUNC[fn]
+                elif fn == "crt_render_kernel" and not in_kernel_file(cur_file):
+                    owner = "prologue / epilogue"
                 elif fn == "crt_render_kernel":
                     owner = ("regeneration pass" if kernel_pass[0] <= cur_line <= kernel_pass[1]
                              else "loop head / other" if kernel_wide[0] <= cur_line <= kernel_wide[1]

@@ -9,7 +9,8 @@ OUT=${1:-gpurun_out/pmc}
 shift || true
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/$OUT
-sha256sum $R/raytracer-cuda_amd/csrc/crt_hip.hip > $R/$OUT/kernel_sha.txt
+# the kernel sources: crt_hip.hip first (the hash bench.py's kernel_source_sha compares), then the render kernels' body
+sha256sum $R/raytracer-cuda_amd/csrc/crt_hip.hip $R/raytracer-cuda_amd/csrc/crt_render_body.inc > $R/$OUT/kernel_sha.txt
 # the library the passes load (CRT_HIP_LIB or the in-tree build): bench.py checks the counters against it
 sha256sum ${CRT_HIP_LIB:-$R/raytracer-cuda_amd/lib/libcrt_hip.so} > $R/$OUT/library_sha.txt
 python3 $R/bench.py --print-workload-key "$@" > $R/$OUT/workload_key.txt

@@ -85,7 +85,9 @@ def main():
             m = re.search(r"(\d+) rays/frame", log.read_text())
             if m:
                 rays = int(m.group(1))
-    sha = (Path(a.pmc_dir) / "kernel_sha.txt").read_text().split()[0] if (Path(a.pmc_dir) / "kernel_sha.txt").exists() else None
+    sha_txt = Path(a.pmc_dir) / "kernel_sha.txt"     # sha256sum lines: crt_hip.hip, then crt_render_body.inc (newer passes)
+    shas = [line.split()[0] for line in sha_txt.read_text().splitlines() if line.split()] if sha_txt.exists() else []
+    sha = shas[0] if shas else None
     lib_txt = Path(a.pmc_dir) / "library_sha.txt"
     lib_sha = lib_txt.read_text().split()[0] if lib_txt.exists() else None
     key = a.key or (Path(a.pmc_dir) / "workload_key.txt").read_text().strip()
@@ -95,6 +97,8 @@ def main():
          "kernel_ns_median_over_passes": dur, "clock_ghz": round(cyc / dur, 4),
          "per_launch": {k: v for k, v in sorted(vals.items())},
          "per_ray": {k: v / rays for k, v in sorted(vals.items())}}
+    if len(shas) > 1:
+        e["kernel_body_sha256"] = shas[1]     # the included body the passes were built from (crt_render_body.inc)
     derived = {
         "valu_busy": 2 * vals["SQ_INSTS_VALU"] / (cyc * 1024),
         "valu_lane_util": vals["SQ_THREAD_CYCLES_VALU"] / (64 * vals["SQ_ACTIVE_INST_VALU"]),

@@ -66,7 +66,17 @@ for i, line in enumerate(src, 1):
             heads.append((i, mm.group(1)))
 
 
-def func_of(line_no: int) -> str:
+# the render kernels' body is an include (csrc/crt_render_body.inc): a site there is reported with that file's line
+# and text, as crt_render_kernel's
+BODY = PKG / "csrc" / "crt_render_body.inc"
+body_src = BODY.read_text().splitlines() if BODY.exists() else []
+files = {int(n): f for n, f in re.findall(r'^\s*\.file\s+(\d+)\s+"[^"]*"\s+"([^"]+)"', asm, re.M)}
+files.update({int(n): f for n, f in re.findall(r'^\s*\.file\s+(\d+)\s+"([^"]+)"\s*$', asm, re.M)})
+
+
+def func_of(line_no: int, in_body: bool = False) -> str:
+    if in_body:
+        return "crt_render_kernel"
     name = "?"
     for i, n in heads:
         if i <= line_no:
@@ -79,14 +89,15 @@ def func_of(line_no: int) -> str:
 i = asm.index(mangled + ":")
 j = asm.index(".Lfunc_end", i)
 body = asm[i:j].splitlines()
-loc = 0
+loc = (0, False)
 spill_vgprs = set()
 sites = []
 for line in body:
     t = line.strip()
-    mm = re.match(r"\.loc\s+\d+\s+(\d+)", t)
+    mm = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
     if mm:
-        loc = int(mm.group(1)) or loc    # line 0: compiler-made code, keep the last real line
+        if int(mm.group(2)):             # line 0: compiler-made code, keep the last real line
+            loc = (int(mm.group(2)), Path(files.get(int(mm.group(1)), "")).name == BODY.name)
         continue
     if t.startswith("v_writelane_b32"):
         spill_vgprs.add(t.split()[1].rstrip(","))
@@ -94,9 +105,10 @@ for line in body:
         sites.append(("vgpr " + ("spill" if "store" in t else "reload"), loc, t.split(";")[0].strip()))
 for line in body:
     t = line.strip()
-    mm = re.match(r"\.loc\s+\d+\s+(\d+)", t)
+    mm = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
     if mm:
-        loc = int(mm.group(1)) or loc    # line 0: compiler-made code, keep the last real line
+        if int(mm.group(2)):             # line 0: compiler-made code, keep the last real line
+            loc = (int(mm.group(2)), Path(files.get(int(mm.group(1)), "")).name == BODY.name)
         continue
     if t.startswith("v_readlane_b32"):
         parts = t.replace(",", " ").split()
@@ -105,9 +117,10 @@ for line in body:
 
 print(f"\n{len([s for s in sites if s[0].startswith('vgpr')])} VGPR spill/reload instructions, "
       f"{len([s for s in sites if s[0] == 'sgpr reload'])} SGPR-spill read-backs (lane VGPRs {sorted(spill_vgprs)})")
-for kind, ln, ins in sites:
-    text = src[ln - 1].strip() if 0 < ln <= len(src) else ""
-    print(f"  {kind:12s} line {ln:5d} {func_of(ln):18s} {ins:48s} | {text[:70]}")
+for kind, (ln, inc), ins in sites:
+    lines = body_src if inc else src
+    text = lines[ln - 1].strip() if 0 < ln <= len(lines) else ""
+    print(f"  {kind:12s} {'body' if inc else 'line'} {ln:5d} {func_of(ln, inc):18s} {ins:48s} | {text[:70]}")
 print("\nby source function:")
-for (kind, fn), n in sorted(Counter((k, func_of(ln)) for k, ln, _ in sites).items()):
+for (kind, fn), n in sorted(Counter((k, func_of(ln, inc)) for k, (ln, inc), _ in sites).items()):
     print(f"  {kind:12s} {fn:20s} {n}")
