@@ -541,6 +541,86 @@ float* crt_renderer_denoised_device_ptr(crt_renderer* r);
  * CRT_ERR_INVALID_ARGUMENT here. */
 int crt_selftest_denoise(crt_renderer* r, const float* color, const float* guides, const crt_denoise_options* options,
                          float* out);
+/* ---- reprojection: a frame's history across camera moves (no reference counterpart; DESIGN.md "Reprojection") ----
+ * (In this library "temporal" names the temporal tile order, crt_renderer_set_temporal_order; this feature is called
+ * reproject / history throughout.)
+ *
+ * crt_renderer_reproject blends the frame in the sums, c = scale * sum per channel (formed as crt_renderer_denoise forms
+ * c_0), into a per-pixel history that follows the camera: each pixel finds where its first hit (the current guides,
+ * crt_renderer_compute_guides) lay in the previous frame and takes the history there if the previous guides vouch for it.
+ * Everything is f32, uncontracted, division correctly rounded.  dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z; dist2 is
+ * the denoiser's d above.
+ * State per renderer handle, allocated by the first call and freed with the handle: two history buffers of one 16-byte
+ * row (r, g, b, len) per pixel (a ping-pong pair), a second guide buffer (the handle then holds two behind an index: the
+ * one a call read as current is kept as the next call's previous, nothing is copied), the previous guide camera (the
+ * crt_camera_desc crt_renderer_compute_guides made its rays from) and a `valid` flag: 64 bytes per pixel and one word per
+ * 64-pixel row segment.  crt_renderer_read_guides and crt_renderer_denoise keep seeing the current guides.  Guides that
+ * crt_selftest_denoise uploaded have no guide camera (all zero): as the previous frame of a later call they give no pixel
+ * a history (LN = 0, so s > 0 fails), and that call starts over.
+ * Per pixel p with current guide (n, t) (pos, key), W and H the frame's size in pixels:
+ *   1. No history if the state is not valid (first call, after crt_renderer_reset_history), if key == 0x7fffffff (a miss)
+ *      or if a channel of c is not finite: out = (c, 1.f).
+ *   2. The previous guide camera (o, ll, hor, ver).  Host side, once per call: L = ll - o; N = cross(hor, ver), each
+ *      component a * b - c * d as two products and a subtraction; LN = dot(L, N); hh = dot(hor, hor); vv = dot(ver, ver);
+ *      tol2 = position_tolerance * position_tolerance.  Per pixel: d = pos - o; s = LN / dot(d, N); q = s * d - L (a
+ *      multiply, then a subtraction); u = dot(q, hor) / hh; v = dot(q, ver) / vv; fx = u * (float)W - 0.5f; fy = v *
+ *      (float)H - 0.5f.  No history unless s > 0 && fx > -1.f && fx < (float)W && fy > -1.f && fy < (float)H (a NaN fails).
+ *      x0 = floorf(fx), ax = fx - x0, likewise y0, ay; lim = tol2 * dot(d, d).
+ *   3. Four taps (x0 + i, y0 + j), j outer and i inner, w = (i ? ax : 1.f - ax) * (j ? ay : 1.f - ay).  A tap is skipped
+ *      if it lies outside the frame, if !(w > 0.f), if the previous key differs from key, if !(dist2(pos, prev_pos) <= lim)
+ *      (position_tolerance == +inf: off, lim is not computed and the test passes), if the normal term is on and
+ *      !(dot(n, prev_n) >= normal_min) (normal_min == -inf: off, not computed, the previous normals are not loaded), or if
+ *      one of the tap's three history colours is not finite.  Else acc = acc + w * row for the row's four components and
+ *      sw = sw + w.
+ *   4. If sw > 0: hist = acc / sw per component; m = fminf(hist.len + 1.f, max_history); a = 1.f / m; out.c = hist.c +
+ *      (c.c - hist.c) * a per channel; out.len = m.  Else out = (c, 1.f).
+ * After the launch the current guides and guide camera become the previous ones, the history buffers swap and valid is
+ * set.  So a non-finite sample lives in the history for exactly one frame (its pixel shows it, no later tap takes it); a
+ * pixel nothing vouches for restarts at len = 1; len never exceeds max_history: the running mean becomes an exponential
+ * one with floor 1 / max_history.  The sums, the RNG state, the RGBA8 buffer, the guides and the denoised buffer are not
+ * touched.
+ * The history is biased where the frame changes and the first hit does not say so: what a glass or mirror surface shows
+ * lags behind the camera by up to max_history frames, repeated bilinear resampling blurs it under motion, and a rim that
+ * comes into view starts from one noisy sample.
+ * There are no defaults for position_tolerance and max_history: the tolerance is relative to the distance from the
+ * previous camera, and a useful value is a few pixel footprints (about 2 tan(fov_x / 2) / W each), so it depends on the
+ * frame's width and field of view.
+ * stats_out (optional): reproject_ms = HIP events round the launch, pixels_reprojected = the pixels with sw > 0 (ballot
+ * population counts stored per wave, summed on the host), pixels_hit as crt_denoise_stats'.  With stats_out the call
+ * waits for its launch; without, it is asynchronous.  Before any device work and before anything is allocated,
+ * CRT_ERR_INVALID_ARGUMENT: a null handle or options, a position_tolerance that is NaN or outside [2^-50, 2^50] and not
+ * +inf, a normal_min that is NaN or outside [-1, 1] and not -inf, a max_history that is NaN or outside [1, 2^24], flag
+ * bits (none is defined), reserved != 0, a scale that is NaN or <= 0, no guides computed yet; CRT_ERR_UNSUPPORTED: a
+ * pixel shard other than (0, 1).  These entries joined ABI version 3 after its first release. */
+typedef struct crt_reproject_options {
+    float position_tolerance;           /* [2^-50, 2^50] relative to the distance from the previous camera, or +inf = off */
+    float normal_min;                   /* [-1, 1], or -inf = off */
+    float max_history;                  /* [1, 2^24] */
+    uint32_t flags;                     /* 0 */
+    int32_t reserved;
+} crt_reproject_options;
+typedef struct crt_reproject_stats { float reproject_ms; uint32_t pixels_reprojected, pixels_hit; } crt_reproject_stats;
+int crt_renderer_reproject(crt_renderer* r, const crt_reproject_options* o, float scale, crt_reproject_stats* stats_out, void* stream);
+/* The next crt_renderer_reproject starts over (every pixel (c, 1)).  Nothing is freed. */
+int crt_renderer_reset_history(crt_renderer* r);
+/* crt_renderer_denoise with c_0 = the history colours (scale 1), through the same host function and kernels, guided by
+ * the current guides; the result is the handle's `denoised` buffer (crt_renderer_resolve_denoised / _read_denoised).
+ * CRT_DENOISE_TILE_SCALE is CRT_ERR_INVALID_ARGUMENT here, as is a handle without a history. */
+int crt_renderer_denoise_history(crt_renderer* r, const crt_denoise_options* o, crt_denoise_stats* stats_out, void* stream);
+/* writeColor of the history colours with scale 1 into the RGBA8 buffer. */
+int crt_renderer_resolve_history(crt_renderer* r, void* stream);
+/* W*H*4 floats (r, g, b, len); waits for the device.  CRT_ERR_INVALID_ARGUMENT before the first reprojection. */
+int crt_renderer_read_history(crt_renderer* r, float* host_out);
+/* The latest history on the device (W*H*4 floats), NULL before the first reprojection.  The two buffers alternate: ask
+ * again after every crt_renderer_reproject. */
+float* crt_renderer_history_device_ptr(crt_renderer* r);
+/* Self-test of the reprojection (like crt_selftest_denoise: no camera or scene): uploads color (W*H*3, into the
+ * renderer's own linear buffer, taken with scale 1), guides and prev_guides (W*H*8 each) and prev_history (W*H*4; NULL =
+ * the state is not valid) into the renderer's buffers, takes prev_camera as the previous guide camera, runs the host
+ * function crt_renderer_reproject calls on the null stream and reads the new history into out_history (W*H*4). */
+int crt_selftest_reproject(crt_renderer* r, const float* color, const float* guides, const float* prev_guides,
+                           const float* prev_history, const crt_camera_desc* prev_camera,
+                           const crt_reproject_options* options, float* out_history);
 /* Host only, no GPU (like crt_scene_export_identity): the per-material rows the step kernel reads, n_materials x 8
  * floats = (code, 0, 0, 0) (payload): code (int bits) 0 lambertian, 1 metal, 2 dielectric, 3 light, 4 unknown type
  * (emits 0); payload (albedo.xyz, 0), (albedo.xyz, min(roughness, 1)), (ior, 1 / ior, r0(1 / ior), r0(ior)) with

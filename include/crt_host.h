@@ -97,6 +97,13 @@ int  crth_viewer_create(const char* const* obj_files, int n_files, int device, c
 /* One frame: Raytracer::updateAndRender(dt, input); info may be NULL. */
 int  crth_viewer_frame(crth_viewer* v, float dt, const crth_input* in, crth_frame_info* info);
 int  crth_viewer_camera(const crth_viewer* v, crt_camera_desc* out);
+/* The reproject mode (crt_hip.h "reprojection"): after each frame's render the viewer computes the first-hit guides, runs
+ * crt_renderer_reproject with `o` and the frame's pixel_sample_scale, then, with d != NULL, crt_renderer_denoise_history
+ * with `d`, and resolves the result, so the RGBA8 buffer holds the reconstructed frame and the renderer's history() /
+ * denoised() the linear one.  d == NULL: no filter (the history is resolved); o == NULL: the mode is switched off and the
+ * history reset.  The option values are checked by the library on the next crth_viewer_frame.
+ * CRT_ERR_INVALID_ARGUMENT: a null viewer, or a viewer created with accumulate != 0 (the two modes exclude each other). */
+int  crth_viewer_set_reproject(crth_viewer* v, const crt_reproject_options* o, const crt_denoise_options* d);
 /* The viewer's renderer (read_rgba8 / read_linear / read_rng / device pointers via crt_hip.h). */
 crt_renderer* crth_viewer_renderer(crth_viewer* v);
 void crth_viewer_destroy(crth_viewer* v);

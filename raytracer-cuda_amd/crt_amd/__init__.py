@@ -821,6 +821,105 @@ class Renderer:
         check(_lib.require("crt_selftest_denoise")(self.h, _p(c), _p(g), C.byref(o), _p(out)), "selftest_denoise")
         return out
 
+    # ---- reprojection (crt_hip.h crt_renderer_reproject ff.)
+    @staticmethod
+    def _reproject_options(who, position_tolerance, normal_min, max_history):
+        vals = []
+        for name, v in (("position_tolerance", position_tolerance), ("normal_min", normal_min), ("max_history", max_history)):
+            try:
+                vals.append(float(np.float32(v)))
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: {name} must be a number") from None
+        tol, nmin, cap = vals
+        if not (tol == float("inf") or 2.0 ** -50 <= tol <= 2.0 ** 50):
+            raise ValueError(f"{who}: position_tolerance must be in [2^-50, 2^50] or +inf (that term off)")
+        if not (nmin == float("-inf") or -1.0 <= nmin <= 1.0):
+            raise ValueError(f"{who}: normal_min must be in [-1, 1] or -inf (that term off)")
+        if not 1.0 <= cap <= 2.0 ** 24:
+            raise ValueError(f"{who}: max_history must be in [1, 2^24]")
+        return _lib.ReprojectOptions(tol, nmin, cap, 0, 0)
+
+    def reproject(self, position_tolerance, normal_min=float("-inf"), *, max_history, scale=None, stream=None) -> dict:
+        """Blend scale * the sums into the history that follows the camera (crt_renderer_reproject; crt_hip.h states
+        every operation), guided by compute_guides' buffers of this frame and of the previous call's.  No defaults for
+        position_tolerance (relative to the distance from the previous camera; a few pixel footprints) and max_history
+        (the cap of the per-pixel length: the floor 1 / max_history of the blend weight); float("inf") / float("-inf")
+        switch the position / normal term off.  scale: what resolve() would take.  The result is history(); the sums,
+        the RNG state, rgba8(), guides() and denoised() are untouched.  Synchronous.
+        Returns {"reproject_ms", "pixels_reprojected", "pixels_hit"}."""
+        o = self._reproject_options("reproject", position_tolerance, normal_min, max_history)
+        try:
+            sc = float(np.float32(scale))
+        except (TypeError, ValueError):
+            raise ValueError("reproject: scale must be a number") from None
+        if not sc > 0:
+            raise ValueError("reproject: scale must be > 0")
+        s = _lib.ReprojectStats()
+        check(_lib.require("crt_renderer_reproject")(self.h, C.byref(o), C.c_float(sc), C.byref(s), stream), "reproject")
+        return {"reproject_ms": float(s.reproject_ms), "pixels_reprojected": int(s.pixels_reprojected),
+                "pixels_hit": int(s.pixels_hit)}
+
+    def history(self) -> np.ndarray:
+        """The last reproject()'s history, float32 [height, width, 4]: linear r, g, b and the length."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        check(_lib.require("crt_renderer_read_history")(self.h, _p(out)), "read_history")
+        return out
+
+    def resolve_history(self, stream=None):
+        """resolve(1.0) of the history colours into rgba8() (crt_renderer_resolve_history)."""
+        check(_lib.require("crt_renderer_resolve_history")(self.h, stream), "resolve_history")
+
+    def history_device_ptr(self) -> int:
+        """The latest history on the device (height * width * 4 floats) for torch interop; 0 before the first
+        reproject().  Two buffers alternate: ask again after every reproject()."""
+        fn = _lib.require("crt_renderer_history_device_ptr")
+        return fn(self.h) or 0
+
+    def reset_history(self):
+        """The next reproject() starts over (crt_renderer_reset_history)."""
+        check(_lib.require("crt_renderer_reset_history")(self.h), "reset_history")
+
+    def denoise_history(self, sigma_color, sigma_normal, sigma_position, iterations: int = 5, direct_only: bool = False,
+                        stream=None) -> dict:
+        """denoise() with c_0 = the history colours instead of scale * the sums (crt_renderer_denoise_history): the same
+        filter, the result is denoised().  Synchronous.  Returns {"guides_ms", "filter_ms", "iterations", "pixels_hit"}."""
+        o = self._denoise_options("denoise_history", sigma_color, sigma_normal, sigma_position, iterations, False, direct_only)
+        s = _lib.DenoiseStats()
+        check(_lib.require("crt_renderer_denoise_history")(self.h, C.byref(o), C.byref(s), stream), "denoise_history")
+        return {"guides_ms": float(s.guides_ms), "filter_ms": float(s.filter_ms), "iterations": int(s.iterations),
+                "pixels_hit": int(s.pixels_hit)}
+
+    def selftest_reproject(self, color, guides, prev_guides, prev_history, prev_camera, position_tolerance,
+                           normal_min=float("-inf"), *, max_history) -> np.ndarray:
+        """The reprojection on caller-supplied buffers (crt_selftest_reproject): color [height, width, 3] float32 (it
+        replaces the sums, scale 1), guides and prev_guides [height, width, 8], prev_history [height, width, 4] or None
+        (no previous frame), prev_camera a CameraDesc or its floats (origin, lower_left, horizontal, vertical first).
+        Returns the new history [height, width, 4]."""
+        o = self._reproject_options("selftest_reproject", position_tolerance, normal_min, max_history)
+        n = self.width * self.height
+        c = np.ascontiguousarray(color, np.float32).reshape(-1)
+        g = np.ascontiguousarray(guides, np.float32).reshape(-1)
+        pg = np.ascontiguousarray(prev_guides, np.float32).reshape(-1)
+        ph = None if prev_history is None else np.ascontiguousarray(prev_history, np.float32).reshape(-1)
+        if c.size != n * 3:
+            raise ValueError("selftest_reproject: color must hold height * width * 3 floats")
+        if g.size != n * 8 or pg.size != n * 8:
+            raise ValueError("selftest_reproject: guides and prev_guides must hold height * width * 8 floats")
+        if ph is not None and ph.size != n * 4:
+            raise ValueError("selftest_reproject: prev_history must hold height * width * 4 floats")
+        if isinstance(prev_camera, _lib.CameraDesc):
+            cam = prev_camera
+        else:
+            f = np.ascontiguousarray(prev_camera, np.float32).reshape(-1)
+            if f.size < 12:
+                raise ValueError("selftest_reproject: prev_camera must be a CameraDesc or at least 12 floats")
+            cam = _lib.CameraDesc()
+            C.memmove(C.byref(cam), f.ctypes.data, 4 * min(f.size, 19))
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        check(_lib.require("crt_selftest_reproject")(self.h, _p(c), _p(g), _p(pg), None if ph is None else _p(ph),
+                                                     C.byref(cam), C.byref(o), _p(out)), "selftest_reproject")
+        return out
+
     def set_leaf_carry(self, lanes: int, max_pairs: int):
         """Variant 8's leaf-pair carry: measured and removed in round 5; the library reports
         CRT_ERR_UNSUPPORTED, so this raises CrtError (profiles/r04c/leaf_carry.patch restores the kernels)."""
@@ -959,6 +1058,27 @@ class Viewer:
         check_host(_lib.host().crth_viewer_frame(self.h, dt, C.byref(_input(**inp)), C.byref(fi)), "crth_viewer_frame")
         return {"frame": fi.frame, "spp": fi.spp, "accumulated": fi.accumulated, "moving": bool(fi.moving),
                 "high_quality": bool(fi.high_quality), "kernel_ms": fi.kernel_ms, "frame_ms": fi.frame_ms}
+
+    def set_reproject(self, position_tolerance=None, normal_min=float("-inf"), *, max_history=None, denoise=None,
+                      denoise_iterations: int = 5):
+        """The reproject mode (crth_viewer_set_reproject): after each frame's render the viewer computes the guides,
+        runs Renderer.reproject with these options and the frame's pixel_sample_scale and resolves the history; with
+        denoise = (sigma_color, sigma_normal, sigma_position) it filters the history first (Renderer.denoise_history)
+        and resolves that.  position_tolerance None switches the mode off and resets the history.  Not together with
+        accumulate."""
+        if position_tolerance is None:
+            check_host(_lib.host().crth_viewer_set_reproject(self.h, None, None), "crth_viewer_set_reproject")
+            return
+        o = Renderer._reproject_options("set_reproject", position_tolerance, normal_min, max_history)
+        d = None
+        if denoise is not None:
+            try:
+                sc, sn, sx = denoise
+            except (TypeError, ValueError):
+                raise ValueError("set_reproject: denoise must be (sigma_color, sigma_normal, sigma_position)") from None
+            d = Renderer._denoise_options("set_reproject", sc, sn, sx, denoise_iterations, False, False)
+        check_host(_lib.host().crth_viewer_set_reproject(self.h, C.byref(o), None if d is None else C.byref(d)),
+                   "crth_viewer_set_reproject")
 
     def camera(self) -> CameraDesc:
         d = CameraDesc()

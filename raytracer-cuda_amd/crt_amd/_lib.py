@@ -147,6 +147,15 @@ class DenoiseStats(C.Structure):     # crt_hip.h crt_denoise_stats
                 ("pixels_hit", C.c_uint32)]
 
 
+class ReprojectOptions(C.Structure):  # crt_hip.h crt_reproject_options
+    _fields_ = [("position_tolerance", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class ReprojectStats(C.Structure):    # crt_hip.h crt_reproject_stats
+    _fields_ = [("reproject_ms", C.c_float), ("pixels_reprojected", C.c_uint32), ("pixels_hit", C.c_uint32)]
+
+
 DENOISE_TILE_SCALE = 1               # crt_denoise_options.flags
 DENOISE_DIRECT_ONLY = 0x80000000     # measurement switch: every iteration through the direct kernel
 
@@ -180,10 +189,12 @@ HIP_SYMBOLS = [
     "crt_renderer_compute_guides", "crt_renderer_denoise", "crt_renderer_resolve_denoised",
     "crt_renderer_read_denoised", "crt_renderer_read_guides", "crt_renderer_denoised_device_ptr", "crt_selftest_denoise",
     "crt_renderer_denoise_iteration_ms", "crt_debug_live_allocations", "crt_renderer_last_launch_frozen",
+    "crt_renderer_reproject", "crt_renderer_reset_history", "crt_renderer_denoise_history", "crt_renderer_resolve_history",
+    "crt_renderer_read_history", "crt_renderer_history_device_ptr", "crt_selftest_reproject",
 ]
 # Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, the
 # schedule self-tests, the path finish, adaptive sampling, the denoiser, the live-allocation count, then which twin of a
-# variant-8 kernel ran): bound when the loaded
+# variant-8 kernel ran, then the reprojection): bound when the loaded
 # library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
 # require() otherwise.
 OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
@@ -197,13 +208,17 @@ OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_devi
                     "crt_renderer_compute_guides", "crt_renderer_denoise", "crt_renderer_resolve_denoised",
                     "crt_renderer_read_denoised", "crt_renderer_read_guides", "crt_renderer_denoised_device_ptr",
                     "crt_selftest_denoise", "crt_renderer_denoise_iteration_ms", "crt_debug_live_allocations",
-                    "crt_renderer_last_launch_frozen")
+                    "crt_renderer_last_launch_frozen",
+                    "crt_renderer_reproject", "crt_renderer_reset_history", "crt_renderer_denoise_history",
+                    "crt_renderer_resolve_history", "crt_renderer_read_history", "crt_renderer_history_device_ptr",
+                    "crt_selftest_reproject")
 
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
     "crth_scene_loader_arrays", "crth_camera", "crth_last_error", "crth_encode_image", "crth_write_image",
     "crth_build_mesh_bvh", "crth_camera_create", "crth_camera_update", "crth_camera_get", "crth_camera_destroy",
     "crth_viewer_create", "crth_viewer_frame", "crth_viewer_camera", "crth_viewer_renderer", "crth_viewer_destroy",
+    "crth_viewer_set_reproject",
 ]
 
 _hip = None
@@ -313,6 +328,13 @@ def hip():
             "crt_renderer_denoise_iteration_ms": ([P, P], i32),
             "crt_debug_live_allocations": ([P, P], i32),
             "crt_renderer_last_launch_frozen": ([P], i32),
+            "crt_renderer_reproject": ([P, P, f32, P, P], i32),
+            "crt_renderer_reset_history": ([P], i32),
+            "crt_renderer_denoise_history": ([P, P, P, P], i32),
+            "crt_renderer_resolve_history": ([P, P], i32),
+            "crt_renderer_read_history": ([P, P], i32),
+            "crt_renderer_history_device_ptr": ([P], P),
+            "crt_selftest_reproject": ([P, P, P, P, P, P, P, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):
@@ -356,8 +378,11 @@ def host():
             "crth_viewer_create": ([P, i32, i32, P, i32, i32, f32, f32, f32, P, f32, C.c_ulonglong, i32, P], i32),
             "crth_viewer_frame": ([P, f32, P, P], i32), "crth_viewer_camera": ([P, P], i32),
             "crth_viewer_renderer": ([P], P), "crth_viewer_destroy": ([P], None),
+            "crth_viewer_set_reproject": ([P, P, P], i32),
         }
         for name, (args, res) in sig.items():
+            if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):
+                continue   # an A/B build of an older revision (CRT_HOST_LIB): entries added since then are absent
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = res

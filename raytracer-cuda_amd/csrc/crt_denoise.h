@@ -209,7 +209,7 @@ int denoise_state(crt_renderer* R, DenoiseState** out) {
         const size_t n_pix = (size_t)R->width * R->height;
         HIP_TRY(N->rays.alloc(n_pix * 2));
         HIP_TRY(N->hits.alloc(n_pix * 2));
-        HIP_TRY(N->guides.alloc(n_pix * 2));
+        HIP_TRY(N->guides[0].alloc(n_pix * 2));
         HIP_TRY(N->col[0].alloc(n_pix));
         HIP_TRY(N->col[1].alloc(n_pix));
         HIP_TRY(N->denoised.alloc(n_pix * 3));
@@ -223,6 +223,11 @@ int denoise_state(crt_renderer* R, DenoiseState** out) {
         return set_error(CRT_ERR_OUT_OF_MEMORY, "the denoiser state of this renderer could not be allocated");
     *out = R->denoise.get();
     return CRT_OK;
+}
+
+// Before new guides are written: a buffer the reprojection keeps as its previous frame is left alone.
+void denoise_next_guides(DenoiseState* N) {
+    if (N->keep) { N->gi ^= 1; N->keep = false; }
 }
 
 // The checks of the options alone (no handle, no device).
@@ -242,18 +247,21 @@ int denoise_check_options(const crt_denoise_options* o, const char* who) {
 }
 
 // The filter on `st`: c0 from the sums, then one launch per iteration.  The handle's guides and options were checked.
+// c0 non-null (crt_renderer_denoise_history): iteration 0 reads those rows' (x, y, z) instead and the sums are not read.
 // timed: an event after every launch (crt_renderer_denoise_iteration_ms); the caller waits for f1 before reading them.
-int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, float scale, hipStream_t st, bool timed) {
+int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, float scale, hipStream_t st, bool timed,
+                const float4* c0 = nullptr) {
     const int W = R->width, H = R->height, n_pix = W * H;
     const int iterations = o->iterations ? o->iterations : 5;
     const bool tile_scale = (o->flags & CRT_DENOISE_TILE_SCALE) != 0, direct_only = (o->flags & CRT_DENOISE_DIRECT_ONLY) != 0;
     HIP_TRY(hipEventRecord(N->f0.get(), st));
-    hipLaunchKernelGGL(crt_denoise_input_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, R->d_sum, N->col[0].get(),
-                       tile_scale ? R->adaptive->tile_spp.get() : nullptr, W, n_pix, (W + 7) / 8, scale);
+    if (!c0)
+        hipLaunchKernelGGL(crt_denoise_input_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, R->d_sum, N->col[0].get(),
+                           tile_scale ? R->adaptive->tile_spp.get() : nullptr, W, n_pix, (W + 7) / 8, scale);
     N->timed_iterations = 0;
     if (timed) HIP_TRY(hipEventRecord(N->it[0].get(), st));
     DenoiseParams D{};
-    D.guides = N->guides.get();
+    D.guides = N->guides[N->gi].get();
     D.width = W; D.height = H;
     const float inf = __builtin_inff();
     D.on_c = o->sigma_color != inf; D.on_n = o->sigma_normal != inf; D.on_x = o->sigma_position != inf;
@@ -262,7 +270,7 @@ int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, 
     D.inv_x = D.on_x ? 1.f / (o->sigma_position * o->sigma_position) : 0.f;
     for (int i = 0; i < iterations; ++i) {
         const bool last = i == iterations - 1;
-        D.in = N->col[i & 1].get();
+        D.in = i == 0 && c0 ? c0 : N->col[i & 1].get();
         D.out = last ? nullptr : N->col[(i + 1) & 1].get();
         D.out3 = last ? N->denoised.get() : nullptr;
         D.stride = 1 << i;
@@ -293,6 +301,31 @@ int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, 
     return CRT_OK;
 }
 
+// The pixels whose guide is a hit: the pack kernel's per-wave counts, summed (N->counted).
+int denoise_pixels_hit(crt_renderer* R, DenoiseState* N, uint32_t* out) {
+    std::vector<uint32_t> w(((size_t)R->width * R->height + 63) / 64);
+    HIP_TRY(hipMemcpy(w.data(), N->wave_hits.get(), w.size() * 4, hipMemcpyDeviceToHost));
+    for (uint32_t c : w) *out += c;
+    return CRT_OK;
+}
+
+// The stats of the filter run just enqueued on `N` (crt_renderer_denoise, crt_renderer_denoise_history): waits for its
+// last launch.
+int denoise_stats(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, crt_denoise_stats* out) {
+    crt_denoise_stats s{};
+    s.iterations = (uint32_t)(o->iterations ? o->iterations : 5);
+    HIP_TRY(hipEventSynchronize(N->f1.get()));
+    HIP_TRY(hipEventElapsedTime(&s.filter_ms, N->f0.get(), N->f1.get()));
+    if (N->timed_guides) {
+        HIP_TRY(hipEventSynchronize(N->g1.get()));
+        HIP_TRY(hipEventElapsedTime(&s.guides_ms, N->g0.get(), N->g1.get()));
+    }
+    if (N->counted)
+        if (int rc = denoise_pixels_hit(R, N, &s.pixels_hit)) return rc;
+    *out = s;
+    return CRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -309,6 +342,8 @@ int crt_renderer_compute_guides(crt_renderer* R, const crt_scene* S, const crt_t
     if (int rc = denoise_state(R, &N)) return rc;
     const int n_pix = R->width * R->height;
     N->have_guides = N->counted = false;
+    denoise_next_guides(N);
+    N->guide_cam = R->cam;
     HIP_TRY(hipEventRecord(N->g0.get(), st));
     GuideRayParams G{};
     G.cam = R->cam; G.width = R->width; G.height = R->height; G.rays = N->rays.get();
@@ -317,7 +352,7 @@ int crt_renderer_compute_guides(crt_renderer* R, const crt_scene* S, const crt_t
     if (int rc = crt_scene_trace_device(S, reinterpret_cast<const crt_ray*>(N->rays.get()), n_pix, opts,
                                         reinterpret_cast<crt_hit*>(N->hits.get()), nullptr, 0u, stream))
         return rc;
-    hipLaunchKernelGGL(crt_guide_pack_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, N->rays.get(), N->hits.get(), N->guides.get(),
+    hipLaunchKernelGGL(crt_guide_pack_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, N->rays.get(), N->hits.get(), N->guides[N->gi].get(),
                        N->wave_hits.get(), n_pix);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(N->g1.get(), st));
@@ -340,23 +375,7 @@ int crt_renderer_denoise(crt_renderer* R, const crt_denoise_options* o, float sc
     DenoiseState* N = nullptr;
     if (int rc = denoise_state(R, &N)) return rc;
     if (int rc = denoise_run(R, N, o, scale, (hipStream_t)stream, stats_out != nullptr)) return rc;
-    if (stats_out) {
-        crt_denoise_stats s{};
-        s.iterations = (uint32_t)(o->iterations ? o->iterations : 5);
-        HIP_TRY(hipEventSynchronize(N->f1.get()));
-        HIP_TRY(hipEventElapsedTime(&s.filter_ms, N->f0.get(), N->f1.get()));
-        if (N->timed_guides) {
-            HIP_TRY(hipEventSynchronize(N->g1.get()));
-            HIP_TRY(hipEventElapsedTime(&s.guides_ms, N->g0.get(), N->g1.get()));
-        }
-        if (N->counted) {
-            std::vector<uint32_t> w(((size_t)R->width * R->height + 63) / 64);
-            HIP_TRY(hipMemcpy(w.data(), N->wave_hits.get(), w.size() * 4, hipMemcpyDeviceToHost));
-            for (uint32_t c : w) s.pixels_hit += c;
-        }
-        *stats_out = s;
-    }
-    return CRT_OK;
+    return stats_out ? denoise_stats(R, N, o, stats_out) : CRT_OK;
 }
 
 int crt_renderer_resolve_denoised(crt_renderer* R, void* stream) {
@@ -382,7 +401,7 @@ int crt_renderer_read_guides(crt_renderer* R, float* out) {
     if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "read guides: null argument");
     if (!R->denoise || !R->denoise->have_guides)
         return set_error(CRT_ERR_INVALID_ARGUMENT, "read guides: no guides computed yet (crt_renderer_compute_guides)");
-    return read_dev(R, out, R->denoise->guides.get(), (size_t)R->width * R->height * 32);
+    return read_dev(R, out, R->denoise->guides[R->denoise->gi].get(), (size_t)R->width * R->height * 32);
 }
 
 int crt_renderer_denoise_iteration_ms(crt_renderer* R, float* out9) {
@@ -412,9 +431,11 @@ int crt_selftest_denoise(crt_renderer* R, const float* color, const float* guide
     if (int rc = denoise_state(R, &N)) return rc;
     const size_t n_pix = (size_t)R->width * R->height;
     HIP_TRY(hipMemcpy(R->d_sum, color, n_pix * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->guides.get(), guides, n_pix * 32, hipMemcpyHostToDevice));
+    denoise_next_guides(N);
+    HIP_TRY(hipMemcpy(N->guides[N->gi].get(), guides, n_pix * 32, hipMemcpyHostToDevice));
     N->have_guides = true;
     N->counted = N->timed_guides = false;
+    N->guide_cam = crt_camera_desc{};                // no camera made these guides: a reprojection after this restarts
     if (int rc = denoise_run(R, N, o, 1.f, 0, false)) return rc;
     HIP_TRY(hipStreamSynchronize(0));
     HIP_TRY(hipMemcpy(out, N->denoised.get(), n_pix * 12, hipMemcpyDeviceToHost));

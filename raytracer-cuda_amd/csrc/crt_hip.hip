@@ -2703,7 +2703,11 @@ struct AdaptiveState {
 struct DenoiseState {
     DevBuf<float4> rays;            // 2 rows per pixel: the pixel-centre rays (crt_ray)
     DevBuf<float4> hits;            // 2 rows per pixel: their closest hits (crt_hit)
-    DevBuf<float4> guides;          // 2 rows per pixel: (normal.xyz, t) (position.xyz, key)
+    DevBuf<float4> guides[2];       // 2 rows per pixel: (normal.xyz, t) (position.xyz, key); [gi] is the current one,
+                                    // [1] exists only once the reprojection keeps previous guides (crt_reproject.h)
+    int gi = 0;
+    bool keep = false;              // guides[gi] is also the reprojection's previous frame: the next guides go to [gi ^ 1]
+    crt_camera_desc guide_cam{};    // the camera guides[gi]'s rays were made from (compute_guides)
     DevBuf<float4> col[2];          // 1 row per pixel: (c.xyz, 0)
     DevBuf<float> denoised;         // W*H*3
     DevBuf<uint32_t> wave_hits;     // per 64 pixels: how many of them hit something
@@ -2716,6 +2720,20 @@ struct DenoiseState {
     DevEvent it[9];                 // a timed run: after the input kernel, then after every iteration
     bool lds_raised = false;        // the tiled kernel's dynamic LDS limit was raised for this device
     int timed_iterations = 0;       // iterations of the last timed run (crt_renderer_denoise_iteration_ms), 0: none
+};
+
+// The renderer's reprojection state (crt_reproject.h).  Bytes per pixel: two history buffers of 16-byte rows 32 + the
+// second guide buffer 32 = 64, plus one word per wave of the reprojection kernel's grid.
+struct ReprojectState {
+    DevBuf<float4> hist[2];         // 1 row per pixel: (r, g, b, len); [hi] holds the latest history
+    DevBuf<uint32_t> wave_taken;    // per wave of the kernel's grid: how many of its pixels took history
+    int hi = 0;
+    int prev_gi = 0;                // DenoiseState::guides[prev_gi]: the guides of the frame hist[hi] belongs to
+    crt_camera_desc prev_cam{};     // and their guide camera
+    bool ready = false;
+    bool valid = false;             // hist[hi], guides[prev_gi] and prev_cam describe one earlier frame
+    bool have_history = false;      // hist[hi] holds a reprojection's result
+    DevEvent e0, e1;
 };
 
 struct crt_scene {
@@ -2806,6 +2824,7 @@ struct crt_renderer {
     std::unique_ptr<WavefrontScratch> wavefront;    // crt_renderer_render_wavefront: batches of the handle, allocated on first use (crt_paths.h)
     std::unique_ptr<AdaptiveState> adaptive;        // crt_renderer_render_adaptive: per-tile state of the handle, allocated on first use (crt_adaptive.h)
     std::unique_ptr<DenoiseState> denoise;          // crt_renderer_compute_guides / crt_renderer_denoise: guides and colour buffers of the handle, allocated on first use (crt_denoise.h)
+    std::unique_ptr<ReprojectState> reproject;      // crt_renderer_reproject: history buffers of the handle, allocated on first use (crt_reproject.h)
 };
 
 namespace {
@@ -4285,3 +4304,4 @@ int crt_selftest_schedule_buffer(crt_renderer* R, int which, uint32_t* out, int6
 #include "crt_paths.h"
 #include "crt_adaptive.h"
 #include "crt_denoise.h"
+#include "crt_reproject.h"

@@ -13,6 +13,10 @@
 // still, 1-spp frames add into the linear sum and resolve with 1/(samples so far), so the image
 // converges progressively; any camera motion (or a high-quality frame) restarts the sum.  K
 // accumulated 1-spp frames equal one K-spp frame bit for bit (same per-pixel sample order).
+// The reproject mode (setReproject) is a second addition, for the frames `accumulate` cannot help: after each frame's
+// render it computes the first-hit guides, blends the frame into the history that follows the camera
+// (crt_renderer_reproject with the frame's pixel_sample_scale), optionally filters the history
+// (crt_renderer_denoise_history) and resolves that, so the RGBA8 buffer holds the reconstructed frame.
 #pragma once
 #include <chrono>
 #include <string>
@@ -51,6 +55,10 @@ struct FrameInfo {
     bool highQuality = false;
     float kernelMs = 0.f;       // render kernel, HIP events
     double frameMs = 0.0;       // updateAndRender wall clock (camera update + upload + render + resolve + sync)
+    // the reproject mode: HIP events of the library's stats; without a filter the guides are timed by the wall clock
+    // round crt_renderer_compute_guides and a synchronisation (the library reports their events only with a filter's stats)
+    float guidesMs = 0.f, reprojectMs = 0.f, filterMs = 0.f;
+    unsigned pixelsReprojected = 0;
 };
 
 class Raytracer {
@@ -82,6 +90,7 @@ public:
         if (!m_Options.accumulate) {
             m_Renderer.render(m_SceneManager.getBVHNodes(), m_SceneManager.getWorld());   // CUDARenderer::render
             m_Accumulated = fi.spp;
+            if (m_Reproject) reconstruct(r, fi);
         } else {
             const bool still = !fi.moving && !fi.highQuality;
             CRT_CHECK(crt_renderer_render(r, m_SceneManager.getBVHNodes(), fi.spp, 20, keep ? CRT_RENDER_ACCUMULATE : 0u,
@@ -109,6 +118,17 @@ public:
         }
     }
 
+    // The reproject mode: o == nullptr switches it off, d == nullptr runs no filter.  The options are checked by the
+    // library on the next frame.  Not together with `accumulate`: that mode keeps the sums, this one the history.
+    void setReproject(const crt_reproject_options* o, const crt_denoise_options* d) {
+        if (o && m_Options.accumulate) throw std::runtime_error("the reproject mode and accumulate exclude each other");
+        m_Reproject = o != nullptr;
+        m_Filter = o && d;
+        if (o) m_ReprojectOptions = *o;
+        if (m_Filter) m_FilterOptions = *d;
+        if (!o) CRT_CHECK(crt_renderer_reset_history(m_Renderer.handle()));
+    }
+
     const Camera& camera() const { return m_Camera; }
     HIPRenderer& renderer() { return m_Renderer; }
     SceneManager& sceneManager() { return m_SceneManager; }
@@ -116,6 +136,30 @@ public:
     int height() const { return m_Height; }
 
 private:
+    // guides, reprojection, optional filter and the matching resolve of the frame just rendered
+    void reconstruct(crt_renderer* r, FrameInfo& fi) {
+        const auto g0 = std::chrono::steady_clock::now();
+        CRT_CHECK(crt_renderer_compute_guides(r, m_SceneManager.getBVHNodes(), nullptr, nullptr));
+        if (!m_Filter) {
+            CRT_CHECK(crt_renderer_synchronize(r, nullptr));
+            fi.guidesMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - g0).count();
+        }
+        crt_reproject_stats rs{};
+        CRT_CHECK(crt_renderer_reproject(r, &m_ReprojectOptions, m_Camera.toDesc().pixel_sample_scale, &rs, nullptr));
+        fi.reprojectMs = rs.reproject_ms;
+        fi.pixelsReprojected = rs.pixels_reprojected;
+        if (m_Filter) {
+            crt_denoise_stats ds{};
+            CRT_CHECK(crt_renderer_denoise_history(r, &m_FilterOptions, &ds, nullptr));
+            fi.guidesMs = ds.guides_ms;
+            fi.filterMs = ds.filter_ms;
+            CRT_CHECK(crt_renderer_resolve_denoised(r, nullptr));
+        } else {
+            CRT_CHECK(crt_renderer_resolve_history(r, nullptr));
+        }
+        CRT_CHECK(crt_renderer_synchronize(r, nullptr));
+    }
+
     void initializeScene() {
         const Vec3 target(0, 0, 0), worldY(0, 1, 0);
         const Vec3 pos = m_Options.hasPose ? m_Options.position : Vec3(0, 4, 4);
@@ -137,6 +181,9 @@ private:
     HIPRenderer m_Renderer;
     long long m_Frame = 0;
     int m_Accumulated = 0;
+    bool m_Reproject = false, m_Filter = false;
+    crt_reproject_options m_ReprojectOptions{};
+    crt_denoise_options m_FilterOptions{};
 };
 
 }  // namespace CRT

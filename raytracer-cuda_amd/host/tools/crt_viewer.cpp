@@ -3,10 +3,14 @@
 // frame times are reported (the reference throttles to 60 fps; here frames run back to back).
 //
 //   crt_viewer [-w W] [-h H] [-frames N] [-script still|walk|orbit|hq] [-bvh reference|rebuilt]
-//              [-accumulate] [-no-temporal] [-drain LANES] [-seed S] [-o last.png] model.obj...
+//              [-accumulate] [-no-temporal] [-drain LANES] [-seed S] [-o last.png]
+//              [-reproject TOL:NMIN:MAXH [-denoise SC:SN:SX [-denoise-iters N]]] model.obj...
 //
 // Scripts: still = no input (1 spp per frame, RNG continues); walk = W held; orbit = right mouse dragged
 // in a circle; hq = F pressed once, then still (2000 spp frames).
+// -reproject TOL:NMIN:MAXH: the reproject mode (Raytracer::setReproject) with the position tolerance, the least normal
+// cosine and the history cap given (`inf` / `-inf` switch a term off; there are no defaults); -denoise SC:SN:SX filters
+// the history before it is shown, -denoise-iters iterations (default 5).  Not together with -accumulate.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -17,11 +21,26 @@
 #include "crt/ImageIO.h"
 #include "crt/Raytracer.h"
 
+// "A:B:C" -> three numbers; "inf" and "-inf" are the infinities.
+static bool parseTriple(const char* text, float out[3]) {
+    const char* p = text;
+    for (int k = 0; k < 3; ++k) {
+        char* end = nullptr;
+        out[k] = std::strtof(p, &end);
+        if (end == p || *end != (k < 2 ? ':' : '\0')) return false;
+        p = end + 1;
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     try {
         int W = 2560, H = -1;
         long long frames = 240;
         std::string script = "still", out;
+        bool reproject = false, denoise = false, denoiseItersGiven = false;
+        float rp[3] = {0.f, 0.f, 0.f}, sigma[3] = {0.f, 0.f, 0.f};
+        int denoiseIters = 5;
         CRT::RaytracerOptions opts;
         opts.hasPose = true;                          // the bench pose that frames the Cornell box
         opts.position = CRT::Vec3(0.f, 0.f, 0.3f);
@@ -38,6 +57,17 @@ int main(int argc, char** argv) {
             else if (a == "-accumulate") opts.accumulate = true;
             else if (a == "-no-temporal") opts.temporalOrder = false;
             else if (a == "-drain") { need(1); opts.drainThreshold = std::atoi(argv[++i]); }
+            else if (a == "-reproject" || a == "-denoise") {
+                need(1);
+                const bool r = a == "-reproject";
+                (r ? reproject : denoise) = true;
+                if (!parseTriple(argv[++i], r ? rp : sigma)) {
+                    std::fprintf(stderr, r ? "-reproject takes TOL:NMIN:MAXH (numbers, inf or -inf)\n"
+                                           : "-denoise takes SC:SN:SX (numbers or inf)\n");
+                    return 2;
+                }
+            }
+            else if (a == "-denoise-iters") { need(1); denoiseIters = std::atoi(argv[++i]); denoiseItersGiven = true; }
             else if (a == "-bvh") {
                 need(1);
                 std::string m = argv[++i];
@@ -51,7 +81,25 @@ int main(int argc, char** argv) {
         if (script != "still" && script != "walk" && script != "orbit" && script != "hq")
             throw std::runtime_error("unknown script " + script);
 
+        if (denoise && !reproject) {
+            std::fprintf(stderr, "-denoise filters the history: it needs -reproject\n");
+            return 2;
+        }
+        if (denoiseItersGiven && !denoise) {
+            std::fprintf(stderr, "-denoise-iters counts the filter's iterations: it needs -denoise\n");
+            return 2;
+        }
+        if (reproject && opts.accumulate) {
+            std::fprintf(stderr, "-reproject and -accumulate exclude each other\n");
+            return 2;
+        }
+
         CRT::Raytracer rt(W, H, ASPECT_RATIO, 80.0f, 0.000001f, opts);
+        if (reproject) {
+            const crt_reproject_options ro{rp[0], rp[1], rp[2], 0u, 0};
+            const crt_denoise_options dn{denoiseIters, sigma[0], sigma[1], sigma[2], 0u, 0};
+            rt.setReproject(&ro, denoise ? &dn : nullptr);
+        }
         const float dt = 1.0f / 60.0f;
         auto input = [&](long long f, float* dtOut) {
             *dtOut = dt;
@@ -66,11 +114,13 @@ int main(int argc, char** argv) {
             return in;
         };
         std::vector<double> frameMs, kernelMs;
+        double guidesMs = 0, reprojectMs = 0, filterMs = 0;
         long long samples = 0;
         CRT::FrameInfo last;
         rt.run(frames, input, [&](const CRT::FrameInfo& fi) {
             frameMs.push_back(fi.frameMs);
             kernelMs.push_back(fi.kernelMs);
+            guidesMs += fi.guidesMs; reprojectMs += fi.reprojectMs; filterMs += fi.filterMs;
             samples += fi.spp;
             last = fi;
         });
@@ -88,11 +138,17 @@ int main(int argc, char** argv) {
         std::printf("{\"width\": %d, \"height\": %d, \"script\": \"%s\", \"bvh\": \"%s\", \"accumulate\": %s, "
                     "\"temporal\": %s, \"drain\": %d, \"frames\": %lld, \"fps\": %.1f, \"frame_ms_mean\": %.3f, \"frame_ms_p50\": %.3f, "
                     "\"frame_ms_p99\": %.3f, \"kernel_ms_mean\": %.3f, \"samples_per_pixel_total\": %lld, "
-                    "\"paths_per_s\": %.4g, \"last_accumulated\": %d}\n",
+                    "\"paths_per_s\": %.4g, \"last_accumulated\": %d",
                     W, H, script.c_str(), opts.scene.bvh == CRT_BVH_REBUILT ? "rebuilt" : "reference",
                     opts.accumulate ? "true" : "false", opts.temporalOrder ? "true" : "false", opts.drainThreshold, frames, n ? 1000.0 * n / tot : 0.0, n ? tot / n : 0.0,
                     pct(0.5), pct(0.99), n ? ktot / n : 0.0, samples,
                     tot > 0 ? (double)W * H * samples / (tot / 1e3) : 0.0, last.accumulated);
+        if (reproject)
+            std::printf(", \"reproject\": \"%g:%g:%g\", \"guides_ms_mean\": %.3f, \"reproject_ms_mean\": %.3f, "
+                        "\"filter_ms_mean\": %.3f, \"pixels_reprojected_last\": %u",
+                        rp[0], rp[1], rp[2], n ? guidesMs / n : 0.0, n ? reprojectMs / n : 0.0, n ? filterMs / n : 0.0,
+                        last.pixelsReprojected);
+        std::printf("}\n");
         return EXIT_SUCCESS;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "Error: %s\n", e.what());

@@ -2,7 +2,7 @@
 
     make -C <tree>/raytracer-cuda_amd isa > <tree>/isa.log 2>&1      (in both trees)
     python tools/kernels_unchanged.py <parent tree> <this tree> [--show 'crt_render_kernel<false, 8, 7>' ...]
-                                      [--expect-changed crt_path_step_kernel ...]
+                                      [--expect-changed crt_path_step_kernel ...] [--all]
 
 Compares, for every crt_render_kernel / crt_trace_kernel / crt_trace_lane_kernel instantiation, their indirect forms
 and the path kernels (crt_camera_rays_kernel, crt_path_step_kernel, crt_path_advance_kernel and its indirect form,
@@ -11,10 +11,12 @@ crt_path_finish_kernel), the figures of
 .end_amdhsa_kernel: every instruction and the kernel descriptor.  The compiler numbers a function's local labels
 `.LBB<f>_<b>` with f = the function's position in the module; a kernel added ahead of the template instantiations
 shifts f for all of them without changing an instruction, so f is replaced by a constant before the comparison (b, the
-block number inside the function, stays).  Prints the kernels that differ, the totals, the figures of the kernels named
+block number inside the function, stays); a label's trailing comment is padded to a fixed column, so when f gains a
+digit the padding loses a blank, and the blanks between a label and its comment are made one.  Prints the kernels that differ, the totals, the figures of the kernels named
 with --show and of every kernel only the second tree has; exit status 1 if any kernel differs.  A kernel named with
 --expect-changed may differ: it is printed with both trees' figures and instruction counts, and sets exit status 1
-only if a figure got worse (more VGPRs, any scratch or spill, fewer waves per SIMD, more LDS).
+only if a figure got worse (more VGPRs, any scratch or spill, fewer waves per SIMD, more LDS).  --all compares every
+kernel of the parent's build (the self-test, adaptive and denoiser kernels too), not only the families named above.
 """
 import argparse
 import re
@@ -37,7 +39,7 @@ def kernels(asm: Path) -> dict:
         if name is not None:
             buf.append(line)
             if ".end_amdhsa_kernel" in line:
-                out[name] = re.sub(r"BB\d+_", "BBf_", "".join(buf))
+                out[name] = re.sub(r"(?m)^(\.LBBf_\d+:)[ \t]+;", r"\1 ;", re.sub(r"BB\d+_", "BBf_", "".join(buf)))
                 name = None
     return out
 
@@ -83,12 +85,13 @@ def main():
     ap.add_argument("now")
     ap.add_argument("--show", nargs="*", default=[])
     ap.add_argument("--expect-changed", nargs="*", default=[], metavar="NAME")
+    ap.add_argument("--all", action="store_true")
     a = ap.parse_args()
     trees = [Path(a.parent), Path(a.now)]
     asm = [kernels(t / "raytracer-cuda_amd" / "build" / "crt_hip.s") for t in trees]
     fig = [figures(t / "isa.log") for t in trees]
     names = demangle(sorted(set(asm[0]) | set(asm[1])))
-    old = [k for k in asm[0] if any(w in k for w in WANTED)]
+    old = [k for k in asm[0] if a.all or any(w in k for w in WANTED)]
     differ = [k for k in old if asm[1].get(k) != asm[0][k] or fig[1].get(k) != fig[0][k]]
     short = {k: names[k].replace("void ", "").split("(")[0] for k in names}
     failed = [k for k in differ if short[k] not in a.expect_changed]
@@ -103,7 +106,7 @@ def main():
         if bad:
             failed.append(k)
     n_render = sum("crt_render_kernel" in k for k in old)
-    print(f"{len(old)} kernels compared ({n_render} crt_render_kernel, {len(old) - n_render} ray-query and path-step kernels): "
+    print(f"{len(old)} kernels compared ({n_render} crt_render_kernel, {len(old) - n_render} {'other' if a.all else 'ray-query and path-step'} kernels): "
           f"{len(old) - len(differ)} with the same figures and assembly text, {len(differ)} different; "
           f"{sum(asm[0][k].count(chr(10)) for k in old):,} lines in the parent, "
           f"{sum(asm[1][k].count(chr(10)) for k in old if k in asm[1]):,} now")
