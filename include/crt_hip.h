@@ -770,6 +770,22 @@ const char* crt_renderer_last_kernel_name(const crt_renderer* r);
  * any other kernel, no launch yet, or r == NULL.  Added within ABI 3: a caller that may load an older library looks
  * the symbol up first. */
 int crt_renderer_last_launch_frozen(const crt_renderer* r);
+/* Tail fill of a variant-8 launch (one 8x8 tile per one-wave workgroup, most expensive first).  Such a launch ends
+ * with a drain: the last tiles leave most wave slots empty, and the smallest item is a whole tile's samples.  With
+ * tail fill the heads of the first `tiles` tiles of the cost order render all but their last `spp` samples, and those
+ * samples follow the launch's tiles as small items: each continues its pixels from the stored sums and RNG state,
+ * every pixel on one lane and its samples in order, as a render with CRT_RENDER_ACCUMULATE continues a frame.  No
+ * workgroup waits for another: a part that finds its tile's head unfinished is rendered by a second, short launch.
+ * tiles < 0: automatic (the default): on where variant 8 runs with the cost probe at the automatically chosen
+ * occupancy 7, unsharded and not counting, and the held-back samples reach a floor; off elsewhere.  tiles == 0: off.
+ * tiles > 0: the first `tiles` tiles (clamped to the tile count) hold back `spp` samples in every plain variant-8
+ * render on one shard; a render for which `spp` is not within 1 .. its samples - 1 runs without it.
+ * Results never depend on it.  Added within ABI 3: a caller that may load an older library looks the symbol up first. */
+int crt_renderer_set_tail_fill(crt_renderer* r, int tiles, int spp);
+/* The last render's tail fill: out = {tiles, held-back samples, parts rendered inside the main launch, parts rendered
+ * by the sweep launch after it}; the two counts add up to tiles.  All 0 when it rendered without tail fill.  Waits for
+ * that render to end.  Results never depend on it.  Added within ABI 3 (looked up like the setter). */
+int crt_renderer_last_tail_fill(crt_renderer* r, int out[4]);
 
 /* ---- GPU-parallel mesh BVH build (replaces Mesh::buildBVHMesh <<<1,1>>>, Mesh.cuh:121-264, and the Mesh ctor
  * box, Mesh.cuh:39-47; launched by initMesh, CUDAKernels.h:28-33) ----

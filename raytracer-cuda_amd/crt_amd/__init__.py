@@ -447,6 +447,19 @@ class Renderer:
     def set_critical_tiles(self, tiles: int = -1, lanes: int = 16):
         check(_lib.hip().crt_renderer_set_critical_tiles(self.h, int(tiles), int(lanes)), "set_critical_tiles")
 
+    def set_tail_fill(self, tiles: int = -1, spp: int = 0):
+        """Variant 8: the first `tiles` tiles of the cost order hold back their last `spp` samples, which follow the
+        launch's tiles as small items (crt_renderer_set_tail_fill; -1 = automatic, 0 = off).  Results never depend on
+        it.  Raises CrtError naming the entry when the loaded library predates it."""
+        check(_lib.require("crt_renderer_set_tail_fill")(self.h, int(tiles), int(spp)), "set_tail_fill")
+
+    def last_tail_fill(self) -> dict:
+        """The last render's tail fill (crt_renderer_last_tail_fill): tiles, held-back samples, parts rendered inside
+        the main launch and by the sweep; all 0 when it rendered without.  Waits for that render."""
+        a = (C.c_int * 4)()
+        check(_lib.require("crt_renderer_last_tail_fill")(self.h, a), "last_tail_fill")
+        return dict(zip(("tiles", "spp", "in_launch", "swept"), (int(v) for v in a)))
+
     def set_top_levels(self, levels: int = -1):
         """4-wide kernels: a new ray's first node steps from the LDS copy of the tree's top nodes (-1 = default)."""
         check(_lib.hip().crt_renderer_set_top_levels(self.h, int(levels)), "set_top_levels")

@@ -91,6 +91,20 @@ struct RenderParams {
     int wave_drain;                       // variants 4/8: sixty-fourths of the live lanes a draining wave passes at
     int top_levels;                       // 4-wide variants: a new ray's first node steps taken from LDS (<= CRT_TOP_LEVELS)
 };
+// Variant 8's tail fill (crt_renderer_set_tail_fill, fill_prologue) reads its launch arguments from the fields of
+// variant 7's pixel queue and of variant 4's probe, which no variant-8 kernel reads (a launch is one variant): the
+// struct, and with it the argument layout of every kernel that takes it, stays as it is.
+//   queue            null = no tail fill; else two counts (the tail parts rendered by the main launch and by the sweep),
+//                    then one flag per rank of the cost order: 0, 1 = the head stored its state, 2 = the tail part is
+//                    rendered
+//   n_slots          blocks below it are heads (the launch's tiles; 0 in the sweep)
+//   drain_threshold  K: the heads of the first K ranks hold back their last samples
+//   probe_stride     delta: the samples they hold back
+__device__ __forceinline__ uint32_t* fill_flags(const RenderParams& P) { return P.queue + 2; }
+__device__ __forceinline__ uint32_t* fill_done(const RenderParams& P) { return P.queue + (P.n_slots ? 0 : 1); }
+__device__ __forceinline__ uint32_t fill_heads(const RenderParams& P) { return (uint32_t)P.n_slots; }
+__device__ __forceinline__ uint32_t fill_tiles(const RenderParams& P) { return (uint32_t)P.drain_threshold; }
+__device__ __forceinline__ int fill_spp(const RenderParams& P) { return P.probe_stride; }
 
 #ifdef CRT_PROFILE_LIVE
 // profiling build (tools/live_histogram.py): variant 8's wave time by the number of lanes that still have samples,
@@ -670,6 +684,16 @@ constexpr int wide_stack_entries(int minw) { return minw >= 7 ? CRT_STACK7 : min
 // crt_renderer_set_wave_drain).  The frozen render kernels (crt_render_body.inc) hold them as constants.
 constexpr int REGEN_THRESHOLD_WIDE = 44;   // measured: 40 for variant 4, profiles/r01d; 44-48 for 8, r01af
 constexpr int WAVE_DRAIN = 48;             // draining waves pass at 48/64 of their live lanes (profiles/r04n)
+// Tail fill's automatic choice (render_tiles, crt_renderer_set_tail_fill with tiles < 0; measured: profiles/tail_fill):
+// the first NUM/DEN of the cost order hold back spp / SPP_DEN samples (config C: the first half, 125 of 2000 samples,
+// -3.3 %; 250 of them -2.7 %, 500 -2.2 %; a quarter or three quarters of the tiles at 250: -2.8 %).  Every part ends
+// with its wave's own drain, whose share of the part grows as the part shrinks; the smallest part measured (15 samples,
+// the first half of a 250-spp frame: -1.8 %) still gained, nothing below it was measured, so a render whose parts
+// would hold fewer than MIN_SPP samples (one of fewer than 192 samples) keeps the plain launch.
+#ifndef CRT_FILL_AUTO
+#define CRT_FILL_AUTO 1
+#endif
+constexpr int CRT_FILL_TILES_NUM = 1, CRT_FILL_TILES_DEN = 2, CRT_FILL_SPP_DEN = 16, CRT_FILL_MIN_SPP = 12;
 
 struct Wide4 {
     float tmin[4];
@@ -1620,6 +1644,64 @@ __device__ unsigned long long g_wave_prof[2 * 4 * 65536];
 __device__ unsigned long long g_crit_trace[2 * 16384];
 __device__ unsigned g_wave_hw[2 * 4 * 65536];
 #endif
+
+// ---- tail fill: the prologue and epilogue of a variant-8 block (crt_render_body.inc) ----
+// A launch with tail fill has fill_heads + fill_tiles blocks.  Block b < fill_heads is the head of the tile at rank b
+// of the cost order: for b < fill_tiles it renders the first spp - fill_spp samples of its pixels, stores their sums
+// and RNG state as every block does and sets the rank's flag to 1.  Block fill_heads + k is the tail part of rank k:
+// it continues those pixels from the stored sums and state over the last fill_spp samples, exactly as a render with
+// CRT_RENDER_ACCUMULATE continues a frame, and sets the flag to 2.  Blocks are dispatched in index order, so the tail
+// parts arrive when the launch starts to drain, as small items of tiles that ended long before.  A tail part whose
+// flag is not 1 returns at once and touches nothing: no block ever waits for another (no loop in these helpers,
+// tests/test_tail_fill_cpu.py), and the sweep launch that follows on the stream (fill_heads = 0: tail parts only)
+// renders what is left.  The flag's release and acquire are at agent scope: a head and its tail part usually run
+// on different XCDs, whose L2s are not coherent with each other.
+// fill_prologue: the block's rank, sample count and whether it continues stored sums; false = return at once.  `note`
+// (LDS of the wave) keeps for fill_epilogue the flag to set and its value (0: none), so that nothing of this, not
+// even the launch argument that holds the flags, is live in a register across the render loop.
+struct FillNote {
+    uint32_t* flag;    // the rank's flag
+    uint32_t* done;    // the launch's count of rendered tail parts
+    uint32_t set;      // 0: nothing to set; 1: a head that held samples back; 2: a tail part
+};
+__device__ __forceinline__ bool fill_prologue(const RenderParams& P, uint32_t b, uint32_t& rank, int& spp, int& accumulate,
+                                              FillNote* note) {
+    rank = b;
+    spp = P.spp;
+    accumulate = P.accumulate;
+    uint32_t set = 0;
+    if (P.queue) {
+        if (b >= fill_heads(P)) {
+            rank = b - fill_heads(P);
+            const uint32_t f = __hip_atomic_load(fill_flags(P) + rank, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+            if (__builtin_amdgcn_readfirstlane(f) != 1u) return false;
+            spp = fill_spp(P);
+            accumulate = 1;
+            set = 2;
+        } else if (b < fill_tiles(P)) {
+            spp = P.spp - fill_spp(P);
+            set = 1;
+        }
+    }
+    if (threadIdx.x == 0) {
+        note->flag = set ? fill_flags(P) + rank : nullptr;
+        note->done = set ? fill_done(P) : nullptr;
+        note->set = set;
+    }
+    return true;
+}
+// fill_epilogue: after the block stored its pixels' sums and state.  The barrier orders every lane's stores before
+// lane 0's release (one wave per workgroup).
+__device__ __forceinline__ void fill_epilogue(const FillNote* note, int lane) {
+    const uint32_t set = __builtin_amdgcn_readfirstlane(note->set);
+    if (set == 0) return;
+    __syncthreads();
+    if (lane == 0) {
+        __hip_atomic_store(note->flag, set, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        if (set == 2u) atomicAdd(note->done, 1u);
+    }
+}
+// ---- end of the tail-fill helpers ----
 
 // Waves per workgroup: 4 (16x16 pixels), or 1 for variant 8 (one 8x8 tile per workgroup, so a finished wave frees
 // its slot at once instead of holding it until its three siblings end).
@@ -2812,7 +2894,13 @@ struct crt_renderer {
     int temporal = 0;              // variant 7: tiles ordered by the previous variant-7 frame's rays per pixel
     int drain_threshold = 0;       // variant 7: regeneration threshold once the pixel queue is empty (0 = unchanged)
     int wave_drain = WAVE_DRAIN;   // variants 4/8: sixty-fourths of its live lanes a draining wave passes at
-    DevBuf<uint32_t> d_pix_rays;      // variant 7 with the temporal order: rays per pixel of the last frame
+    // variant 8, tail fill (crt_renderer_set_tail_fill): fill_tiles < 0 = automatic, 0 = off, else K with fill_spp = delta
+    int fill_tiles = -1, fill_spp = 0;
+    DevBuf<uint32_t> d_fill;           // the tail parts rendered by the main launch and by the sweep, then one flag per tile rank
+    PinnedBuf<uint32_t> h_fill;        // those two counts of the last render with tail fill (copied on its stream before ev1)
+    int last_fill[2] = {0, 0};         // K and delta of the last render (0, 0: rendered without tail fill)
+    hipEvent_t last_fill_ev = nullptr; // that render's ev1
+    DevBuf<uint32_t> d_pix_rays;     // variant 7 with the temporal order: rays per pixel of the last frame
     DevBuf<uint32_t> d_tile_order;    // its tiles, most expensive first
     bool pix_rays_valid = false;
     int min_waves = 0;             // occupancy target (waves/SIMD); 0 = auto: 7 for variant 8 over >= 4 tiles per wave
@@ -3439,13 +3527,28 @@ static int launch_render(crt_renderer* R, const RenderRow& row, bool cnt, dim3 g
     if (row.open && !S) return set_error(CRT_ERR_INVALID_ARGUMENT, "launch_render: a variant-8 launch needs its scene");
     R->last_frozen = render_launch_frozen(row, cnt, P, S) ? 1 : 0;
     HIP_TRY(hipEventRecord(R->ev_main, st));
-    if (R->last_frozen) {
-        RenderParams Q = P;
-        Q.stack_lds = wide_stack_entries(row.w);   // the fact as the kernel states it (a smaller own bound: see above)
-        hipLaunchKernelGGL(row.plain, grid, block, 0, st, Q);
-    } else {
-        hipLaunchKernelGGL(cnt ? row.counting : row.open ? row.open : row.plain, grid, block, 0, st, P);
+    RenderParams Q = P;
+    // frozen: the stack fact as the kernel states it (a smaller own bound: see above)
+    if (R->last_frozen) Q.stack_lds = wide_stack_entries(row.w);
+    const RenderKernel kernel = R->last_frozen ? row.plain : cnt ? row.counting : row.open ? row.open : row.plain;
+    R->last_fill[0] = R->last_fill[1] = 0;
+    if (row.variant != 8 || !P.queue) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, Q);
+        return CRT_OK;
     }
+    // Tail fill (render_tiles set it up; fill_prologue): the grid's blocks are the heads, K tail parts follow them, and
+    // a sweep of tail parts only renders the ranks whose tail part found its head unfinished.  Both launches lie
+    // between ev_main and ev1.
+    const int k = P.drain_threshold, delta = P.probe_stride;
+    HIP_TRY(hipMemsetAsync(R->d_fill.get(), 0, ((size_t)k + 2) * sizeof(uint32_t), st));
+    Q.n_slots = (int)grid.x;
+    hipLaunchKernelGGL(kernel, dim3(grid.x + (unsigned)k), block, 0, st, Q);
+    Q.n_slots = 0;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)k), block, 0, st, Q);
+    HIP_TRY(hipMemcpyAsync(R->h_fill.get(), R->d_fill.get(), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    R->last_fill[0] = k;
+    R->last_fill[1] = delta;
+    R->last_fill_ev = R->ev1;
     return CRT_OK;
 }
 
@@ -3459,6 +3562,8 @@ static int ensure_order_buffers(crt_renderer* R, hipStream_t st, size_t n_pix, i
         HIP_TRY(R->d_queue.alloc(1));
         HIP_TRY(R->d_tile_cost.alloc(n_pix));
         HIP_TRY(R->d_order_hist.alloc(ORDER_KEYS));
+        HIP_TRY(R->d_fill.alloc((size_t)n_tiles + 2));
+        HIP_TRY(R->h_fill.alloc(2));
         HIP_TRY(hipDeviceGetAttribute(&R->n_cus, hipDeviceAttributeMultiprocessorCount, R->device));
     }
     if (want_tile_key && !R->d_tile_key) HIP_TRY(R->d_tile_key.alloc((size_t)n_tiles));
@@ -3659,6 +3764,25 @@ static int render_tiles(crt_renderer* R, const crt_scene* S, hipStream_t st, Ren
     }
     if (P.crit_tiles > 0) P.crit_tiles = (P.crit_tiles + shards - 1) / shards;
     if (variant == 8) R->last_schedule[1] = (float)occ;
+    if (variant == 8 && !cnt && shards == 1 && R->fill_tiles != 0) {
+        // Tail fill (fill_prologue).  Automatic: where the launch is long against its items, i.e. the
+        // probe-ordered launch at the automatic occupancy 7 (at least 4 tiles per wave slot), the first
+        // CRT_FILL_TILES_NUM / CRT_FILL_TILES_DEN of the cost order hold back spp / CRT_FILL_SPP_DEN samples, unless that
+        // is fewer than CRT_FILL_MIN_SPP.  A delta outside 1..spp-1 renders without it.
+        int k = R->fill_tiles, delta = R->fill_spp;
+        if (k < 0) {
+            const bool on = CRT_FILL_AUTO && P.order && probe_spp_for(R, spp) > 0 && !R->min_waves && occ == 7;
+            k = on ? (int)((long long)n_tiles * CRT_FILL_TILES_NUM / CRT_FILL_TILES_DEN) : 0;
+            delta = spp / CRT_FILL_SPP_DEN;
+            if (delta < CRT_FILL_MIN_SPP) k = 0;
+        }
+        k = std::min(k, n_tiles);
+        if (k > 0 && delta >= 1 && delta <= spp - 1) {
+            P.queue = R->d_fill.get();     // the tail fill's arguments (see RenderParams)
+            P.drain_threshold = k;
+            P.probe_stride = delta;
+        }
+    }
     const dim3 tgrid((unsigned)((n_tiles - shard + shards - 1) / shards));
     return launch_render(R, RENDER_ROWS[render_row(variant, cnt, occ)], cnt, tgrid, dim3(64), st, P, S);
 }
@@ -3929,6 +4053,24 @@ uint32_t* crt_renderer_rng_device_ptr(crt_renderer* R) { return R ? R->d_rng.get
 
 const char* crt_renderer_last_kernel_name(const crt_renderer* R) { return R ? R->kernel_name : ""; }
 int crt_renderer_last_launch_frozen(const crt_renderer* R) { return R ? R->last_frozen : 0; }
+
+int crt_renderer_set_tail_fill(crt_renderer* R, int tiles, int spp) {
+    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "null renderer");
+    R->fill_tiles = tiles < 0 ? -1 : tiles;
+    R->fill_spp = tiles > 0 ? spp : 0;
+    return CRT_OK;
+}
+
+int crt_renderer_last_tail_fill(crt_renderer* R, int out[4]) {
+    if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
+    out[0] = R->last_fill[0]; out[1] = R->last_fill[1]; out[2] = out[3] = 0;
+    if (out[0] == 0) return CRT_OK;
+    HIP_TRY(hipSetDevice(R->device));
+    HIP_TRY(hipEventSynchronize(R->last_fill_ev));   // the render's ev1: its copy of the two counts is done
+    out[2] = (int)R->h_fill.get()[0];
+    out[3] = (int)R->h_fill.get()[1];
+    return CRT_OK;
+}
 
 #ifdef CRT_PROFILE_PAIRS
 extern "C" int crt_profile_pair_hist(unsigned long long* out32, int reset) {

@@ -5,6 +5,17 @@
 // wave_drain and regeneration threshold.  The facts are stated, not assigned: writing them into P makes the whole
 // struct a stack object (536 B of scratch per lane).
     static_assert(!FROZEN || (VARIANT == 8 && !COUNT), "only the plain variant-8 kernels have a frozen twin");
+    // Variant 8: the block's rank in the cost order, its samples and whether it continues stored sums: the launch's,
+    // except with tail fill, where the block is the head or the tail part of a tile (fill_prologue).  First of all:
+    // the tail part's acquire is a barrier to the compiler, and a value of P read before it is read again after it, so
+    // stated ahead of it the frozen facts below would not reach the loop.  (The other kernels read P.spp, P.accumulate
+    // and blockIdx.x where they did.)
+    uint32_t rank = 0;
+    int blk_spp = 0, blk_accumulate = 0;
+    __shared__ FillNote fill_note;             // fill_prologue's note for fill_epilogue
+    if constexpr (VARIANT == 8) {
+        if (!fill_prologue(P, blockIdx.x, rank, blk_spp, blk_accumulate, &fill_note)) return;
+    }
     if constexpr (FROZEN) {
         constexpr int FROZEN_STACK = wide_stack_entries(MINW);   // (a call inside the assumption makes the compiler drop it)
         __builtin_assume(P.stack_lds == FROZEN_STACK);
@@ -67,8 +78,9 @@
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: LDS bases stay scalar
     int x, y;
-    if (TILES) {                               // workgroup b renders 8x8 tile order[b]
-        const uint32_t t = P.order ? P.order[blockIdx.x] : blockIdx.x;
+    if (TILES) {                              // workgroup b renders 8x8 tile order[b]
+        const uint32_t b = TILED ? rank : blockIdx.x;
+        const uint32_t t = P.order ? P.order[b] : b;
         x = (int)(t % (uint32_t)P.tiles_x) * 8 + (lane & 7);
         y = (int)(t / (uint32_t)P.tiles_x) * 8 + (lane >> 3);
     } else {
@@ -98,8 +110,9 @@
     if (valid && !PERSIST) {
         const uint32_t* r = P.rng + 6 * (size_t)pix;
         S.s = rng_load(r);
-        if (P.accumulate) S.pixel = v3(P.sum[3 * (size_t)pix], P.sum[3 * (size_t)pix + 1], P.sum[3 * (size_t)pix + 2]);
-        S.remaining = P.spp;
+        if (TILED ? blk_accumulate : P.accumulate)
+            S.pixel = v3(P.sum[3 * (size_t)pix], P.sum[3 * (size_t)pix + 1], P.sum[3 * (size_t)pix + 2]);
+        S.remaining = TILED ? blk_spp : P.spp;
     }
     const CamRegs C = cam_regs(P.cam, P.width, P.height, P.rcp_w, P.rcp_h, P.fast_uv);
     TraceCounts cnt{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -237,7 +250,7 @@
         if (TILED && lane == 0) L.rays = 0;
         // variant 8: the most expensive tiles of the cost order bound the frame when it has few tiles per wave slot
         // (their pixels' sample chains are sequential); they regenerate sooner (DESIGN.md §5b, profiles/r02h)
-        const int regen_t = (TILED && (int)blockIdx.x < P.crit_tiles) ? P.crit_threshold : P.regen_threshold;
+        const int regen_t = (TILED && (int)rank < P.crit_tiles) ? P.crit_threshold : P.regen_threshold;
         bool first_pass = true;    // uniform
         // variant 8 at occupancy 4 (frames of few tiles per wave slot, bound by their most expensive tiles' sample
         // chains): the next node's rows load during the leaf round (traverse_step4<.., true>, profiles/r06r, r06s)
@@ -466,6 +479,7 @@
         P.sum[3 * (size_t)pix + 1] = S.pixel.y;
         P.sum[3 * (size_t)pix + 2] = S.pixel.z;
     }
+    if constexpr (TILED) fill_epilogue(&fill_note, lane);
     if constexpr (TILED) wave_rays = lds[0].rays;
     const uint64_t wr = TILED ? (uint64_t)wave_rays : wave_sum_u64(S.rays);
     if (COUNT) {

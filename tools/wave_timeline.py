@@ -32,6 +32,8 @@ ap.add_argument("--temporal", action="store_true",
                      "rays per pixel (crt_renderer_set_temporal_order)")
 ap.add_argument("--drain", type=int, default=0, help="variant 7's drain threshold (crt_renderer_set_drain_threshold)")
 ap.add_argument("--wave-drain", type=int, default=48, help="variants 4/8 wave drain in 64ths (crt_renderer_set_wave_drain)")
+ap.add_argument("--tail-fill", type=int, nargs=2, metavar=("TILES", "SPP"), default=None,
+                help="variant 8: crt_renderer_set_tail_fill (default: the library's automatic rule; 0 0 = off)")
 a = ap.parse_args()
 
 hs = crt_amd.HostScene(assets.scene_files(a.scene))
@@ -40,6 +42,8 @@ r = crt_amd.Renderer(a.w, a.h)
 r.set_kernel_variant(a.variant)
 r.set_drain_threshold(a.drain)
 r.set_wave_drain(a.wave_drain)
+if a.tail_fill is not None:
+    r.set_tail_fill(*a.tail_fill)
 r.set_camera(crt_amd.camera(a.spp))
 r.init_rand(41)
 if a.temporal:
@@ -48,12 +52,20 @@ if a.temporal:
 r.render(sc, a.spp, 20)
 r.synchronize()
 kernel_ms = r.last_kernel_ms()
-n_waves = (((a.w + 7) // 8) * ((a.h + 7) // 8) if a.variant == 8 else
+n_tiles = ((a.w + 7) // 8) * ((a.h + 7) // 8)
+fill = r.last_tail_fill() if a.variant == 8 else {"tiles": 0, "spp": 0, "in_launch": 0, "swept": 0}
+# variant 8 with tail fill: the tail parts are blocks n_tiles .. n_tiles + K - 1 (a part that returned at once left no
+# record; a part the sweep rendered recorded over its head, block k)
+n_waves = (n_tiles + fill["tiles"] if a.variant == 8 else
            a.persistent_waves if a.variant == 7 else ((a.w + 15) // 16) * ((a.h + 15) // 16) * 4)
 L = _lib.hip()
 L.crt_profile_wave_times.argtypes = [C.c_void_p, C.c_int]
 buf = np.zeros((n_waves, 2), np.uint64)
 _lib.check(L.crt_profile_wave_times(buf.ctypes.data_as(C.c_void_p), n_waves), "crt_profile_wave_times")
+if fill["tiles"]:
+    # records of the tail parts' slots that this launch did not write are older than the launch's first head
+    buf = buf[buf[:, 0] >= buf[:n_tiles, 0].min()]
+    n_waves = len(buf)
 t = (buf.astype(np.int64) - int(buf[:, 0].min())) / 100.0   # 100 MHz ticks -> microseconds
 start, end = t[:, 0], t[:, 1]
 span = float(end.max())
@@ -75,7 +87,7 @@ for i in range(20):
     lo, hi = bins[i], bins[i + 1]
     ov = np.clip(np.minimum(end, hi) - np.maximum(start, lo), 0, None).sum() / (hi - lo)
     occ.append(round(float(ov), 1))
-out = {"scene": a.scene, "bvh": a.bvh, "variant": a.variant, "temporal": a.temporal, "drain": a.drain, "wave_drain": a.wave_drain, "kernel": r.last_kernel_name(), "spp": a.spp, "kernel_ms": round(kernel_ms, 3), "span_ms": round(span / 1e3, 3),
+out = {"scene": a.scene, "bvh": a.bvh, "variant": a.variant, "temporal": a.temporal, "drain": a.drain, "wave_drain": a.wave_drain, "tail_fill": fill, "kernel": r.last_kernel_name(), "spp": a.spp, "kernel_ms": round(kernel_ms, 3), "span_ms": round(span / 1e3, 3),
        "waves": n_waves, "peak_resident_waves": peak, "occupancy_efficiency": round(eff, 4),
        "tail_ms": round((span - steady_end) / 1e3, 3), "tail_fraction": round((span - steady_end) / span, 4),
        "wave_ms": {"min": round(float(dur.min()) / 1e3, 3), "median": round(float(np.median(dur)) / 1e3, 3),
