@@ -860,6 +860,10 @@ extern "C" int crt_build_mesh_bvh(int device, const float* positions, uint32_t v
 // split (all centroids equal) splits in half.  Bin counts and boxes are order-independent, so the splits
 // equal the host's; the partition here is stable (the host's std::partition is not), so only the order
 // of items inside a node can differ — any order is a valid tree for the rank rule.
+// The one exception: a node halved for want of a split (every centre bit-equal) takes the lower half of
+// its items' order, here the stable one, on the host std::nth_element's over equal keys.  Child sizes and
+// topology agree; which items each half holds, and so the boxes below such a node when the coincident
+// items' boxes differ, are each builder's own (tests/test_gpu_sah_build.py).
 // ======================================================================================================
 #include "crt_sah.h"
 #include "crt/ParallelFor.h"

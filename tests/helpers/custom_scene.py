@@ -188,6 +188,47 @@ def synth_worlds(files):
     return out
 
 
+# worlds for the split-by-split checks of the SAH builders (tests/helpers/sah_model.py)
+SAH_WORLDS = ("spheres9", "spheres17", "spheres40", "soup200_spheres12", "concentric", "concentric_soup",
+              "concentric_tris", "grid8", "grid24")
+# Triangle counts of the sized soups.  The GPU builder's constants are item counts: SAH_SMALL 16 / 17, SCAN_ITEMS 1024,
+# SAH_CHUNK 4096 and twice that.  At width 4 a soup of n triangles is n items, at width 2 it is n + 2 (SizedSoup), so
+# n - 2 stands next to every n.
+SAH_SOUP_SIZES = (1, 2, 14, 15, 16, 17, 33, 1022, 1023, 1024, 1025)    # checked split by split (and host against GPU)
+SAH_SOUP_SIZES_BIG = (4093, 4094, 4095, 4096, 4097, 8191, 8193, 20000)  # host against GPU only
+
+
+class SizedSoup:
+    """synth_scenes.sized_soup(n) through SceneManager itself (crt_amd.HostScene: the standard sphere pair).  At width
+    4 the pair is tested per ray and the SAH builder sees exactly n items; at width 2 every sphere is an item: n + 2."""
+
+    def __init__(self, directory, n):
+        import synth_scenes as synth
+        self.n = n
+        self.hs = crt_amd.HostScene(synth.sized_soup(str(directory), n))
+        self.desc = self.hs.desc()
+
+    def export(self, bvh="reference", **options):
+        return crt_amd.export_desc(self.desc, bvh, **options)
+
+
+def sah_worlds(directory):
+    """name -> CustomScene: sphere worlds of more than 8 spheres (all of them items of the tree, alone and among 200
+    triangles), 20 concentric spheres (coincident box centres; alone and among 100 triangles), 20 concentric triangles
+    and the rippled grids."""
+    import synth_scenes as synth
+    d = str(directory)
+    out = {f"spheres{k}": CustomScene([], synth.random_spheres(k, seed=30 + k), synth.SPHERE_MATS) for k in (9, 17, 40)}
+    out["soup200_spheres12"] = CustomScene(synth.sized_soup(d, 200), synth.random_spheres(12, seed=29), synth.SPHERE_MATS)
+    out["concentric"] = CustomScene([], synth.concentric_spheres(), synth.SPHERE_MATS)
+    out["concentric_soup"] = CustomScene(synth.sized_soup(d, 100), synth.concentric_spheres(), synth.SPHERE_MATS)
+    out["concentric_tris"] = CustomScene(synth.concentric_triangles(d))
+    out["grid8"] = CustomScene(synth.grid(d, 8))
+    out["grid24"] = CustomScene(synth.grid(d, 24))
+    assert set(out) == set(SAH_WORLDS)
+    return out
+
+
 def world_offset(name):
     import synth_scenes as synth
     return np.asarray(synth.FAR_OFFSET if name == "far" else (0, 0, 0), np.float32)

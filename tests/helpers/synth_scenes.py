@@ -213,6 +213,57 @@ def far(directory, seed=606, n=600):
 FAR_OFFSET = (1000.0, 1000.0, -1000.0)
 
 
+def sized_soup(directory, n, seed=707):
+    """The soup recipe with exactly n triangles (file soup_<n>.obj): item counts at the builders' constants."""
+    return soup(directory, seed, n, name=f"soup_{n}")
+
+
+def grid_arrays(k, ripple=0.0):
+    """A regular k x k quad grid in the plane y = 0 with shared vertices: ((k + 1)^2 vertices float32, 2 k^2 faces
+    as vertex index triples).  Every column and every row of cells repeats its x and z box bounds, so many centroid
+    coordinates are equal and many SAH candidates tie.
+
+    ripple = 0: planar, every box has zero y thickness (the mesh builder's case; the reference's own box test never
+    enters such a box, so through a scene every triangle would be unreachable).  ripple = h > 0: vertex (i, j) lies at
+    y = +h where i + j is even and at -h where it is odd.  Every triangle then spans y in [-h, h] exactly, so every
+    box centre is 0.5f * -h' + 0.5f * h' = 0 on y (h' the normalised h: the loaders centre y on 0 exactly), the
+    centroid extent of that axis is zero, and no box is flat."""
+    i, j = np.meshgrid(np.arange(k + 1), np.arange(k + 1), indexing="ij")
+    y = np.where((i + j) % 2 == 0, ripple, -ripple)
+    verts = np.stack([i / k - 0.5, y, j / k - 0.5], -1).reshape(-1, 3).astype(np.float32)
+    at = lambda a, b: a * (k + 1) + b                                   # noqa: E731
+    faces = []
+    for a in range(k):
+        for b in range(k):
+            faces += [(at(a, b), at(a + 1, b), at(a + 1, b + 1)), (at(a, b), at(a + 1, b + 1), at(a, b + 1))]
+    return verts, np.asarray(faces, np.uint32)
+
+
+def concentric_triangles(directory, n=20):
+    """n copies of one triangle scaled about its box centre by (k + 1) / 32, on a floor whose x range makes the
+    normalisation exact (module docstring): every raw coordinate is a small multiple of 1/256, the normalisation's
+    centre is such a number too and its scale 0.5, so every box is C -/+ h_k with exactly representable bounds and every
+    box centre 0.5f * lo + 0.5f * hi is C bit for bit, while the n boxes all differ.  The triangle has a vertex at
+    each end of its box on every axis; the vertex means differ, so the sequential mesh builder splits them as usual.
+    The flat floor is unreachable for the reference's box test and stays out of the rebuilt tree."""
+    verts = [("-" + EDGE, -0.5, -0.5), (EDGE, -0.5, -0.5), (EDGE, -0.5, 0.5), ("-" + EDGE, -0.5, 0.5)]
+    faces = [(0, 1, 2, "white"), (0, 2, 3, "white")]
+    for k in range(n):
+        s = (k + 1) / 32
+        x, y, z = s / 4, s / 8, s * 3 / 16
+        b = len(verts)
+        verts += [(-x, -y, -z), (x, y, -z), (0.0, y, z)]
+        faces.append((b, b + 1, b + 2, MATERIALS[k % len(MATERIALS)]))
+    return [write_obj(directory, "concentric_tris", verts, faces)]
+
+
+def grid(directory, k, ripple=0.03125):
+    """grid_arrays as an OBJ file (grid_<k>.obj), materials cycling."""
+    verts, faces = grid_arrays(k, ripple)
+    return [write_obj(directory, f"grid_{k}", verts,
+                      [(int(f[0]), int(f[1]), int(f[2]), MATERIALS[(t // 2) % len(MATERIALS)]) for t, f in enumerate(faces)])]
+
+
 # ---------------------------------------------------------------------------------------------- sphere worlds
 # material rows for spheres (custom_scene.mat_row layout): grey and green diffuse, fuzzy metal, glass, a light
 SPHERE_MATS = [[0.0, 0.5, 0.5, 0.5, 0, 0, 0, 0.0, 1.0], [0.0, 0.1, 0.6, 0.15, 0, 0, 0, 0.0, 1.0],
@@ -250,6 +301,12 @@ def sphere_worlds(floor_y=-0.3):
                   None, False),
         "tangent": ([((0.0, float(cy), 0.0), float(r), 2), ((-0.1, 0.1, 0.05), 0.04, 0)], None, False),
     }
+
+
+def concentric_spheres(n=20):
+    """n spheres centred exactly at the origin, n distinct radii (largest 0.2): every box is -r .. r, so every box
+    centre is exactly 0 on every axis, and the boxes all differ.  More than the GPU builder's small-node limit of 16."""
+    return [((0.0, 0.0, 0.0), float(np.float32(0.01 * (k + 1))), k % len(SPHERE_MATS)) for k in range(n)]
 
 
 SPHERES_ONLY = {"only3": random_spheres(3, seed=21, lo=0.05, hi=0.12),

@@ -7,12 +7,17 @@ permutations; boxes equal as floats (the GPU's ordered-integer min/max may pick 
 fminf keeps +0, see csrc/crt_bvh_build.hip), bit-identical everywhere else.  Meshes where the reference's
 node cap decides the tree must be refused (CRT_ERR_UNSUPPORTED) so callers fall back to the host builder.
 """
+import sys
 import time
+from pathlib import Path
 
 import numpy as np
 import pytest
 
 import crt_amd
+
+sys.path.insert(0, str(Path(__file__).resolve().parent / "helpers"))
+import synth_scenes as synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -47,14 +52,70 @@ def _both(v, idx, fm):
     return crt_amd.build_mesh_bvh(v, idx, fm), crt_amd.build_mesh_bvh(v, idx, fm, device=0)
 
 
+def _same_or_refused(v, idx, fm):
+    """_both and _assert_same; where the host restatement reports a stack overflow, or its tree shows that the
+    reference's node cap decided it (a leaf of more than ten triangles), the GPU build may instead refuse (status -5)
+    or report the same error.  A GPU refusal of a mesh the host built without either condition fails."""
+    host = host_err = None
+    try:
+        host = crt_amd.build_mesh_bvh(v, idx, fm)
+    except crt_amd.CrtError as e:
+        host_err = e
+    try:
+        gpu = crt_amd.build_mesh_bvh(v, idx, fm, device=0)
+    except crt_amd.CrtError as e:
+        if host_err is not None:
+            assert e.status == -5 or ("stack overflow" in str(host_err) and "stack overflow" in str(e)), (host_err, e)
+        else:
+            leaf = host[0]["is_leaf"] != 0
+            assert e.status == -5 and host[0]["obj_count"][leaf].max() > 30, f"refused a mesh the host builds: {e}"
+        return None
+    assert host_err is None, f"the GPU built a mesh the host refuses: {host_err}"
+    _assert_same(host, gpu)
+    return gpu
+
+
+# triangle counts at the level kernels' constants: LEVEL_SMALL 32, SCAN_ITEMS 1024, LEVEL_CHUNK 4096 (and twice that)
 @pytest.mark.parametrize("n_tri,n_vert,seed,quant", [
     (1, 3, 0, None), (10, 30, 1, None), (11, 33, 2, None), (12, 20, 3, None), (64, 100, 4, None),
     (1000, 700, 5, None), (50_000, 30_000, 6, None), (200_000, 100_000, 7, None),
     (5000, 4000, 8, 4.0), (20_000, 2000, 9, 8.0),
+    (31, 20, 20, None), (32, 21, 21, None), (33, 22, 22, None), (1023, 680, 23, None), (1024, 680, 24, None),
+    (1025, 680, 25, None), (4095, 2700, 26, None), (4096, 2700, 27, None), (4097, 2700, 28, None),
+    (8193, 5400, 29, None),
 ])
 def test_random_soups(n_tri, n_vert, seed, quant):
     host, gpu = _both(*_soup(n_tri, n_vert, seed, quant))
     _assert_same(host, gpu)
+
+
+def _grid(k, offset=(0, 0, 0)):
+    v, faces = synth.grid_arrays(k)
+    return (v + np.asarray(offset, np.float32)).astype(np.float32), faces.reshape(-1), (np.arange(len(faces)) % 7).astype(np.int32)
+
+
+@pytest.mark.parametrize("k", [8, 40])
+@pytest.mark.parametrize("offset", [(0, 0, 0), (1000, 1000, -1000)])
+def test_structured_grids(k, offset):
+    """A planar k x k quad grid with shared vertices: zero extent on y (boxes and centroids), rows and columns of equal
+    centroid coordinates, so SAH candidates tie; then the same grid at coordinates round 1000, where the cell size is
+    a few hundred ulps."""
+    v, idx, fm = _grid(k, offset)
+    assert len(v) == (k + 1) ** 2 and np.all(v[:, 1] == offset[1])
+    assert _same_or_refused(v, idx, fm) is not None, "the host builds the grids without its node cap"
+
+
+def test_signed_zero_coordinates():
+    """A soup with a third of its coordinates exactly -0.0 and a tenth +0.0: the GPU's ordered-integer min / max put -0
+    below +0 where the host's fminf / fmaxf keep the first; boxes may differ in the sign of a zero only, and no split
+    may move."""
+    rng = np.random.default_rng(12)
+    v = rng.normal(size=(300, 3)).astype(np.float32)
+    v[rng.random(v.shape) < 0.3] = -0.0
+    v[rng.random(v.shape) < 0.1] = 0.0
+    assert (np.signbit(v) & (v == 0)).sum() > 200 and (~np.signbit(v) & (v == 0)).sum() > 50
+    idx = rng.integers(0, 300, 3 * 500).astype(np.uint32)
+    assert _same_or_refused(v, idx, rng.integers(0, 7, 500).astype(np.int32)) is not None
 
 
 def test_scene_meshes(scenes):
