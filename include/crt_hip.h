@@ -834,6 +834,14 @@ int crt_selftest_scan(const int* in, int n_waves, int* out);
  *         center3 radius closest unused), out 1 = skipped / 0 = tested exactly. */
 int crt_selftest_geometry(int kind, const float* in, int n, const crt_camera_desc* cam, int width, int height,
                           uint32_t* rng, float* out);
+/* Known-answer self-test of the render kernels' material step (tests/golden/scatter_kat.npz): per record shade_rec()
+ * on a hand-made shading record, then next_ray() with no samples left (the bounce limit and the roulette of the bounce
+ * that follows).  Blocks of 64 lanes: records 64 k .. 64 k + 63 share a wave.
+ * in : 32 words per record: o3 d3 t hit | outward normal3, SHADE_* code | payload4 (crt_scene_export_shade_rows) |
+ *      throughput3 bounce | max_bounces rng6 (hit, the code, bounce and max_bounces are integers; hit 0 = a miss).
+ *      The face is dot(d, normal) < 0, as the render kernels take it.
+ * out: 20 words per record: ended | o3 d3 | throughput3 | bounce | what the path added to its pixel | rng6. */
+int crt_selftest_shade(const float* in, int n, float* out);
 /* XORWOW device self-test: init(seed, subseq[i]) then n_draw uniforms per entry. */
 int crt_selftest_rng(unsigned long long seed, const unsigned long long* subseq, int n, int n_draw,
                      uint32_t* state_out /* n*6 */, float* uniforms_out /* n*n_draw */);

@@ -624,35 +624,47 @@ static V3 sky(const Ray* r) {                                                   
     float t = 0.5f * (ud.e[1] + 1.0f);
     return vadd(smul(1.0f - t, v3(1.0f, 1.0f, 1.0f)), smul(t, v3(0.5f, 0.7f, 1.0f)));
 }
+/* rayColor's loop (CUDAKernels.h:102-145) in its two halves, so that oracle_kat_scatter below runs the very statements
+ * ray_color runs.  bounce_head: the for-condition and the roulette (:110-121); 0 = the loop is left, final_color as it
+ * stands.  bounce_tail: what follows the hit query (:123-142); 0 = the path returns *fin. */
+static int bounce_head(int b, int max_bounces, V3* acc, Rng* s) {
+    const int MIN_BOUNCES = 3;
+    const float MAX_PROB = 0.95f;
+    if (!(b < max_bounces)) return 0;
+    if (b >= MIN_BOUNCES) {
+        float p = fmaxf(acc->e[0], fmaxf(acc->e[1], acc->e[2]));
+        p = fminf(p, MAX_PROB);
+        if (curand_uniform(s) > p) return 0;
+        *acc = smul(1 / p, *acc);   /* operator/= : *this *= 1 / t */
+    }
+    return 1;
+}
+static int bounce_tail(int hit, const Hit* rec, const Mat* mats, int n_mat, Ray* cur, V3* acc, V3* fin, Rng* s) {
+    if (hit) {
+        Ray sc_ray; V3 att;
+        if (rec->mat < (uint32_t)n_mat) {
+            const Mat* m = &mats[rec->mat];
+            if (mat_scatter(m, cur, rec, &att, &sc_ray, s)) {
+                *acc = vmul(*acc, att);
+                *cur = sc_ray;
+            } else {
+                *fin = mat_emit(m);
+                return 0;
+            }
+        }
+        return 1;
+    }
+    *fin = vmul(*acc, sky(cur));
+    return 0;
+}
 static V3 ray_color(const Scene* sc, Ray cur, int max_bounces, Rng* s, Counters* cn) {    /* CUDAKernels.h:102-145 */
     V3 acc = v3(1.0f, 1.0f, 1.0f);
     V3 fin = v3(0.0f, 0.0f, 0.0f);
-    const int MIN_BOUNCES = 3;
-    const float MAX_PROB = 0.95f;
-    for (int b = 0; b < max_bounces; b++) {
+    for (int b = 0; bounce_head(b, max_bounces, &acc, s); b++) {
         Hit rec;
-        if (b >= MIN_BOUNCES) {
-            float p = fmaxf(acc.e[0], fmaxf(acc.e[1], acc.e[2]));
-            p = fminf(p, MAX_PROB);
-            if (curand_uniform(s) > p) break;
-            acc = smul(1 / p, acc);   /* operator/= : *this *= 1 / t */
-        }
         cn->rays++;
-        if (scene_hit(sc, &cur, iv(0.001f, INFINITY), &rec, cn)) {
-            Ray sc_ray; V3 att;
-            if (rec.mat < (uint32_t)sc->n_mat) {
-                const Mat* m = &sc->mats[rec.mat];
-                if (mat_scatter(m, &cur, &rec, &att, &sc_ray, s)) {
-                    acc = vmul(acc, att);
-                    cur = sc_ray;
-                } else {
-                    return mat_emit(m);
-                }
-            }
-        } else {
-            fin = vmul(acc, sky(&cur));
-            break;
-        }
+        int hit = scene_hit(sc, &cur, iv(0.001f, INFINITY), &rec, cn);
+        if (!bounce_tail(hit, &rec, sc->mats, sc->n_mat, &cur, &acc, &fin, s)) break;
     }
     return fin;
 }
@@ -1097,5 +1109,65 @@ EXPORT void oracle_kat_get_ray(const float* cam19, int w, int h, const int* xy, 
         memcpy(rng + 6 * i, &s, sizeof s);
         memcpy(out + 6 * i, r.o.e, 12);
         memcpy(out + 6 * i + 3, r.d.e, 12);
+    }
+}
+
+/* One iteration of rayColor's loop on a hand-made hit, n records of 32 words in, 40 words out.
+ *   in : o3 d3 t | outward normal3, front | material row (type, albedo3, emission3, roughness, ior; the Metal
+ *        constructor's fuzz clamp is applied here as scene_base applies it) | invalid (1: the hit's material index is
+ *        outside the scene's materials) | throughput3, bounce, max_bounces | rng6.  front, invalid, bounce and
+ *        max_bounces are integers, the rest float bits.  t < 0 is a miss; the hit point is ray_at(o, t, d) and the
+ *        shading normal front ? outward : -outward (HitInfo.cuh:12-16), both as the hit functions fill them in.
+ *   out: two stages of 20 words, ended | o3 d3 | throughput3 | bounce | add3 | rng6.  Stage A: after bounce_tail (the
+ *        scatter, the emission or the sky; add = what rayColor returns if the path ended there).  Stage B: after
+ *        bounce_head for the bounce that follows, run only if stage A did not end (ended there adds (0, 0, 0)).
+ *   draws: 2 per record, the generator's outputs used up to stage A and up to stage B. */
+static void kat_stage(uint32_t* out, int ended, const Ray* cur, V3 acc, int b, V3 add, const Rng* s) {
+    out[0] = (uint32_t)ended;
+    memcpy(out + 1, cur->o.e, 12); memcpy(out + 4, cur->d.e, 12);
+    memcpy(out + 7, acc.e, 12);
+    out[10] = (uint32_t)b;
+    memcpy(out + 11, add.e, 12);
+    memcpy(out + 14, s->v, 20); out[19] = s->d;
+}
+EXPORT void oracle_kat_scatter(const uint32_t* in, int n, uint32_t* out, int* draws) {
+    uint32_t inv = 362437u;                                  /* 362437^-1 mod 2^32 (Newton) */
+    for (int k = 0; k < 5; k++) inv *= 2u - 362437u * inv;
+    for (int i = 0; i < n; i++) {
+        const uint32_t* q = in + 32 * i;
+        float f[32];
+        memcpy(f, q, sizeof f);
+        Ray cur; cur.o = v3(f[0], f[1], f[2]); cur.d = v3(f[3], f[4], f[5]);
+        const float t = f[6];
+        const V3 outward = v3(f[7], f[8], f[9]);
+        Hit rec; memset(&rec, 0, sizeof rec);
+        rec.t = t;
+        rec.p = ray_at(&cur, t);
+        rec.front = q[10] != 0;
+        rec.n = rec.front ? outward : vneg(outward);
+        rec.mat = q[20] ? 1u : 0u;
+        Mat m; memset(&m, 0, sizeof m);
+        m.type = (int)f[11];
+        m.albedo = v3(f[12], f[13], f[14]);
+        m.emission = v3(f[15], f[16], f[17]);
+        m.roughness = f[18] < 1.f ? f[18] : 1.f;               /* Metal ctor, Material.cuh:86 */
+        m.ior = f[19];
+        V3 acc = v3(f[21], f[22], f[23]);
+        int b = (int)q[24];
+        const int max_bounces = (int)q[25];
+        Rng s; memcpy(s.v, q + 26, 20); s.d = q[31];
+        const uint32_t d0 = s.d;
+        V3 fin = v3(0.0f, 0.0f, 0.0f);
+        int go = bounce_tail(!(t < 0), &rec, &m, 1, &cur, &acc, &fin, &s);
+        if (go) b++;
+        uint32_t* o = out + 40 * i;
+        kat_stage(o, !go, &cur, acc, b, fin, &s);
+        draws[2 * i] = (int)((s.d - d0) * inv);
+        if (go) {
+            go = bounce_head(b, max_bounces, &acc, &s);
+            fin = v3(0.0f, 0.0f, 0.0f);
+        }
+        kat_stage(o + 20, !go, &cur, acc, b, fin, &s);
+        draws[2 * i + 1] = (int)((s.d - d0) * inv);
     }
 }

@@ -224,6 +224,7 @@ def _kat_lib():
         L.oracle_kat_box.argtypes = [P, i32, P]
         L.oracle_kat_sphere.argtypes = [P, i32, P]
         L.oracle_kat_get_ray.argtypes = [P, i32, i32, P, P, i32, P]
+        L.oracle_kat_scatter.argtypes = [P, i32, P, P]
         L._kat_bound = True
     return L
 
@@ -260,3 +261,16 @@ def kat_get_ray(cam19: np.ndarray, w: int, h: int, xy: np.ndarray, rng: np.ndarr
     out = np.zeros((len(xy), 6), np.float32)
     _kat_lib().oracle_kat_get_ray(_p(cam19), w, h, _p(xy), _p(rng), len(xy), _p(out))
     return out
+
+
+def kat_scatter(rec: np.ndarray):
+    """One iteration of rayColor's loop per record (oracle_kat_scatter): (n, 32) uint32 records o3 d3 t, outward
+    normal3, front, material row (type, albedo3, emission3, roughness, ior), invalid, throughput3, bounce, max_bounces,
+    rng6 -> ((n, 2, 20) uint32: per stage ended, o3 d3, throughput3, bounce, add3, rng6; (n, 2) int32: the draws used
+    up to each stage).  Stage 0 follows the scatter / emission / sky, stage 1 the next iteration's head."""
+    rec = np.ascontiguousarray(rec, np.uint32)
+    assert rec.ndim == 2 and rec.shape[1] == 32
+    out = np.zeros((len(rec), 2, 20), np.uint32)
+    draws = np.zeros((len(rec), 2), np.int32)
+    _kat_lib().oracle_kat_scatter(_p(rec), len(rec), _p(out), _p(draws))
+    return out, draws

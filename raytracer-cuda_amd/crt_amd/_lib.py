@@ -191,11 +191,11 @@ HIP_SYMBOLS = [
     "crt_renderer_denoise_iteration_ms", "crt_debug_live_allocations", "crt_renderer_last_launch_frozen",
     "crt_renderer_reproject", "crt_renderer_reset_history", "crt_renderer_denoise_history", "crt_renderer_resolve_history",
     "crt_renderer_read_history", "crt_renderer_history_device_ptr", "crt_selftest_reproject",
-    "crt_renderer_set_tail_fill", "crt_renderer_last_tail_fill",
+    "crt_renderer_set_tail_fill", "crt_renderer_last_tail_fill", "crt_selftest_shade",
 ]
 # Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, the
 # schedule self-tests, the path finish, adaptive sampling, the denoiser, the live-allocation count, then which twin of a
-# variant-8 kernel ran, then the reprojection, then variant 8's tail fill): bound when the loaded
+# variant-8 kernel ran, then the reprojection, then variant 8's tail fill, then the material self-test): bound when the loaded
 # library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
 # require() otherwise.
 OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
@@ -213,7 +213,7 @@ OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_devi
                     "crt_renderer_reproject", "crt_renderer_reset_history", "crt_renderer_denoise_history",
                     "crt_renderer_resolve_history", "crt_renderer_read_history", "crt_renderer_history_device_ptr",
                     "crt_selftest_reproject",
-                    "crt_renderer_set_tail_fill", "crt_renderer_last_tail_fill")
+                    "crt_renderer_set_tail_fill", "crt_renderer_last_tail_fill", "crt_selftest_shade")
 
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
@@ -339,6 +339,7 @@ def hip():
             "crt_renderer_read_history": ([P, P], i32),
             "crt_renderer_history_device_ptr": ([P], P),
             "crt_selftest_reproject": ([P, P, P, P, P, P, P, P], i32),
+            "crt_selftest_shade": ([P, i32, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):

@@ -1972,6 +1972,39 @@ __global__ void crt_selftest_geometry_kernel(int kind, const float* __restrict__
     }
 }
 
+// Known-answer self-test of the render kernels' material step (tests/golden/scatter_kat.npz): shade_rec() on a
+// hand-made shading record, then next_ray() with no samples left, so that only the bounce limit and the roulette of the
+// bounce that follows run.  64-lane blocks: the order of the records is the composition of the waves.
+//   in : 32 words per record: o3 d3 t hit | r0 (outward normal3, SHADE_* code) | payload4 | throughput3 bounce |
+//        max_bounces rng6 (hit, the code, bounce and max_bounces are integers)
+//   out: 20 words per record: ended | o3 d3 | throughput3 | bounce | what the path added to its pixel | rng6
+__global__ __launch_bounds__(64) void crt_selftest_shade_kernel(const float* __restrict__ in, int n,
+                                                                float* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const float* q = in + 32 * (size_t)i;
+    const uint32_t* qi = reinterpret_cast<const uint32_t*>(q);
+    PathState S = new_sample_state(rng_load(qi + 21));
+    S.o = v3(q[0], q[1], q[2]);
+    S.d = v3(q[3], q[4], q[5]);
+    S.thr = v3(q[16], q[17], q[18]);
+    S.bounce = (int)qi[19];
+    S.remaining = 0;
+    S.need_new = false;
+    const RenderParams P{};
+    shade_rec(S, P, qi[7] ? 0 : -1, q[6], make_float4(q[8], q[9], q[10], q[11]), make_float4(q[12], q[13], q[14], q[15]),
+              true, 0.f);
+    next_ray(S, CamRegs{}, 0, 0, (int)qi[20]);
+    float* o = out + 20 * (size_t)i;
+    uint32_t* oi = reinterpret_cast<uint32_t*>(o);
+    oi[0] = S.need_new ? 1u : 0u;
+    o[1] = S.o.x; o[2] = S.o.y; o[3] = S.o.z; o[4] = S.d.x; o[5] = S.d.y; o[6] = S.d.z;
+    o[7] = S.thr.x; o[8] = S.thr.y; o[9] = S.thr.z;
+    oi[10] = (uint32_t)S.bounce;
+    o[11] = S.pixel.x; o[12] = S.pixel.y; o[13] = S.pixel.z;
+    rng_store(oi + 14, S.s);
+}
+
 __global__ void crt_selftest_rng_kernel(const uint32_t* st_in, int n, int n_draw, float* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -4320,6 +4353,19 @@ int crt_selftest_geometry(int kind, const float* in, int n, const crt_camera_des
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, dout.get(), (size_t)n * out_words[kind] * 4, hipMemcpyDeviceToHost));
     if (kind == 3) HIP_TRY(hipMemcpy(rng, drng.get(), (size_t)n * 24, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+int crt_selftest_shade(const float* in, int n, float* out) {
+    if (!in || !out || n <= 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (int rc = use_device(0)) return rc;
+    DevBuf<float> din, dout;
+    HIP_TRY(din.alloc((size_t)n * 32));
+    HIP_TRY(dout.alloc((size_t)n * 20));
+    HIP_TRY(hipMemcpy(din.get(), in, (size_t)n * 32 * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(crt_selftest_shade_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, din.get(), n, dout.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dout.get(), (size_t)n * 20 * 4, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 

@@ -12,6 +12,9 @@ Fixtures (small; data only):
   primitives.json        known answers of Moller-Trumbore, AABB::hit, Sphere::hit and Camera::getRay on random
                          and edge-case inputs (zero-thickness boxes, axis-parallel rays, grazing / tangent rays,
                          det ~ 0, origins inside spheres, the radius-999 ground sphere)
+  scatter_kat.npz        known answers of the material scatter, the sky, the bounce limit and the roulette on
+                         hand-made hits with chosen draws (tests/helpers/scatter_kat.py; this one alone:
+                         python tests/golden/make_golden.py scatter_kat)
 External anchors reproduced (not generated here): the reference-run ray counts recorded in
 SURVEY.md/BASELINE.md (3,197,876 and 3,420,058 for config A) and rocRAND's XORWOW
 sequence-jump table.
@@ -172,7 +175,20 @@ def primitive_kats():
                         "rng_in": rng0.tolist(), "rng_out": rng1.tolist(), "ray_hex": hexf(rays)}}
 
 
+def scatter_kats():
+    """scatter_kat.npz: hand-made hits through one iteration of rayColor's loop (tests/helpers/scatter_kat.py)."""
+    sys.path.insert(0, str(HERE.parent / "helpers"))
+    import scatter_kat
+    fx = scatter_kat.build_fixture()
+    scatter_kat.save(HERE / "scatter_kat.npz", fx)
+    return scatter_kat.census(fx)
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["scatter_kat"]:                  # this fixture alone (the frames take minutes)
+        print(scatter_kats())
+        sys.exit(0)
+    scatter_kats()
     (HERE / "xorwow_kat.json").write_text(json.dumps(xorwow_kat(), indent=1))
     (HERE / "scene_bvh.json").write_text(json.dumps(bvh_fixture()))
     fr = frames()

@@ -143,6 +143,7 @@ def _selftests(r):
             r.h, _p(np.ones(n_pix * 3, np.float32)), _p(np.ones(n_pix * 8, np.float32)),
             C.byref(crt_amd.Renderer._denoise_options("selftest denoise", *SIGMAS, 1, False, False)),
             _p(np.zeros(n_pix * 3, np.float32))),
+        "shade": lambda: _lib.require("crt_selftest_shade")(_p(np.ones(32, np.float32)), 1, _p(np.zeros(20, np.float32))),
     }
     for kind, words in geometry_in.items():
         # kind 3 reads its two words as the pixel's integer coordinates: (0, 0)
@@ -153,7 +154,7 @@ def _selftests(r):
 
 
 SELFTESTS = ("math", "rcp", "sqrt", "unit", "scan", "geometry0", "geometry1", "geometry2", "geometry3", "geometry4", "rng",
-             "uv_div", "tile_schedule", "pixel_order", "adaptive_plan", "denoise")
+             "uv_div", "tile_schedule", "pixel_order", "adaptive_plan", "denoise", "shade")
 
 
 @pytest.fixture(scope="module")
