@@ -1714,6 +1714,28 @@ template <int VARIANT> struct KernelShape { static constexpr int waves = VARIANT
 // knob from P.  The host launches the frozen twin only where all its facts hold (render_launch_frozen), so both give
 // the same bits.  (The body is an include and not a __device__ function: called from the kernels, by reference or by
 // value, it changed the assembly of 44 or 45 of the 45 other render kernels, profiles/frozen_launch.)
+// Phase priority of the frozen twins (crt_render_body.inc, DESIGN.md §5b, profiles/phase_priority): a wave's s_setprio
+// level while it traverses (CRT_PRIO_TRAVERSAL) and while it runs a regeneration pass (CRT_PRIO_PASS); equal levels
+// emit no s_setprio at all.  Traversal over pass gains where the launch is bound by throughput (config C at occupancy
+// 7: -2.3 %; the reverse order, the control, +2.4 %) and loses where it is bound by the sample chains of its most
+// expensive tiles, whose waves' passes then wait (config B at occupancy 4: +4.6 %).  So, by kernel:
+//   MINW >= CRT_PRIO_KEEP_BELOW (7)   every wave lowers itself for its passes;
+//   below it (5, 6)                   a wave that is draining (n_live < regen_t) or renders a critical tile keeps the
+//                                     traversal level through its passes (chain-bound or not: -1.5 % and -3.7 %);
+//   MINW < CRT_PRIO_MIN_W (4)         no phase priority: the kernel a chain-bound frame is given keeps its text.
+// Compile-time only: a candidate is a library of its own (CRT_HIP_LIB).
+#ifndef CRT_PRIO_TRAVERSAL
+#define CRT_PRIO_TRAVERSAL 2
+#endif
+#ifndef CRT_PRIO_PASS
+#define CRT_PRIO_PASS 0
+#endif
+#ifndef CRT_PRIO_MIN_W
+#define CRT_PRIO_MIN_W 5
+#endif
+#ifndef CRT_PRIO_KEEP_BELOW
+#define CRT_PRIO_KEEP_BELOW 7
+#endif
 template <bool COUNT, int VARIANT, int MINW>
 __global__ __launch_bounds__(64 * KernelShape<VARIANT>::waves, MINW) void crt_render_kernel(RenderParams P) {
     constexpr bool FROZEN = VARIANT == 8 && !COUNT;

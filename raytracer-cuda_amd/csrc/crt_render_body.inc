@@ -266,6 +266,15 @@
         int lb_prev = 8;
 #endif
         constexpr bool TIME = COUNT || kProfilePass;
+        // Phase priority (frozen twins; profiles/phase_priority): traversal is short bursts of arithmetic between
+        // dependent loads, a pass is hundreds of VALU in a row behind one load, so a wave traverses at one s_setprio
+        // level and runs its passes at another.  s_setprio ignores EXEC: every call sits in wave-uniform code.
+        constexpr bool PRIO = FROZEN && MINW >= CRT_PRIO_MIN_W && CRT_PRIO_TRAVERSAL != CRT_PRIO_PASS;
+        // Below CRT_PRIO_KEEP_BELOW waves per SIMD the waves that end the launch (critical tiles, and any wave once it
+        // drains) keep the traversal level through their passes.  Both tests read regen_t, which the loop head holds:
+        // a critical tile is one whose regen_t is not the frozen twin's constant threshold (a crit_threshold set equal
+        // to it makes the tile ordinary).  Below CRT_PRIO_MIN_W the kernel has no s_setprio (crt_hip.hip).
+        if constexpr (PRIO) __builtin_amdgcn_s_setprio(CRT_PRIO_TRAVERSAL);
         for (;;) {
             const uint64_t h0 = kProfilePass ? shader_clock() : 0;
             const uint64_t parked_mask = live_mask & wave_ballot(node < 0);
@@ -304,6 +313,17 @@
             // (crt_renderer_set_wave_drain; 64 = all) shortens the wave's own drain (profiles/r04n)
             const bool drain_pass = n_live < regen_t && n_parked * 64 >= n_live * P.wave_drain;
             if (n_parked >= regen_t || n_parked == n_live || drain_pass) {
+                if constexpr (PRIO) {
+                    bool keep = false;
+                    if constexpr (MINW < CRT_PRIO_KEEP_BELOW) {
+                        // (an opaque copy: with regen_t itself the compiler hoists the tests out of the loop as lane
+                        // masks, four scalar registers that <false, 8, 7> does not have: 2 SGPR spills, 1 VGPR spill)
+                        int rt = regen_t;
+                        asm volatile("" : "+s"(rt));
+                        keep = rt != REGEN_THRESHOLD_WIDE || n_live < rt;
+                    }
+                    if (!keep) __builtin_amdgcn_s_setprio(CRT_PRIO_PASS);
+                }
                 if (COUNT || kProfilePass) cnt.passes++;
 #ifdef CRT_PROFILE_LOOPS
                 uint32_t pk1 = 0, pk2 = 0, pkr = 0;
@@ -400,6 +420,7 @@
                 // variant 8 counts the wave's rays in LDS (one VGPR less in the hot loop); (an LDS add without return
                 // instead of the read-modify-write measured +0.4 % on config C, profiles/r05e)
                 if (TILED && lane == 0) L.rays += (uint32_t)__popcll(parked_mask & live_mask);
+                if constexpr (PRIO) __builtin_amdgcn_s_setprio(CRT_PRIO_TRAVERSAL);
             }
             if (TIME) cnt.cyc_regen += shader_clock() - c0;
             if constexpr (PFV) {
