@@ -621,6 +621,85 @@ float* crt_renderer_history_device_ptr(crt_renderer* r);
 int crt_selftest_reproject(crt_renderer* r, const float* color, const float* guides, const float* prev_guides,
                            const float* prev_history, const crt_camera_desc* prev_camera,
                            const crt_reproject_options* options, float* out_history);
+/* ---- variance-guided filtering of the history (no reference counterpart; DESIGN.md "Variance-guided filter") ----
+ * The spatiotemporal variance-guided filter of Schied et al. (HPG 2017) over the reprojection's history: the first two
+ * luminance moments travel with the history, give a per-pixel variance, and that variance, itself filtered, sets the
+ * width of the filter's luminance edge-stop per pixel and per level, so a pixel whose history is 32 frames long and one
+ * that restarted a frame ago are no longer served by one sigma.  Everything is f32, uncontracted, division and sqrtf
+ * correctly rounded.  lum(c) = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z.
+ *
+ * 1. crt_renderer_reproject_moments is crt_renderer_reproject with a second ping-pong pair of rows (m1, m2) per pixel,
+ *    8 bytes each, allocated by the first call (16 bytes per pixel; a user of crt_renderer_reproject alone never pays
+ *    them) and freed with the handle.  From the same state its history rows, stats and state transitions are
+ *    crt_renderer_reproject's, bit for bit.  The frame's moments are l = lum(c), (l, l * l).  Where the pixel restarts
+ *    (step 1 of the rule above, a failed projection, or sw == 0): out_m = (l, l * l).  Else, for exactly the taps the
+ *    colour accumulation took and in its order: am = am + w * prev_m per component; hm = am / sw; out_m = hm + (new -
+ *    hm) * a per component with the colours' a.  The moments are valid after this call and not valid after a
+ *    crt_renderer_reproject or a crt_renderer_reset_history; a crt_renderer_reproject_moments on a history that is valid
+ *    while its moments are not starts the whole history over: every pixel (c, 1), (l, l * l).
+ *    crt_renderer_read_moments: W*H*2 floats, CRT_ERR_INVALID_ARGUMENT without valid moments.
+ * 2. crt_renderer_denoise_history_variance first runs the estimate kernel: per pixel with history row (r, g, b, len) it
+ *    writes c_0 = (r, g, b, v) into the filter's first colour buffer and v into a W*H buffer of the handle
+ *    (crt_renderer_read_variance; 4 bytes per pixel, allocated by the first call).
+ *      len >= min_history: v = fmaxf(0.f, m2 - m1 * m1).
+ *      Else the 7 x 7 window, dy = -3 .. 3 outer and dx inner, the centre in its place: a tap q is taken if it lies
+ *      inside the frame, key(q) == key(p) and both of its moments are finite; S1 = S1 + m1(q), S2 = S2 + m2(q), n = n +
+ *      1.f.  n == 0: v = 0.  Else M1 = S1 / n, M2 = S2 / n, v = fmaxf(0.f, M2 - M1 * M1) * (min_history / len): the
+ *      paper's boost for young pixels.
+ *    fmaxf(0, NaN) is 0, so for a len in [1, 2^24], as the reprojection writes it, v is never NaN.  It is +inf where m2
+ *    overflowed.
+ * 3. Then the filter: iterations, strides, k, the frame test, the key test, the normal and position terms, the !(X < 80.f)
+ *    skip, exp_neg and the last iteration's write into `denoised` are crt_renderer_denoise's.  The differences:
+ *      The prefiltered variance g at p: a 3 x 3 Gaussian over the v of this level at +-1 pixel whatever the stride, dy
+ *      outer, kg = hg[dy + 1] * hg[dx + 1], hg = (1/4, 1/2, 1/4); taps outside the frame or of another key are skipped;
+ *      gs = gs + kg * v(q), gw = gw + kg, g = gs / gw.
+ *      The colour term: den = sigma_luminance * sqrtf(g) + 0x1p-20f; inv_den = 1.f / den; xc = fabsf(lum(c) - lum(qc)) *
+ *      inv_den (X = (xc + xn) + xx).  sigma_luminance is not halved per level: the shrinking variance does that.
+ *      sigma_luminance == +inf: the term is off, g is not computed, the variance is still propagated.
+ *      Per tap kw = k * w (the centre: kw = k): acc.c = acc.c + kw * qc.c; av = av + (kw * kw) * qc.w; sw = sw + kw.
+ *      c_{i+1} = acc / sw per channel, v_{i+1} = av / (sw * sw).
+ *    A non-finite sample: its pixel's moments are NaN, so its v is 0 (long history) or comes from its neighbours (short);
+ *    as a tap its lum is not finite, X is NaN and it is skipped, so with the luminance term on no other pixel's colour
+ *    becomes non-finite; as a centre it stays a NaN of that pixel alone.  A v of +inf: every pixel within +-1 of it has
+ *    g = +inf, den = +inf, inv_den = 0 and xc = 0 for every finite tap: at those pixels the luminance term is as good as
+ *    off for this level and the normal and position terms alone stop edges (a tap whose luminance difference is not
+ *    finite gives 0 * inf = NaN and is skipped).  The +inf travels on in v (and becomes NaN where kw * kw underflows
+ *    to 0); a NaN g makes X NaN for every tap, so that pixel keeps its own colour through the level ((k * c) / k).  No case
+ *    makes a finite colour non-finite.
+ * The two kernels are crt_renderer_denoise's two with the variance in the colour rows' fourth lane: the direct one at
+ * every stride with CRT_DENOISE_DIRECT_ONLY and at strides >= 32, the tiled one else; the bits are the same.
+ * crt_renderer_denoise_history_variance fills the same `denoised` buffer (crt_renderer_resolve_denoised, _read_denoised,
+ * _denoised_device_ptr); its stats are crt_renderer_denoise's, and crt_renderer_denoise_iteration_ms reports the estimate
+ * kernel in out9[0].  There are no default sigmas and no default min_history (the paper uses sigma_luminance 4 and 4
+ * frames).  Before any device work and before anything is allocated, CRT_ERR_INVALID_ARGUMENT: a null handle or options,
+ * iterations outside 0..8, a sigma that is NaN or outside [2^-50, 2^50] and not +inf, a min_history that is NaN or outside
+ * [1, 2^24], flag bits other than CRT_DENOISE_DIRECT_ONLY, reserved != 0, no history, a history without valid moments;
+ * CRT_ERR_UNSUPPORTED: a pixel shard other than (0, 1).  crt_renderer_reproject_moments refuses what
+ * crt_renderer_reproject refuses.  The variance is that of the history's luminance over time: it knows nothing of the
+ * two half buffers of crt_renderer_render_adaptive, and the filter does not demodulate albedo.
+ * These entries joined ABI version 3 after its first release. */
+typedef struct crt_denoise_variance_options {
+    int32_t iterations;                 /* 1..8; 0 = 5 */
+    float sigma_luminance, sigma_normal, sigma_position;   /* each in [2^-50, 2^50], or +inf = that term off */
+    float min_history;                  /* [1, 2^24]: below it the variance is the 7 x 7 spatial estimate */
+    uint32_t flags;                     /* CRT_DENOISE_DIRECT_ONLY (bit 31): measurement switch */
+    int32_t reserved;
+} crt_denoise_variance_options;
+int crt_renderer_reproject_moments(crt_renderer* r, const crt_reproject_options* o, float scale, crt_reproject_stats* stats_out, void* stream);
+int crt_renderer_read_moments(crt_renderer* r, float* host_out);
+int crt_renderer_denoise_history_variance(crt_renderer* r, const crt_denoise_variance_options* o, crt_denoise_stats* stats_out, void* stream);
+/* W*H floats: the estimate kernel's v of the last crt_renderer_denoise_history_variance; waits for the device. */
+int crt_renderer_read_variance(crt_renderer* r, float* host_out);
+/* crt_selftest_reproject with prev_moments (W*H*2; it may be NULL only with a NULL prev_history) and out_moments (W*H*2). */
+int crt_selftest_reproject_moments(crt_renderer* r, const float* color, const float* guides, const float* prev_guides,
+                                   const float* prev_history, const float* prev_moments, const crt_camera_desc* prev_camera,
+                                   const crt_reproject_options* options, float* out_history, float* out_moments);
+/* Self-test of the estimate and the filter: uploads history (W*H*4), moments (W*H*2) and guides (W*H*8) into the
+ * renderer's buffers, runs the host function crt_renderer_denoise_history_variance calls on the null stream and reads the
+ * result into out (W*H*3) and the estimate's v into out_variance (W*H).  The uploaded history has no previous frame: a
+ * reprojection after this starts over. */
+int crt_selftest_denoise_variance(crt_renderer* r, const float* history, const float* moments, const float* guides,
+                                  const crt_denoise_variance_options* options, float* out, float* out_variance);
 /* Host only, no GPU (like crt_scene_export_identity): the per-material rows the step kernel reads, n_materials x 8
  * floats = (code, 0, 0, 0) (payload): code (int bits) 0 lambertian, 1 metal, 2 dielectric, 3 light, 4 unknown type
  * (emits 0); payload (albedo.xyz, 0), (albedo.xyz, min(roughness, 1)), (ior, 1 / ior, r0(1 / ior), r0(ior)) with

@@ -104,6 +104,13 @@ int  crth_viewer_camera(const crth_viewer* v, crt_camera_desc* out);
  * history reset.  The option values are checked by the library on the next crth_viewer_frame.
  * CRT_ERR_INVALID_ARGUMENT: a null viewer, or a viewer created with accumulate != 0 (the two modes exclude each other). */
 int  crth_viewer_set_reproject(crth_viewer* v, const crt_reproject_options* o, const crt_denoise_options* d);
+/* The variance-guided filter of the reproject mode (crt_hip.h "variance-guided filtering"): with it set, each frame's
+ * chain is render, guides, crt_renderer_reproject_moments, crt_renderer_denoise_history_variance with `d`,
+ * crt_renderer_resolve_denoised.  d == NULL switches it off again.  It needs the reproject mode and excludes that mode's
+ * plain filter: CRT_ERR_INVALID_ARGUMENT, with a message that says so, for a viewer whose reproject mode is off or was
+ * set with a filter, and for a null viewer.  A later crth_viewer_set_reproject switches it off.  The option values are
+ * checked by the library on the next crth_viewer_frame. */
+int  crth_viewer_set_denoise_variance(crth_viewer* v, const crt_denoise_variance_options* d);
 /* The viewer's renderer (read_rgba8 / read_linear / read_rng / device pointers via crt_hip.h). */
 crt_renderer* crth_viewer_renderer(crth_viewer* v);
 void crth_viewer_destroy(crth_viewer* v);

@@ -933,6 +933,136 @@ class Renderer:
                                                      C.byref(cam), C.byref(o), _p(out)), "selftest_reproject")
         return out
 
+    # ---- variance-guided filtering of the history (crt_hip.h crt_renderer_reproject_moments ff.)
+    def reproject_moments(self, position_tolerance, normal_min=float("-inf"), *, max_history, scale=None, stream=None) -> dict:
+        """reproject() that also carries the first two luminance moments of every pixel (crt_renderer_reproject_moments):
+        the same history, bit for bit, plus moments() for denoise_history_variance().  A plain reproject() or
+        reset_history() ends the moments' validity, and the next reproject_moments() then starts the whole history
+        over.  Synchronous.  Returns {"reproject_ms", "pixels_reprojected", "pixels_hit"}."""
+        o = self._reproject_options("reproject_moments", position_tolerance, normal_min, max_history)
+        try:
+            sc = float(np.float32(scale))
+        except (TypeError, ValueError):
+            raise ValueError("reproject_moments: scale must be a number") from None
+        if not sc > 0:
+            raise ValueError("reproject_moments: scale must be > 0")
+        s = _lib.ReprojectStats()
+        check(_lib.require("crt_renderer_reproject_moments")(self.h, C.byref(o), C.c_float(sc), C.byref(s), stream),
+              "reproject_moments")
+        return {"reproject_ms": float(s.reproject_ms), "pixels_reprojected": int(s.pixels_reprojected),
+                "pixels_hit": int(s.pixels_hit)}
+
+    def moments(self) -> np.ndarray:
+        """The last reproject_moments()'s moments, float32 [height, width, 2]: the history's means of the luminance
+        and of its square."""
+        out = np.zeros((self.height, self.width, 2), np.float32)
+        check(_lib.require("crt_renderer_read_moments")(self.h, _p(out)), "read_moments")
+        return out
+
+    @staticmethod
+    def _denoise_variance_options(who, sigma_luminance, sigma_normal, sigma_position, min_history, iterations, direct_only):
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations <= 8:
+            raise ValueError(f"{who}: iterations must be an int in 1..8")
+        sig = []
+        for name, v in (("sigma_luminance", sigma_luminance), ("sigma_normal", sigma_normal),
+                        ("sigma_position", sigma_position)):
+            try:
+                f = float(np.float32(v))
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: {name} must be a number") from None
+            if not (f == float("inf") or 2.0 ** -50 <= f <= 2.0 ** 50):
+                raise ValueError(f"{who}: {name} must be in [2^-50, 2^50] or +inf (that term off)")
+            sig.append(f)
+        try:
+            mh = float(np.float32(min_history))
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: min_history must be a number") from None
+        if not 1.0 <= mh <= 2.0 ** 24:
+            raise ValueError(f"{who}: min_history must be in [1, 2^24]")
+        return _lib.DenoiseVarianceOptions(int(iterations), sig[0], sig[1], sig[2], mh,
+                                           _lib.DENOISE_DIRECT_ONLY if direct_only else 0, 0)
+
+    def denoise_history_variance(self, sigma_luminance, sigma_normal, sigma_position, *, min_history, iterations: int = 5,
+                                 direct_only: bool = False, stream=None) -> dict:
+        """The variance-guided a-trous filter over the history of reproject_moments()
+        (crt_renderer_denoise_history_variance; crt_hip.h states every operation): a per-pixel variance from the
+        moments, or from the 7 x 7 neighbourhood where the history is shorter than min_history, sets the width of the
+        luminance edge-stop.  No defaults for the sigmas and min_history (the paper: sigma_luminance 4, 4 frames);
+        float("inf") switches a term off.  The result is denoised(), the estimate variance().  Synchronous.
+        Returns {"guides_ms", "filter_ms", "iterations", "pixels_hit"}."""
+        o = self._denoise_variance_options("denoise_history_variance", sigma_luminance, sigma_normal, sigma_position,
+                                           min_history, iterations, direct_only)
+        s = _lib.DenoiseStats()
+        check(_lib.require("crt_renderer_denoise_history_variance")(self.h, C.byref(o), C.byref(s), stream),
+              "denoise_history_variance")
+        return {"guides_ms": float(s.guides_ms), "filter_ms": float(s.filter_ms), "iterations": int(s.iterations),
+                "pixels_hit": int(s.pixels_hit)}
+
+    def variance(self) -> np.ndarray:
+        """The last denoise_history_variance()'s per-pixel variance estimate (before the filter), float32 [height, width]."""
+        out = np.zeros((self.height, self.width), np.float32)
+        check(_lib.require("crt_renderer_read_variance")(self.h, _p(out)), "read_variance")
+        return out
+
+    def selftest_reproject_moments(self, color, guides, prev_guides, prev_history, prev_moments, prev_camera,
+                                   position_tolerance, normal_min=float("-inf"), *, max_history):
+        """selftest_reproject() with the moments (crt_selftest_reproject_moments): prev_moments [height, width, 2] or
+        None together with prev_history.  Returns (history [height, width, 4], moments [height, width, 2])."""
+        o = self._reproject_options("selftest_reproject_moments", position_tolerance, normal_min, max_history)
+        n = self.width * self.height
+        c = np.ascontiguousarray(color, np.float32).reshape(-1)
+        g = np.ascontiguousarray(guides, np.float32).reshape(-1)
+        pg = np.ascontiguousarray(prev_guides, np.float32).reshape(-1)
+        ph = None if prev_history is None else np.ascontiguousarray(prev_history, np.float32).reshape(-1)
+        pm = None if prev_moments is None else np.ascontiguousarray(prev_moments, np.float32).reshape(-1)
+        if c.size != n * 3:
+            raise ValueError("selftest_reproject_moments: color must hold height * width * 3 floats")
+        if g.size != n * 8 or pg.size != n * 8:
+            raise ValueError("selftest_reproject_moments: guides and prev_guides must hold height * width * 8 floats")
+        if ph is not None and ph.size != n * 4:
+            raise ValueError("selftest_reproject_moments: prev_history must hold height * width * 4 floats")
+        if (ph is None) != (pm is None):
+            raise ValueError("selftest_reproject_moments: prev_moments goes with prev_history (both or neither)")
+        if pm is not None and pm.size != n * 2:
+            raise ValueError("selftest_reproject_moments: prev_moments must hold height * width * 2 floats")
+        if isinstance(prev_camera, _lib.CameraDesc):
+            cam = prev_camera
+        else:
+            f = np.ascontiguousarray(prev_camera, np.float32).reshape(-1)
+            if f.size < 12:
+                raise ValueError("selftest_reproject_moments: prev_camera must be a CameraDesc or at least 12 floats")
+            cam = _lib.CameraDesc()
+            C.memmove(C.byref(cam), f.ctypes.data, 4 * min(f.size, 19))
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        out_m = np.zeros((self.height, self.width, 2), np.float32)
+        check(_lib.require("crt_selftest_reproject_moments")(
+            self.h, _p(c), _p(g), _p(pg), None if ph is None else _p(ph), None if pm is None else _p(pm), C.byref(cam),
+            C.byref(o), _p(out), _p(out_m)), "selftest_reproject_moments")
+        return out, out_m
+
+    def selftest_denoise_variance(self, history, moments, guides, sigma_luminance, sigma_normal, sigma_position, *,
+                                  min_history, iterations: int = 5, direct_only: bool = False):
+        """The estimate and the filter on caller-supplied buffers (crt_selftest_denoise_variance): history [height,
+        width, 4] (r, g, b, len), moments [height, width, 2], guides [height, width, 8].  Returns (the filtered frame
+        [height, width, 3], the variance estimate [height, width])."""
+        o = self._denoise_variance_options("selftest_denoise_variance", sigma_luminance, sigma_normal, sigma_position,
+                                           min_history, iterations, direct_only)
+        n = self.width * self.height
+        h = np.ascontiguousarray(history, np.float32).reshape(-1)
+        m = np.ascontiguousarray(moments, np.float32).reshape(-1)
+        g = np.ascontiguousarray(guides, np.float32).reshape(-1)
+        if h.size != n * 4:
+            raise ValueError("selftest_denoise_variance: history must hold height * width * 4 floats")
+        if m.size != n * 2:
+            raise ValueError("selftest_denoise_variance: moments must hold height * width * 2 floats")
+        if g.size != n * 8:
+            raise ValueError("selftest_denoise_variance: guides must hold height * width * 8 floats")
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        out_v = np.zeros((self.height, self.width), np.float32)
+        check(_lib.require("crt_selftest_denoise_variance")(self.h, _p(h), _p(m), _p(g), C.byref(o), _p(out), _p(out_v)),
+              "selftest_denoise_variance")
+        return out, out_v
+
     def set_leaf_carry(self, lanes: int, max_pairs: int):
         """Variant 8's leaf-pair carry: measured and removed in round 5; the library reports
         CRT_ERR_UNSUPPORTED, so this raises CrtError (profiles/r04c/leaf_carry.patch restores the kernels)."""
@@ -1092,6 +1222,19 @@ class Viewer:
             d = Renderer._denoise_options("set_reproject", sc, sn, sx, denoise_iterations, False, False)
         check_host(_lib.host().crth_viewer_set_reproject(self.h, C.byref(o), None if d is None else C.byref(d)),
                    "crth_viewer_set_reproject")
+
+    def set_denoise_variance(self, sigma_luminance=None, sigma_normal=None, sigma_position=None, *, min_history=None,
+                             iterations: int = 5):
+        """The variance-guided filter of the reproject mode (crth_viewer_set_denoise_variance): each frame's chain
+        becomes render, guides, Renderer.reproject_moments, Renderer.denoise_history_variance with these options,
+        resolve_denoised.  It needs set_reproject() before it, without that call's denoise.  sigma_luminance None
+        switches it off."""
+        if sigma_luminance is None:
+            check_host(_lib.host().crth_viewer_set_denoise_variance(self.h, None), "crth_viewer_set_denoise_variance")
+            return
+        d = Renderer._denoise_variance_options("set_denoise_variance", sigma_luminance, sigma_normal, sigma_position,
+                                               min_history, iterations, False)
+        check_host(_lib.host().crth_viewer_set_denoise_variance(self.h, C.byref(d)), "crth_viewer_set_denoise_variance")
 
     def camera(self) -> CameraDesc:
         d = CameraDesc()

@@ -156,6 +156,11 @@ class ReprojectStats(C.Structure):    # crt_hip.h crt_reproject_stats
     _fields_ = [("reproject_ms", C.c_float), ("pixels_reprojected", C.c_uint32), ("pixels_hit", C.c_uint32)]
 
 
+class DenoiseVarianceOptions(C.Structure):   # crt_hip.h crt_denoise_variance_options
+    _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float), ("min_history", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
 DENOISE_TILE_SCALE = 1               # crt_denoise_options.flags
 DENOISE_DIRECT_ONLY = 0x80000000     # measurement switch: every iteration through the direct kernel
 
@@ -192,10 +197,12 @@ HIP_SYMBOLS = [
     "crt_renderer_reproject", "crt_renderer_reset_history", "crt_renderer_denoise_history", "crt_renderer_resolve_history",
     "crt_renderer_read_history", "crt_renderer_history_device_ptr", "crt_selftest_reproject",
     "crt_renderer_set_tail_fill", "crt_renderer_last_tail_fill", "crt_selftest_shade",
+    "crt_renderer_reproject_moments", "crt_renderer_read_moments", "crt_renderer_denoise_history_variance",
+    "crt_renderer_read_variance", "crt_selftest_reproject_moments", "crt_selftest_denoise_variance",
 ]
 # Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, the
 # schedule self-tests, the path finish, adaptive sampling, the denoiser, the live-allocation count, then which twin of a
-# variant-8 kernel ran, then the reprojection, then variant 8's tail fill, then the material self-test): bound when the loaded
+# variant-8 kernel ran, then the reprojection, then variant 8's tail fill, then the material self-test, then the variance-guided filter): bound when the loaded
 # library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
 # require() otherwise.
 OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
@@ -213,14 +220,17 @@ OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_devi
                     "crt_renderer_reproject", "crt_renderer_reset_history", "crt_renderer_denoise_history",
                     "crt_renderer_resolve_history", "crt_renderer_read_history", "crt_renderer_history_device_ptr",
                     "crt_selftest_reproject",
-                    "crt_renderer_set_tail_fill", "crt_renderer_last_tail_fill", "crt_selftest_shade")
+                    "crt_renderer_set_tail_fill", "crt_renderer_last_tail_fill", "crt_selftest_shade",
+                    "crt_renderer_reproject_moments", "crt_renderer_read_moments",
+                    "crt_renderer_denoise_history_variance", "crt_renderer_read_variance",
+                    "crt_selftest_reproject_moments", "crt_selftest_denoise_variance")
 
 HOST_SYMBOLS = [
     "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
     "crth_scene_loader_arrays", "crth_camera", "crth_last_error", "crth_encode_image", "crth_write_image",
     "crth_build_mesh_bvh", "crth_camera_create", "crth_camera_update", "crth_camera_get", "crth_camera_destroy",
     "crth_viewer_create", "crth_viewer_frame", "crth_viewer_camera", "crth_viewer_renderer", "crth_viewer_destroy",
-    "crth_viewer_set_reproject",
+    "crth_viewer_set_reproject", "crth_viewer_set_denoise_variance",
 ]
 
 _hip = None
@@ -340,6 +350,12 @@ def hip():
             "crt_renderer_history_device_ptr": ([P], P),
             "crt_selftest_reproject": ([P, P, P, P, P, P, P, P], i32),
             "crt_selftest_shade": ([P, i32, P], i32),
+            "crt_renderer_reproject_moments": ([P, P, f32, P, P], i32),
+            "crt_renderer_read_moments": ([P, P], i32),
+            "crt_renderer_denoise_history_variance": ([P, P, P, P], i32),
+            "crt_renderer_read_variance": ([P, P], i32),
+            "crt_selftest_reproject_moments": ([P, P, P, P, P, P, P, P, P, P], i32),
+            "crt_selftest_denoise_variance": ([P, P, P, P, P, P, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):
@@ -384,6 +400,7 @@ def host():
             "crth_viewer_frame": ([P, f32, P, P], i32), "crth_viewer_camera": ([P, P], i32),
             "crth_viewer_renderer": ([P], P), "crth_viewer_destroy": ([P], None),
             "crth_viewer_set_reproject": ([P, P, P], i32),
+            "crth_viewer_set_denoise_variance": ([P, P], i32),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):

@@ -2873,6 +2873,17 @@ struct ReprojectState {
     DevEvent e0, e1;
 };
 
+// The renderer's variance state (crt_variance.h).  Bytes per pixel: two moment buffers of 8-byte rows 16, allocated by
+// the first crt_renderer_reproject_moments, + the variance 4, allocated by the first crt_renderer_denoise_history_variance.
+struct VarianceState {
+    DevBuf<float2> mom[2];          // 1 row per pixel: (m1, m2) of the luminance; [mi] belongs to ReprojectState::hist[hi]
+    DevBuf<float> variance;         // W*H: the estimate kernel's v (crt_renderer_read_variance)
+    int mi = 0;
+    bool moments_valid = false;     // mom[mi] and hist[hi] describe the same frames (a plain reprojection or a reset ends it)
+    bool have_variance = false;
+    bool lds_raised = false;        // the variance tiled kernel's dynamic LDS limit was raised for this device
+};
+
 struct crt_scene {
     int device = 0;
     DevBuf<float4> d_nodes, d_prims, d_mats;
@@ -2968,6 +2979,7 @@ struct crt_renderer {
     std::unique_ptr<AdaptiveState> adaptive;        // crt_renderer_render_adaptive: per-tile state of the handle, allocated on first use (crt_adaptive.h)
     std::unique_ptr<DenoiseState> denoise;          // crt_renderer_compute_guides / crt_renderer_denoise: guides and colour buffers of the handle, allocated on first use (crt_denoise.h)
     std::unique_ptr<ReprojectState> reproject;      // crt_renderer_reproject: history buffers of the handle, allocated on first use (crt_reproject.h)
+    std::unique_ptr<VarianceState> variance;        // crt_renderer_reproject_moments / crt_renderer_denoise_history_variance: moments and variance of the handle, allocated on first use (crt_variance.h)
 };
 
 namespace {
@@ -4515,3 +4527,4 @@ int crt_selftest_schedule_buffer(crt_renderer* R, int which, uint32_t* out, int6
 #include "crt_adaptive.h"
 #include "crt_denoise.h"
 #include "crt_reproject.h"
+#include "crt_variance.h"

@@ -167,10 +167,10 @@ int reproject_check_options(const crt_reproject_options* o, const char* who) {
     return CRT_OK;
 }
 
-// One reprojection on `st`: the launch, then the current frame becomes the previous one.  Options, guides and state
-// were checked.
-int reproject_run(crt_renderer* R, DenoiseState* N, ReprojectState* S, const crt_reproject_options* o, float scale,
-                  hipStream_t st) {
+// The kernel's parameters for one call (crt_reproject_kernel and, with the moments beside them,
+// crt_reproject_moments_kernel of crt_variance.h).  Options, guides and state were checked.
+ReprojectParams reproject_params(crt_renderer* R, DenoiseState* N, ReprojectState* S, const crt_reproject_options* o,
+                                 float scale) {
     const float inf = __builtin_inff();
     ReprojectParams P{};
     P.sum = R->d_sum;
@@ -199,16 +199,43 @@ int reproject_run(crt_renderer* R, DenoiseState* N, ReprojectState* S, const crt
     P.tol2 = P.on_x ? o->position_tolerance * o->position_tolerance : 0.f;
     P.normal_min = o->normal_min;
     P.max_history = o->max_history;
-    HIP_TRY(hipEventRecord(S->e0.get(), st));
-    hipLaunchKernelGGL(crt_reproject_kernel, dim3(P.blocks_x, (R->height + REPROJECT_BY - 1) / REPROJECT_BY),
-                       dim3(REPROJECT_BX, REPROJECT_BY), 0, st, P);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S->e1.get(), st));
+    return P;
+}
+
+// After a call's launch: the current frame becomes the previous one.
+void reproject_advance(DenoiseState* N, ReprojectState* S) {
     S->hi ^= 1;
     S->prev_gi = N->gi;
     S->prev_cam = N->guide_cam;
     N->keep = true;
     S->valid = S->have_history = true;
+}
+
+// One reprojection on `st`: the launch, then the current frame becomes the previous one.  Options, guides and state
+// were checked.
+int reproject_run(crt_renderer* R, DenoiseState* N, ReprojectState* S, const crt_reproject_options* o, float scale,
+                  hipStream_t st) {
+    const ReprojectParams P = reproject_params(R, N, S, o, scale);
+    HIP_TRY(hipEventRecord(S->e0.get(), st));
+    hipLaunchKernelGGL(crt_reproject_kernel, dim3(P.blocks_x, (R->height + REPROJECT_BY - 1) / REPROJECT_BY),
+                       dim3(REPROJECT_BX, REPROJECT_BY), 0, st, P);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S->e1.get(), st));
+    reproject_advance(N, S);
+    return CRT_OK;
+}
+
+// The stats of the reprojection just enqueued: waits for its launch.
+int reproject_stats(crt_renderer* R, DenoiseState* N, ReprojectState* S, crt_reproject_stats* out) {
+    crt_reproject_stats s{};
+    HIP_TRY(hipEventSynchronize(S->e1.get()));
+    HIP_TRY(hipEventElapsedTime(&s.reproject_ms, S->e0.get(), S->e1.get()));
+    std::vector<uint32_t> w((size_t)reproject_waves(R));
+    HIP_TRY(hipMemcpy(w.data(), S->wave_taken.get(), w.size() * 4, hipMemcpyDeviceToHost));
+    for (uint32_t c : w) s.pixels_reprojected += c;
+    if (N->counted)
+        if (int rc = denoise_pixels_hit(R, N, &s.pixels_hit)) return rc;
+    *out = s;
     return CRT_OK;
 }
 
@@ -228,24 +255,15 @@ int crt_renderer_reproject(crt_renderer* R, const crt_reproject_options* o, floa
     DenoiseState* N = R->denoise.get();
     ReprojectState* S = nullptr;
     if (int rc = reproject_state(R, &S)) return rc;
+    if (R->variance) R->variance->moments_valid = false;     // this history has no moments (crt_variance.h)
     if (int rc = reproject_run(R, N, S, o, scale, (hipStream_t)stream)) return rc;
-    if (stats_out) {
-        crt_reproject_stats s{};
-        HIP_TRY(hipEventSynchronize(S->e1.get()));
-        HIP_TRY(hipEventElapsedTime(&s.reproject_ms, S->e0.get(), S->e1.get()));
-        std::vector<uint32_t> w((size_t)reproject_waves(R));
-        HIP_TRY(hipMemcpy(w.data(), S->wave_taken.get(), w.size() * 4, hipMemcpyDeviceToHost));
-        for (uint32_t c : w) s.pixels_reprojected += c;
-        if (N->counted)
-            if (int rc = denoise_pixels_hit(R, N, &s.pixels_hit)) return rc;
-        *stats_out = s;
-    }
-    return CRT_OK;
+    return stats_out ? reproject_stats(R, N, S, stats_out) : CRT_OK;
 }
 
 int crt_renderer_reset_history(crt_renderer* R) {
     if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "reset history: null renderer");
     if (R->reproject) R->reproject->valid = false;
+    if (R->variance) R->variance->moments_valid = false;
     return CRT_OK;
 }
 

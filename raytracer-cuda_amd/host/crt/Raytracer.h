@@ -16,7 +16,9 @@
 // The reproject mode (setReproject) is a second addition, for the frames `accumulate` cannot help: after each frame's
 // render it computes the first-hit guides, blends the frame into the history that follows the camera
 // (crt_renderer_reproject with the frame's pixel_sample_scale), optionally filters the history
-// (crt_renderer_denoise_history) and resolves that, so the RGBA8 buffer holds the reconstructed frame.
+// (crt_renderer_denoise_history) and resolves that, so the RGBA8 buffer holds the reconstructed frame.  With
+// setDenoiseVariance the blend also carries the luminance moments (crt_renderer_reproject_moments) and the filter is
+// the variance-guided one (crt_renderer_denoise_history_variance).
 #pragma once
 #include <chrono>
 #include <string>
@@ -124,9 +126,22 @@ public:
         if (o && m_Options.accumulate) throw std::runtime_error("the reproject mode and accumulate exclude each other");
         m_Reproject = o != nullptr;
         m_Filter = o && d;
+        m_Variance = false;
         if (o) m_ReprojectOptions = *o;
         if (m_Filter) m_FilterOptions = *d;
         if (!o) CRT_CHECK(crt_renderer_reset_history(m_Renderer.handle()));
+    }
+
+    // The variance-guided filter of the reproject mode (crt_renderer_reproject_moments, then
+    // crt_renderer_denoise_history_variance): d == nullptr switches it off.  It filters the history, so it needs the
+    // reproject mode, and it takes the place of that mode's plain filter, so the two exclude each other.
+    void setDenoiseVariance(const crt_denoise_variance_options* d) {
+        if (d && !m_Reproject)
+            throw std::runtime_error("the variance-guided filter needs the reproject mode (-reproject, setReproject)");
+        if (d && m_Filter)
+            throw std::runtime_error("the variance-guided filter and the reproject mode's plain filter (-denoise) exclude each other");
+        m_Variance = d != nullptr;
+        if (d) m_VarianceOptions = *d;
     }
 
     const Camera& camera() const { return m_Camera; }
@@ -140,17 +155,21 @@ private:
     void reconstruct(crt_renderer* r, FrameInfo& fi) {
         const auto g0 = std::chrono::steady_clock::now();
         CRT_CHECK(crt_renderer_compute_guides(r, m_SceneManager.getBVHNodes(), nullptr, nullptr));
-        if (!m_Filter) {
+        if (!m_Filter && !m_Variance) {
             CRT_CHECK(crt_renderer_synchronize(r, nullptr));
             fi.guidesMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - g0).count();
         }
         crt_reproject_stats rs{};
-        CRT_CHECK(crt_renderer_reproject(r, &m_ReprojectOptions, m_Camera.toDesc().pixel_sample_scale, &rs, nullptr));
+        if (m_Variance)
+            CRT_CHECK(crt_renderer_reproject_moments(r, &m_ReprojectOptions, m_Camera.toDesc().pixel_sample_scale, &rs, nullptr));
+        else
+            CRT_CHECK(crt_renderer_reproject(r, &m_ReprojectOptions, m_Camera.toDesc().pixel_sample_scale, &rs, nullptr));
         fi.reprojectMs = rs.reproject_ms;
         fi.pixelsReprojected = rs.pixels_reprojected;
-        if (m_Filter) {
+        if (m_Filter || m_Variance) {
             crt_denoise_stats ds{};
-            CRT_CHECK(crt_renderer_denoise_history(r, &m_FilterOptions, &ds, nullptr));
+            if (m_Variance) CRT_CHECK(crt_renderer_denoise_history_variance(r, &m_VarianceOptions, &ds, nullptr));
+            else CRT_CHECK(crt_renderer_denoise_history(r, &m_FilterOptions, &ds, nullptr));
             fi.guidesMs = ds.guides_ms;
             fi.filterMs = ds.filter_ms;
             CRT_CHECK(crt_renderer_resolve_denoised(r, nullptr));
@@ -181,9 +200,10 @@ private:
     HIPRenderer m_Renderer;
     long long m_Frame = 0;
     int m_Accumulated = 0;
-    bool m_Reproject = false, m_Filter = false;
+    bool m_Reproject = false, m_Filter = false, m_Variance = false;
     crt_reproject_options m_ReprojectOptions{};
     crt_denoise_options m_FilterOptions{};
+    crt_denoise_variance_options m_VarianceOptions{};
 };
 
 }  // namespace CRT

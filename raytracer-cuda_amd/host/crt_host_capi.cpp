@@ -266,6 +266,17 @@ int crth_viewer_set_reproject(crth_viewer* v, const crt_reproject_options* o, co
     }
 }
 
+int crth_viewer_set_denoise_variance(crth_viewer* v, const crt_denoise_variance_options* d) {
+    if (!v) { g_err = "null viewer"; return CRT_ERR_INVALID_ARGUMENT; }
+    try {
+        v->rt->setDenoiseVariance(d);
+        return CRT_OK;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return CRT_ERR_INVALID_ARGUMENT;
+    }
+}
+
 crt_renderer* crth_viewer_renderer(crth_viewer* v) { return v ? v->rt->renderer().handle() : nullptr; }
 
 void crth_viewer_destroy(crth_viewer* v) { delete v; }

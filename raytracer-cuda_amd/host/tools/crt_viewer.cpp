@@ -4,13 +4,17 @@
 //
 //   crt_viewer [-w W] [-h H] [-frames N] [-script still|walk|orbit|hq] [-bvh reference|rebuilt]
 //              [-accumulate] [-no-temporal] [-drain LANES] [-seed S] [-o last.png]
-//              [-reproject TOL:NMIN:MAXH [-denoise SC:SN:SX [-denoise-iters N]]] model.obj...
+//              [-reproject TOL:NMIN:MAXH [-denoise SC:SN:SX | -denoise-variance SL:SN:SX:MINH] [-denoise-iters N]]
+//              model.obj...
 //
 // Scripts: still = no input (1 spp per frame, RNG continues); walk = W held; orbit = right mouse dragged
 // in a circle; hq = F pressed once, then still (2000 spp frames).
 // -reproject TOL:NMIN:MAXH: the reproject mode (Raytracer::setReproject) with the position tolerance, the least normal
 // cosine and the history cap given (`inf` / `-inf` switch a term off; there are no defaults); -denoise SC:SN:SX filters
 // the history before it is shown, -denoise-iters iterations (default 5).  Not together with -accumulate.
+// -denoise-variance SL:SN:SX:MINH: the variance-guided filter instead (Raytracer::setDenoiseVariance): the luminance,
+// normal and position sigmas and the history length below which the variance is estimated spatially.  It needs
+// -reproject and excludes -denoise.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -33,13 +37,25 @@ static bool parseTriple(const char* text, float out[3]) {
     return true;
 }
 
+// "A:B:C:D" -> four numbers.
+static bool parseQuad(const char* text, float out[4]) {
+    const char* p = text;
+    for (int k = 0; k < 4; ++k) {
+        char* end = nullptr;
+        out[k] = std::strtof(p, &end);
+        if (end == p || *end != (k < 3 ? ':' : '\0')) return false;
+        p = end + 1;
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     try {
         int W = 2560, H = -1;
         long long frames = 240;
         std::string script = "still", out;
-        bool reproject = false, denoise = false, denoiseItersGiven = false;
-        float rp[3] = {0.f, 0.f, 0.f}, sigma[3] = {0.f, 0.f, 0.f};
+        bool reproject = false, denoise = false, denoiseItersGiven = false, variance = false;
+        float rp[3] = {0.f, 0.f, 0.f}, sigma[3] = {0.f, 0.f, 0.f}, vs[4] = {0.f, 0.f, 0.f, 0.f};
         int denoiseIters = 5;
         CRT::RaytracerOptions opts;
         opts.hasPose = true;                          // the bench pose that frames the Cornell box
@@ -67,6 +83,14 @@ int main(int argc, char** argv) {
                     return 2;
                 }
             }
+            else if (a == "-denoise-variance") {
+                need(1);
+                variance = true;
+                if (!parseQuad(argv[++i], vs)) {
+                    std::fprintf(stderr, "-denoise-variance takes SL:SN:SX:MINH (numbers or inf)\n");
+                    return 2;
+                }
+            }
             else if (a == "-denoise-iters") { need(1); denoiseIters = std::atoi(argv[++i]); denoiseItersGiven = true; }
             else if (a == "-bvh") {
                 need(1);
@@ -85,7 +109,15 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "-denoise filters the history: it needs -reproject\n");
             return 2;
         }
-        if (denoiseItersGiven && !denoise) {
+        if (variance && !reproject) {
+            std::fprintf(stderr, "-denoise-variance filters the history: it needs -reproject\n");
+            return 2;
+        }
+        if (variance && denoise) {
+            std::fprintf(stderr, "-denoise-variance and -denoise exclude each other\n");
+            return 2;
+        }
+        if (denoiseItersGiven && !denoise && !variance) {
             std::fprintf(stderr, "-denoise-iters counts the filter's iterations: it needs -denoise\n");
             return 2;
         }
@@ -99,6 +131,8 @@ int main(int argc, char** argv) {
             const crt_reproject_options ro{rp[0], rp[1], rp[2], 0u, 0};
             const crt_denoise_options dn{denoiseIters, sigma[0], sigma[1], sigma[2], 0u, 0};
             rt.setReproject(&ro, denoise ? &dn : nullptr);
+            const crt_denoise_variance_options dv{denoiseIters, vs[0], vs[1], vs[2], vs[3], 0u, 0};
+            if (variance) rt.setDenoiseVariance(&dv);
         }
         const float dt = 1.0f / 60.0f;
         auto input = [&](long long f, float* dtOut) {
@@ -148,6 +182,7 @@ int main(int argc, char** argv) {
                         "\"filter_ms_mean\": %.3f, \"pixels_reprojected_last\": %u",
                         rp[0], rp[1], rp[2], n ? guidesMs / n : 0.0, n ? reprojectMs / n : 0.0, n ? filterMs / n : 0.0,
                         last.pixelsReprojected);
+        if (variance) std::printf(", \"denoise_variance\": \"%g:%g:%g:%g\"", vs[0], vs[1], vs[2], vs[3]);
         std::printf("}\n");
         return EXIT_SUCCESS;
     } catch (const std::exception& e) {
