@@ -754,11 +754,12 @@ class Renderer:
         return out
 
     @staticmethod
-    def _denoise_options(who, sigma_color, sigma_normal, sigma_position, iterations, tile_scale, direct_only):
+    def _filter_sigmas(who, first, sigmas, iterations):
+        """Either a-trous filter's iterations and three sigmas (`first` names the colour term's), checked: the floats."""
         if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations <= 8:
             raise ValueError(f"{who}: iterations must be an int in 1..8")
         sig = []
-        for name, v in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_position", sigma_position)):
+        for name, v in zip((first, "sigma_normal", "sigma_position"), sigmas):
             try:
                 f = float(np.float32(v))
             except (TypeError, ValueError):
@@ -766,8 +767,35 @@ class Renderer:
             if not (f == float("inf") or 2.0 ** -50 <= f <= 2.0 ** 50):
                 raise ValueError(f"{who}: {name} must be in [2^-50, 2^50] or +inf (that term off)")
             sig.append(f)
+        return sig
+
+    @staticmethod
+    def _denoise_options(who, sigma_color, sigma_normal, sigma_position, iterations, tile_scale, direct_only):
+        sig = Renderer._filter_sigmas(who, "sigma_color", (sigma_color, sigma_normal, sigma_position), iterations)
         flags = (_lib.DENOISE_TILE_SCALE if tile_scale else 0) | (_lib.DENOISE_DIRECT_ONLY if direct_only else 0)
-        return _lib.DenoiseOptions(int(iterations), sig[0], sig[1], sig[2], flags, 0)
+        return _lib.DenoiseOptions(int(iterations), *sig, flags, 0)
+
+    @staticmethod
+    def _positive_scale(who, scale, hint=""):
+        try:
+            sc = float(np.float32(scale))
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: scale must be a number{hint}") from None
+        if not sc > 0:
+            raise ValueError(f"{who}: scale must be > 0")
+        return sc
+
+    def _flat(self, who, name, a, k):
+        """`a` as a flat float32 array of height * width * k floats."""
+        f = np.ascontiguousarray(a, np.float32).reshape(-1)
+        if f.size != self.width * self.height * k:
+            raise ValueError(f"{who}: {name} must hold height * width * {k} floats")
+        return f
+
+    @staticmethod
+    def _denoise_stats(s) -> dict:
+        return {"guides_ms": float(s.guides_ms), "filter_ms": float(s.filter_ms), "iterations": int(s.iterations),
+                "pixels_hit": int(s.pixels_hit)}
 
     def denoise(self, sigma_color, sigma_normal, sigma_position, iterations: int = 5, scale=None, tile_scale: bool = False,
                 direct_only: bool = False, stream=None) -> dict:
@@ -784,16 +812,10 @@ class Renderer:
                 raise ValueError("denoise: scale and tile_scale exclude each other")
             sc = 1.0
         else:
-            try:
-                sc = float(np.float32(scale))
-            except (TypeError, ValueError):
-                raise ValueError("denoise: scale must be a number (or tile_scale=True)") from None
-            if not sc > 0:
-                raise ValueError("denoise: scale must be > 0")
+            sc = self._positive_scale("denoise", scale, " (or tile_scale=True)")
         s = _lib.DenoiseStats()
         check(_lib.require("crt_renderer_denoise")(self.h, C.byref(o), C.c_float(sc), C.byref(s), stream), "denoise")
-        return {"guides_ms": float(s.guides_ms), "filter_ms": float(s.filter_ms), "iterations": int(s.iterations),
-                "pixels_hit": int(s.pixels_hit)}
+        return self._denoise_stats(s)
 
     def denoise_iteration_ms(self) -> dict:
         """The last denoise()'s launches, timed one by one (crt_renderer_denoise_iteration_ms): {"input_ms": the kernel
@@ -824,12 +846,8 @@ class Renderer:
         the sums), guides [height, width, 8] float32 (key as int bits).  Returns the filtered frame."""
         o = self._denoise_options("selftest_denoise", sigma_color, sigma_normal, sigma_position, iterations, False,
                                   direct_only)
-        c = np.ascontiguousarray(color, np.float32).reshape(-1)
-        g = np.ascontiguousarray(guides, np.float32).reshape(-1)
-        if c.size != self.width * self.height * 3:
-            raise ValueError("selftest_denoise: color must hold height * width * 3 floats")
-        if g.size != self.width * self.height * 8:
-            raise ValueError("selftest_denoise: guides must hold height * width * 8 floats")
+        c = self._flat("selftest_denoise", "color", color, 3)
+        g = self._flat("selftest_denoise", "guides", guides, 8)
         out = np.zeros((self.height, self.width, 3), np.float32)
         check(_lib.require("crt_selftest_denoise")(self.h, _p(c), _p(g), C.byref(o), _p(out)), "selftest_denoise")
         return out
@@ -852,6 +870,15 @@ class Renderer:
             raise ValueError(f"{who}: max_history must be in [1, 2^24]")
         return _lib.ReprojectOptions(tol, nmin, cap, 0, 0)
 
+    def _reproject(self, name, position_tolerance, normal_min, max_history, scale, stream) -> dict:
+        """reproject() and reproject_moments(): `name` is the method's and, after crt_renderer_, the entry's."""
+        o = self._reproject_options(name, position_tolerance, normal_min, max_history)
+        sc = self._positive_scale(name, scale)
+        s = _lib.ReprojectStats()
+        check(_lib.require("crt_renderer_" + name)(self.h, C.byref(o), C.c_float(sc), C.byref(s), stream), name)
+        return {"reproject_ms": float(s.reproject_ms), "pixels_reprojected": int(s.pixels_reprojected),
+                "pixels_hit": int(s.pixels_hit)}
+
     def reproject(self, position_tolerance, normal_min=float("-inf"), *, max_history, scale=None, stream=None) -> dict:
         """Blend scale * the sums into the history that follows the camera (crt_renderer_reproject; crt_hip.h states
         every operation), guided by compute_guides' buffers of this frame and of the previous call's.  No defaults for
@@ -860,17 +887,7 @@ class Renderer:
         switch the position / normal term off.  scale: what resolve() would take.  The result is history(); the sums,
         the RNG state, rgba8(), guides() and denoised() are untouched.  Synchronous.
         Returns {"reproject_ms", "pixels_reprojected", "pixels_hit"}."""
-        o = self._reproject_options("reproject", position_tolerance, normal_min, max_history)
-        try:
-            sc = float(np.float32(scale))
-        except (TypeError, ValueError):
-            raise ValueError("reproject: scale must be a number") from None
-        if not sc > 0:
-            raise ValueError("reproject: scale must be > 0")
-        s = _lib.ReprojectStats()
-        check(_lib.require("crt_renderer_reproject")(self.h, C.byref(o), C.c_float(sc), C.byref(s), stream), "reproject")
-        return {"reproject_ms": float(s.reproject_ms), "pixels_reprojected": int(s.pixels_reprojected),
-                "pixels_hit": int(s.pixels_hit)}
+        return self._reproject("reproject", position_tolerance, normal_min, max_history, scale, stream)
 
     def history(self) -> np.ndarray:
         """The last reproject()'s history, float32 [height, width, 4]: linear r, g, b and the length."""
@@ -899,8 +916,34 @@ class Renderer:
         o = self._denoise_options("denoise_history", sigma_color, sigma_normal, sigma_position, iterations, False, direct_only)
         s = _lib.DenoiseStats()
         check(_lib.require("crt_renderer_denoise_history")(self.h, C.byref(o), C.byref(s), stream), "denoise_history")
-        return {"guides_ms": float(s.guides_ms), "filter_ms": float(s.filter_ms), "iterations": int(s.iterations),
-                "pixels_hit": int(s.pixels_hit)}
+        return self._denoise_stats(s)
+
+    def _selftest_reproject(self, name, color, guides, prev_guides, prev_history, prev_moments, prev_camera,
+                            position_tolerance, normal_min, max_history):
+        """selftest_reproject() and, with a name that ends in _moments, selftest_reproject_moments()."""
+        moments = name.endswith("_moments")
+        o = self._reproject_options(name, position_tolerance, normal_min, max_history)
+        c = self._flat(name, "color", color, 3)
+        g = self._flat(name, "guides and prev_guides", guides, 8)
+        pg = self._flat(name, "guides and prev_guides", prev_guides, 8)
+        ph = None if prev_history is None else self._flat(name, "prev_history", prev_history, 4)
+        if moments and (prev_history is None) != (prev_moments is None):
+            raise ValueError(f"{name}: prev_moments goes with prev_history (both or neither)")
+        pm = None if prev_moments is None else self._flat(name, "prev_moments", prev_moments, 2)
+        if isinstance(prev_camera, _lib.CameraDesc):
+            cam = prev_camera
+        else:
+            f = np.ascontiguousarray(prev_camera, np.float32).reshape(-1)
+            if f.size < 12:
+                raise ValueError(f"{name}: prev_camera must be a CameraDesc or at least 12 floats")
+            cam = _lib.CameraDesc()
+            C.memmove(C.byref(cam), f.ctypes.data, 4 * min(f.size, 19))
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        out_m = np.zeros((self.height, self.width, 2), np.float32)
+        prev = [None if ph is None else _p(ph)] + ([None if pm is None else _p(pm)] if moments else [])
+        outs = [_p(out)] + ([_p(out_m)] if moments else [])
+        check(_lib.require("crt_" + name)(self.h, _p(c), _p(g), _p(pg), *prev, C.byref(cam), C.byref(o), *outs), name)
+        return (out, out_m) if moments else out
 
     def selftest_reproject(self, color, guides, prev_guides, prev_history, prev_camera, position_tolerance,
                            normal_min=float("-inf"), *, max_history) -> np.ndarray:
@@ -908,30 +951,8 @@ class Renderer:
         replaces the sums, scale 1), guides and prev_guides [height, width, 8], prev_history [height, width, 4] or None
         (no previous frame), prev_camera a CameraDesc or its floats (origin, lower_left, horizontal, vertical first).
         Returns the new history [height, width, 4]."""
-        o = self._reproject_options("selftest_reproject", position_tolerance, normal_min, max_history)
-        n = self.width * self.height
-        c = np.ascontiguousarray(color, np.float32).reshape(-1)
-        g = np.ascontiguousarray(guides, np.float32).reshape(-1)
-        pg = np.ascontiguousarray(prev_guides, np.float32).reshape(-1)
-        ph = None if prev_history is None else np.ascontiguousarray(prev_history, np.float32).reshape(-1)
-        if c.size != n * 3:
-            raise ValueError("selftest_reproject: color must hold height * width * 3 floats")
-        if g.size != n * 8 or pg.size != n * 8:
-            raise ValueError("selftest_reproject: guides and prev_guides must hold height * width * 8 floats")
-        if ph is not None and ph.size != n * 4:
-            raise ValueError("selftest_reproject: prev_history must hold height * width * 4 floats")
-        if isinstance(prev_camera, _lib.CameraDesc):
-            cam = prev_camera
-        else:
-            f = np.ascontiguousarray(prev_camera, np.float32).reshape(-1)
-            if f.size < 12:
-                raise ValueError("selftest_reproject: prev_camera must be a CameraDesc or at least 12 floats")
-            cam = _lib.CameraDesc()
-            C.memmove(C.byref(cam), f.ctypes.data, 4 * min(f.size, 19))
-        out = np.zeros((self.height, self.width, 4), np.float32)
-        check(_lib.require("crt_selftest_reproject")(self.h, _p(c), _p(g), _p(pg), None if ph is None else _p(ph),
-                                                     C.byref(cam), C.byref(o), _p(out)), "selftest_reproject")
-        return out
+        return self._selftest_reproject("selftest_reproject", color, guides, prev_guides, prev_history, None, prev_camera,
+                                        position_tolerance, normal_min, max_history)
 
     # ---- variance-guided filtering of the history (crt_hip.h crt_renderer_reproject_moments ff., DESIGN.md §24)
     def reproject_moments(self, position_tolerance, normal_min=float("-inf"), *, max_history, scale=None, stream=None) -> dict:
@@ -939,18 +960,7 @@ class Renderer:
         the same history, bit for bit, plus moments() for denoise_history_variance().  A plain reproject() or
         reset_history() ends the moments' validity, and the next reproject_moments() then starts the whole history
         over.  Synchronous.  Returns {"reproject_ms", "pixels_reprojected", "pixels_hit"}."""
-        o = self._reproject_options("reproject_moments", position_tolerance, normal_min, max_history)
-        try:
-            sc = float(np.float32(scale))
-        except (TypeError, ValueError):
-            raise ValueError("reproject_moments: scale must be a number") from None
-        if not sc > 0:
-            raise ValueError("reproject_moments: scale must be > 0")
-        s = _lib.ReprojectStats()
-        check(_lib.require("crt_renderer_reproject_moments")(self.h, C.byref(o), C.c_float(sc), C.byref(s), stream),
-              "reproject_moments")
-        return {"reproject_ms": float(s.reproject_ms), "pixels_reprojected": int(s.pixels_reprojected),
-                "pixels_hit": int(s.pixels_hit)}
+        return self._reproject("reproject_moments", position_tolerance, normal_min, max_history, scale, stream)
 
     def moments(self) -> np.ndarray:
         """The last reproject_moments()'s moments, float32 [height, width, 2]: the history's means of the luminance
@@ -961,26 +971,14 @@ class Renderer:
 
     @staticmethod
     def _denoise_variance_options(who, sigma_luminance, sigma_normal, sigma_position, min_history, iterations, direct_only):
-        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations <= 8:
-            raise ValueError(f"{who}: iterations must be an int in 1..8")
-        sig = []
-        for name, v in (("sigma_luminance", sigma_luminance), ("sigma_normal", sigma_normal),
-                        ("sigma_position", sigma_position)):
-            try:
-                f = float(np.float32(v))
-            except (TypeError, ValueError):
-                raise ValueError(f"{who}: {name} must be a number") from None
-            if not (f == float("inf") or 2.0 ** -50 <= f <= 2.0 ** 50):
-                raise ValueError(f"{who}: {name} must be in [2^-50, 2^50] or +inf (that term off)")
-            sig.append(f)
+        sig = Renderer._filter_sigmas(who, "sigma_luminance", (sigma_luminance, sigma_normal, sigma_position), iterations)
         try:
             mh = float(np.float32(min_history))
         except (TypeError, ValueError):
             raise ValueError(f"{who}: min_history must be a number") from None
         if not 1.0 <= mh <= 2.0 ** 24:
             raise ValueError(f"{who}: min_history must be in [1, 2^24]")
-        return _lib.DenoiseVarianceOptions(int(iterations), sig[0], sig[1], sig[2], mh,
-                                           _lib.DENOISE_DIRECT_ONLY if direct_only else 0, 0)
+        return _lib.DenoiseVarianceOptions(int(iterations), *sig, mh, _lib.DENOISE_DIRECT_ONLY if direct_only else 0, 0)
 
     def denoise_history_variance(self, sigma_luminance, sigma_normal, sigma_position, *, min_history, iterations: int = 5,
                                  direct_only: bool = False, stream=None) -> dict:
@@ -995,8 +993,7 @@ class Renderer:
         s = _lib.DenoiseStats()
         check(_lib.require("crt_renderer_denoise_history_variance")(self.h, C.byref(o), C.byref(s), stream),
               "denoise_history_variance")
-        return {"guides_ms": float(s.guides_ms), "filter_ms": float(s.filter_ms), "iterations": int(s.iterations),
-                "pixels_hit": int(s.pixels_hit)}
+        return self._denoise_stats(s)
 
     def variance(self) -> np.ndarray:
         """The last denoise_history_variance()'s per-pixel variance estimate (before the filter), float32 [height, width]."""
@@ -1008,37 +1005,8 @@ class Renderer:
                                    position_tolerance, normal_min=float("-inf"), *, max_history):
         """selftest_reproject() with the moments (crt_selftest_reproject_moments): prev_moments [height, width, 2] or
         None together with prev_history.  Returns (history [height, width, 4], moments [height, width, 2])."""
-        o = self._reproject_options("selftest_reproject_moments", position_tolerance, normal_min, max_history)
-        n = self.width * self.height
-        c = np.ascontiguousarray(color, np.float32).reshape(-1)
-        g = np.ascontiguousarray(guides, np.float32).reshape(-1)
-        pg = np.ascontiguousarray(prev_guides, np.float32).reshape(-1)
-        ph = None if prev_history is None else np.ascontiguousarray(prev_history, np.float32).reshape(-1)
-        pm = None if prev_moments is None else np.ascontiguousarray(prev_moments, np.float32).reshape(-1)
-        if c.size != n * 3:
-            raise ValueError("selftest_reproject_moments: color must hold height * width * 3 floats")
-        if g.size != n * 8 or pg.size != n * 8:
-            raise ValueError("selftest_reproject_moments: guides and prev_guides must hold height * width * 8 floats")
-        if ph is not None and ph.size != n * 4:
-            raise ValueError("selftest_reproject_moments: prev_history must hold height * width * 4 floats")
-        if (ph is None) != (pm is None):
-            raise ValueError("selftest_reproject_moments: prev_moments goes with prev_history (both or neither)")
-        if pm is not None and pm.size != n * 2:
-            raise ValueError("selftest_reproject_moments: prev_moments must hold height * width * 2 floats")
-        if isinstance(prev_camera, _lib.CameraDesc):
-            cam = prev_camera
-        else:
-            f = np.ascontiguousarray(prev_camera, np.float32).reshape(-1)
-            if f.size < 12:
-                raise ValueError("selftest_reproject_moments: prev_camera must be a CameraDesc or at least 12 floats")
-            cam = _lib.CameraDesc()
-            C.memmove(C.byref(cam), f.ctypes.data, 4 * min(f.size, 19))
-        out = np.zeros((self.height, self.width, 4), np.float32)
-        out_m = np.zeros((self.height, self.width, 2), np.float32)
-        check(_lib.require("crt_selftest_reproject_moments")(
-            self.h, _p(c), _p(g), _p(pg), None if ph is None else _p(ph), None if pm is None else _p(pm), C.byref(cam),
-            C.byref(o), _p(out), _p(out_m)), "selftest_reproject_moments")
-        return out, out_m
+        return self._selftest_reproject("selftest_reproject_moments", color, guides, prev_guides, prev_history, prev_moments,
+                                        prev_camera, position_tolerance, normal_min, max_history)
 
     def selftest_denoise_variance(self, history, moments, guides, sigma_luminance, sigma_normal, sigma_position, *,
                                   min_history, iterations: int = 5, direct_only: bool = False):
@@ -1047,16 +1015,9 @@ class Renderer:
         [height, width, 3], the variance estimate [height, width])."""
         o = self._denoise_variance_options("selftest_denoise_variance", sigma_luminance, sigma_normal, sigma_position,
                                            min_history, iterations, direct_only)
-        n = self.width * self.height
-        h = np.ascontiguousarray(history, np.float32).reshape(-1)
-        m = np.ascontiguousarray(moments, np.float32).reshape(-1)
-        g = np.ascontiguousarray(guides, np.float32).reshape(-1)
-        if h.size != n * 4:
-            raise ValueError("selftest_denoise_variance: history must hold height * width * 4 floats")
-        if m.size != n * 2:
-            raise ValueError("selftest_denoise_variance: moments must hold height * width * 2 floats")
-        if g.size != n * 8:
-            raise ValueError("selftest_denoise_variance: guides must hold height * width * 8 floats")
+        h = self._flat("selftest_denoise_variance", "history", history, 4)
+        m = self._flat("selftest_denoise_variance", "moments", moments, 2)
+        g = self._flat("selftest_denoise_variance", "guides", guides, 8)
         out = np.zeros((self.height, self.width, 3), np.float32)
         out_v = np.zeros((self.height, self.width), np.float32)
         check(_lib.require("crt_selftest_denoise_variance")(self.h, _p(h), _p(m), _p(g), C.byref(o), _p(out), _p(out_v)),

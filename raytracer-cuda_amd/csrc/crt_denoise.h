@@ -6,7 +6,8 @@
 // i with stride 1 << i over colours kept as one 16-B row per pixel, ping-ponging between two buffers; the last
 // iteration writes the W*H*3 `denoised` buffer.  Every operation is f32 and uncontracted and in the order the header
 // states, so tests/helpers/denoise_model.py reproduces the bits.  Two kernels share one tap loop (denoise_taps): the
-// direct one loads every tap from global memory, the tiled one from rows staged in LDS.
+// direct one loads every tap from global memory, the tiled one from rows staged in LDS.  The variance-guided filter of
+// crt_variance.h is the same tap loop, bodies and host launch loop in their other mode (VAR).
 #pragma once
 
 constexpr int DENOISE_MISS_KEY = 0x7fffffff;
@@ -71,13 +72,17 @@ __global__ __launch_bounds__(256) void crt_denoise_input_kernel(const float* __r
     col[pix] = make_float4(scale * sum[3 * (size_t)pix], scale * sum[3 * (size_t)pix + 1], scale * sum[3 * (size_t)pix + 2], 0.f);
 }
 
+__device__ __forceinline__ float variance_lum(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
+
+// One struct for the plain and the variance-guided kernels (crt_variance.h).
 struct DenoiseParams {
-    const float4* __restrict__ in;      // c_i, 1 row per pixel
+    const float4* __restrict__ in;      // c_i (variance: (c_i, v_i)), 1 row per pixel
     const float4* __restrict__ guides;  // 2 rows per pixel
     float4* __restrict__ out;           // c_{i+1} as rows, or null on the last iteration
     float* __restrict__ out3;           // the last iteration's output, 3 floats per pixel
     int width, height, stride;
-    float inv_c, inv_n, inv_x;          // 1 / sigma^2 of this iteration
+    float k_c;                          // plain: 1 / sigma_color^2 of this level; variance: sigma_luminance as given
+    float inv_n, inv_x;                 // 1 / sigma^2
     int on_c, on_n, on_x;               // 0: the term is off (sigma = +inf), never computed
 };
 
@@ -101,16 +106,43 @@ __device__ __forceinline__ float denoise_dist2(float4 a, float4 b) {
     return (dx * dx + dy * dy) + dz * dz;
 }
 
-// The tap loop both kernels share.  Pixel (x, y) with its own rows (c, g0, g1); fetch(dy, dx, qx, qy, which) returns
-// row `which` (0 colour, 1 guide row 0, 2 guide row 1) of tap q = (x + dx s, y + dy s), and is only called for a q
-// inside the frame.  dy outer, dx inner, the centre in its place with w = 1; a tap outside the frame, with another
-// key, or with !(X < 80) is skipped.
-template <class Fetch>
+// The tap loop all four kernels share.  Pixel (x, y) with its own rows (c, g0, g1); fetch(dy, dx, qx, qy, which)
+// returns row `which` (0 colour, 1 guide row 0, 2 guide row 1) of tap q = (x + dx s, y + dy s), and is only called for
+// a q inside the frame.  dy outer, dx inner, the centre in its place with w = 1; a tap outside the frame, with another
+// key, or with !(X < 80) is skipped.  VAR (the variance-guided filter): the luminance term, as wide as the 3 x 3
+// prefiltered variance says, stands in the colour term's place, and the variance c.w is accumulated beside the colours;
+// vfetch(dy, dx, qx, qy) returns (v, key as float bits) of the prefilter's tap (x + dx, y + dy), called only inside
+// the frame.
+template <bool VAR, class Fetch, class VFetch>
 __device__ __forceinline__ float4 denoise_taps(const DenoiseParams& D, int x, int y, float4 c, float4 g0, float4 g1,
-                                               Fetch fetch) {
+                                               Fetch fetch, VFetch vfetch) {
     constexpr float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     const int key = __float_as_int(g1.w);
-    float ax = 0.f, ay = 0.f, az = 0.f, sw = 0.f;
+    float inv_den = 0.f, lc = 0.f;
+    if constexpr (VAR) {
+        constexpr float hg[3] = {0.25f, 0.5f, 0.25f};
+        if (D.on_c) {
+            float gs = 0.f, gw = 0.f;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const float kg = hg[dy + 1] * hg[dx + 1];
+                    if (dy == 0 && dx == 0) { gs = gs + kg * c.w; gw = gw + kg; continue; }
+                    const int qx = x + dx, qy = y + dy;
+                    if (qx < 0 || qx >= D.width || qy < 0 || qy >= D.height) continue;
+                    const float2 vk = vfetch(dy, dx, qx, qy);
+                    if (__float_as_int(vk.y) != key) continue;
+                    gs = gs + kg * vk.x; gw = gw + kg;
+                }
+            }
+            const float g = gs / gw;
+            const float den = D.k_c * sqrtf(g) + 0x1p-20f;
+            inv_den = 1.f / den;
+        }
+        lc = variance_lum(c.x, c.y, c.z);
+    }
+    float ax = 0.f, ay = 0.f, az = 0.f, av = 0.f, sw = 0.f;
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll
@@ -118,6 +150,7 @@ __device__ __forceinline__ float4 denoise_taps(const DenoiseParams& D, int x, in
             const float k = h[dy + 2] * h[dx + 2];
             if (dy == 0 && dx == 0) {
                 ax = ax + k * c.x; ay = ay + k * c.y; az = az + k * c.z;
+                if constexpr (VAR) av = av + (k * k) * c.w;
                 sw = sw + k;
                 continue;
             }
@@ -127,17 +160,22 @@ __device__ __forceinline__ float4 denoise_taps(const DenoiseParams& D, int x, in
             if (__float_as_int(q1.w) != key) continue;
             const float4 qc = fetch(dy, dx, qx, qy, 0);
             float xc = 0.f, xn = 0.f, xx = 0.f;
-            if (D.on_c) xc = denoise_dist2(c, qc) * D.inv_c;
+            if constexpr (VAR) {
+                if (D.on_c) xc = fabsf(lc - variance_lum(qc.x, qc.y, qc.z)) * inv_den;
+            } else {
+                if (D.on_c) xc = denoise_dist2(c, qc) * D.k_c;
+            }
             if (D.on_n) xn = denoise_dist2(g0, fetch(dy, dx, qx, qy, 1)) * D.inv_n;
             if (D.on_x) xx = denoise_dist2(g1, q1) * D.inv_x;
             const float X = (xc + xn) + xx;
             if (!(X < 80.f)) continue;
             const float kw = k * denoise_exp_neg(X);
             ax = ax + kw * qc.x; ay = ay + kw * qc.y; az = az + kw * qc.z;
+            if constexpr (VAR) av = av + (kw * kw) * qc.w;
             sw = sw + kw;
         }
     }
-    return make_float4(ax / sw, ay / sw, az / sw, 0.f);
+    return make_float4(ax / sw, ay / sw, az / sw, VAR ? av / (sw * sw) : 0.f);
 }
 
 __device__ __forceinline__ void denoise_store(const DenoiseParams& D, size_t pix, float4 o) {
@@ -145,21 +183,30 @@ __device__ __forceinline__ void denoise_store(const DenoiseParams& D, size_t pix
     else D.out[pix] = o;
 }
 
-// The direct kernel: one lane per pixel, every tap from global memory.  The yardstick; any stride.
+// The prefilter's tap from global memory: the fourth lanes of the colour row and of the second guide row.
+__device__ __forceinline__ float2 denoise_vk_global(const DenoiseParams& D, int qx, int qy) {
+    const size_t q = (size_t)qy * D.width + qx;          // inside the frame: the caller checked
+    return make_float2(D.in[q].w, D.guides[2 * q + 1].w);
+}
+
+// The direct kernels: one lane per pixel, every tap from global memory.  The yardstick; any stride.
 constexpr int DENOISE_BX = 64, DENOISE_DIRECT_BY = 4;
-__global__ __launch_bounds__(DENOISE_BX * DENOISE_DIRECT_BY) void crt_denoise_direct_kernel(DenoiseParams D) {
+template <bool VAR>
+__device__ __forceinline__ void denoise_direct_body(const DenoiseParams& D) {
     const int x = blockIdx.x * DENOISE_BX + threadIdx.x, y = blockIdx.y * DENOISE_DIRECT_BY + threadIdx.y;
     if (x >= D.width || y >= D.height) return;
     const size_t pix = (size_t)y * D.width + x;
     const float4 c = D.in[pix], g0 = D.guides[2 * pix], g1 = D.guides[2 * pix + 1];
-    const float4 o = denoise_taps(D, x, y, c, g0, g1, [&](int, int, int qx, int qy, int which) {
-        const size_t q = (size_t)qy * D.width + qx;      // inside the frame: the tap loop checked
-        return which == 0 ? D.in[q] : D.guides[2 * q + (which - 1)];
-    });
+    const float4 o = denoise_taps<VAR>(D, x, y, c, g0, g1,
+        [&](int, int, int qx, int qy, int which) {
+            const size_t q = (size_t)qy * D.width + qx;  // inside the frame: the tap loop checked
+            return which == 0 ? D.in[q] : D.guides[2 * q + (which - 1)];
+        },
+        [&](int, int, int qx, int qy) { return denoise_vk_global(D, qx, qy); });
     denoise_store(D, pix, o);
 }
 
-// The tiled kernel: a workgroup of 64 x 8 lanes filters the pixels x0 .. x0 + 63 of the 8 rows y = r + s (8 g + j),
+// The tiled kernels: a workgroup of 64 x 8 lanes filters the pixels x0 .. x0 + 63 of the 8 rows y = r + s (8 g + j),
 // j = 0 .. 7, of one residue class r of y modulo the stride s: in an a-trous pass only those rows interact.  It stages
 // the 12 rows j = -2 .. 9 over x0 - 2 s .. x0 + 63 + 2 s in LDS, as three arrays of 16-B rows (colour, guide row 0,
 // guide row 1) with coalesced 16-B loads along x, then runs the shared tap loop out of LDS.  LDS: 12 (64 + 4 s) 48 B,
@@ -167,9 +214,14 @@ __global__ __launch_bounds__(DENOISE_BX * DENOISE_DIRECT_BY) void crt_denoise_di
 // (DENOISE_TILED_MAX_STRIDE: measured faster than the direct kernel at s = 1 .. 16 and slower at s = 32, where a block
 // fetches 12 x 192 rows for 512 pixels).  Above 64 KiB the host raises the kernel's dynamic LDS limit once.
 // Entries outside the frame are never written and never read (the tap loop's frame test comes before the fetch).
+// VAR: the variance rides in the staged colour rows' fourth lane.  The prefilter's eight taps lie at +-1 pixel whatever
+// the stride: at s = 1 they are among the staged rows and columns (j +- 1, x +- 1) and come from LDS; at s > 1 the rows
+// y +- 1 belong to other residue classes, which this block does not stage, and all eight come from global memory
+// (DESIGN.md §24 has the cost).
 constexpr int DENOISE_TY = 8, DENOISE_ROWS = DENOISE_TY + 4;
 constexpr int DENOISE_TILED_MAX_STRIDE = 16;
-__global__ __launch_bounds__(DENOISE_BX * DENOISE_TY) void crt_denoise_tiled_kernel(DenoiseParams D, int groups) {
+template <bool VAR>
+__device__ __forceinline__ void denoise_tiled_body(const DenoiseParams& D, int groups) {
     extern __shared__ float4 denoise_lds[];
     const int s = D.stride, cols = DENOISE_BX + 4 * s, n = DENOISE_ROWS * cols;
     float4* l_c = denoise_lds;
@@ -192,11 +244,30 @@ __global__ __launch_bounds__(DENOISE_BX * DENOISE_TY) void crt_denoise_tiled_ker
     const int x = x0 + threadIdx.x, y = r + s * (j0 + threadIdx.y);
     if (x >= D.width || y >= D.height) return;
     const int at = (threadIdx.y + 2) * cols + threadIdx.x + 2 * s;
-    const float4 o = denoise_taps(D, x, y, l_c[at], l_g0[at], l_g1[at], [&](int dy, int dx, int, int, int which) {
-        const int q = at + dy * cols + dx * s;           // row j + dy, column x + dx s of the staged block
-        return which == 0 ? l_c[q] : which == 1 ? l_g0[q] : l_g1[q];
-    });
+    const float4 o = denoise_taps<VAR>(D, x, y, l_c[at], l_g0[at], l_g1[at],
+        [&](int dy, int dx, int, int, int which) {
+            const int q = at + dy * cols + dx * s;       // row j + dy, column x + dx s of the staged block
+            return which == 0 ? l_c[q] : which == 1 ? l_g0[q] : l_g1[q];
+        },
+        [&](int dy, int dx, int qx, int qy) {
+            if (s == 1) { const int q = at + dy * cols + dx; return make_float2(l_c[q].w, l_g1[q].w); }
+            return denoise_vk_global(D, qx, qy);
+        });
     denoise_store(D, (size_t)y * D.width + x, o);
+}
+
+// The host takes these four addresses (the dynamic LDS limit is per kernel function) and the profiles name them.
+__global__ __launch_bounds__(DENOISE_BX * DENOISE_DIRECT_BY) void crt_denoise_direct_kernel(DenoiseParams D) {
+    denoise_direct_body<false>(D);
+}
+__global__ __launch_bounds__(DENOISE_BX * DENOISE_TY) void crt_denoise_tiled_kernel(DenoiseParams D, int groups) {
+    denoise_tiled_body<false>(D, groups);
+}
+__global__ __launch_bounds__(DENOISE_BX * DENOISE_DIRECT_BY) void crt_denoise_variance_direct_kernel(DenoiseParams D) {
+    denoise_direct_body<true>(D);
+}
+__global__ __launch_bounds__(DENOISE_BX * DENOISE_TY) void crt_denoise_variance_tiled_kernel(DenoiseParams D, int groups) {
+    denoise_tiled_body<true>(D, groups);
 }
 
 namespace {
@@ -230,44 +301,56 @@ void denoise_next_guides(DenoiseState* N) {
     if (N->keep) { N->gi ^= 1; N->keep = false; }
 }
 
+// The iterations and the three sigmas of either filter's options; first: the colour term's name.
+int denoise_check_sigmas(const std::string& w, int iterations, const char* first, float s0, float s1, float s2) {
+    if (iterations < 0 || iterations > 8) return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": iterations must be 0..8 (0 = 5)");
+    const float sig[3] = {s0, s1, s2};
+    const char* name[3] = {first, "sigma_normal", "sigma_position"};
+    for (int k = 0; k < 3; ++k)
+        if (!(sig[k] == __builtin_inff() || (sig[k] >= 0x1p-50f && sig[k] <= 0x1p50f)))
+            return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": " + name[k] + " must be in [2^-50, 2^50] or +inf (that term off)");
+    return CRT_OK;
+}
+
 // The checks of the options alone (no handle, no device).
 int denoise_check_options(const crt_denoise_options* o, const char* who) {
     const std::string w = who;
     if (!o) return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": null options");
-    if (o->iterations < 0 || o->iterations > 8) return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": iterations must be 0..8 (0 = 5)");
-    const float sig[3] = {o->sigma_color, o->sigma_normal, o->sigma_position};
-    const char* name[3] = {"sigma_color", "sigma_normal", "sigma_position"};
-    for (int k = 0; k < 3; ++k)
-        if (!(sig[k] == __builtin_inff() || (sig[k] >= 0x1p-50f && sig[k] <= 0x1p50f)))
-            return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": " + name[k] + " must be in [2^-50, 2^50] or +inf (that term off)");
+    if (int rc = denoise_check_sigmas(w, o->iterations, "sigma_color", o->sigma_color, o->sigma_normal, o->sigma_position))
+        return rc;
     if (o->flags & ~(CRT_DENOISE_TILE_SCALE | CRT_DENOISE_DIRECT_ONLY))
         return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": unknown flag bits");
     if (o->reserved != 0) return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": reserved must be 0");
     return CRT_OK;
 }
 
-// The filter on `st`: c0 from the sums, then one launch per iteration.  The handle's guides and options were checked.
-// c0 non-null (crt_renderer_denoise_history): iteration 0 reads those rows' (x, y, z) instead and the sums are not read.
+// What differs between the two filters on the host: the kernel pair, whose dynamic LDS limit was raised (the attribute is
+// per kernel function), and the colour term.
+struct DenoiseFilter {
+    void (*tiled)(DenoiseParams, int);
+    void (*direct)(DenoiseParams);
+    bool* lds_raised;
+    bool quarter;       // true: the colour term is 1 / sigma^2 and quarters per level; false: the sigma as given, every level
+};
+
+// One launch per iteration i with stride 1 << i, from c0 (or col[0]) to `denoised`.  sigma: colour (or luminance),
+// normal, position; iterations, flags: the options' (checked).
 // timed: an event after every launch (crt_renderer_denoise_iteration_ms); the caller waits for f1 before reading them.
-int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, float scale, hipStream_t st, bool timed,
-                const float4* c0 = nullptr) {
-    const int W = R->width, H = R->height, n_pix = W * H;
-    const int iterations = o->iterations ? o->iterations : 5;
-    const bool tile_scale = (o->flags & CRT_DENOISE_TILE_SCALE) != 0, direct_only = (o->flags & CRT_DENOISE_DIRECT_ONLY) != 0;
-    HIP_TRY(hipEventRecord(N->f0.get(), st));
-    if (!c0)
-        hipLaunchKernelGGL(crt_denoise_input_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, R->d_sum, N->col[0].get(),
-                           tile_scale ? R->adaptive->tile_spp.get() : nullptr, W, n_pix, (W + 7) / 8, scale);
+int denoise_iterations(crt_renderer* R, DenoiseState* N, const DenoiseFilter& F, const float* sigma, int iterations,
+                       uint32_t flags, const float4* c0, hipStream_t st, bool timed) {
+    const int W = R->width, H = R->height;
+    if (!iterations) iterations = 5;
+    const bool direct_only = (flags & CRT_DENOISE_DIRECT_ONLY) != 0;
     N->timed_iterations = 0;
     if (timed) HIP_TRY(hipEventRecord(N->it[0].get(), st));
     DenoiseParams D{};
     D.guides = N->guides[N->gi].get();
     D.width = W; D.height = H;
     const float inf = __builtin_inff();
-    D.on_c = o->sigma_color != inf; D.on_n = o->sigma_normal != inf; D.on_x = o->sigma_position != inf;
-    D.inv_c = D.on_c ? 1.f / (o->sigma_color * o->sigma_color) : 0.f;
-    D.inv_n = D.on_n ? 1.f / (o->sigma_normal * o->sigma_normal) : 0.f;
-    D.inv_x = D.on_x ? 1.f / (o->sigma_position * o->sigma_position) : 0.f;
+    D.on_c = sigma[0] != inf; D.on_n = sigma[1] != inf; D.on_x = sigma[2] != inf;
+    D.k_c = !D.on_c ? 0.f : F.quarter ? 1.f / (sigma[0] * sigma[0]) : sigma[0];
+    D.inv_n = D.on_n ? 1.f / (sigma[1] * sigma[1]) : 0.f;
+    D.inv_x = D.on_x ? 1.f / (sigma[2] * sigma[2]) : 0.f;
     for (int i = 0; i < iterations; ++i) {
         const bool last = i == iterations - 1;
         D.in = i == 0 && c0 ? c0 : N->col[i & 1].get();
@@ -278,20 +361,18 @@ int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, 
             const int s = D.stride, rows = (H + s - 1) / s;                   // the rows of residue class 0, the longest
             const int groups = (rows + DENOISE_TY - 1) / DENOISE_TY;
             const size_t lds = (size_t)DENOISE_ROWS * (DENOISE_BX + 4 * s) * 48;
-            if (lds > 65536 && !N->lds_raised) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(crt_denoise_tiled_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize,
+            if (lds > 65536 && !*F.lds_raised) {
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(F.tiled), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             DENOISE_ROWS * (DENOISE_BX + 4 * DENOISE_TILED_MAX_STRIDE) * 48));
-                N->lds_raised = true;
+                *F.lds_raised = true;
             }
-            hipLaunchKernelGGL(crt_denoise_tiled_kernel, dim3((W + DENOISE_BX - 1) / DENOISE_BX, s * groups),
-                               dim3(DENOISE_BX, DENOISE_TY), lds, st, D, groups);
+            hipLaunchKernelGGL(F.tiled, dim3((W + DENOISE_BX - 1) / DENOISE_BX, s * groups), dim3(DENOISE_BX, DENOISE_TY), lds,
+                               st, D, groups);
         } else {
-            hipLaunchKernelGGL(crt_denoise_direct_kernel,
-                               dim3((W + DENOISE_BX - 1) / DENOISE_BX, (H + DENOISE_DIRECT_BY - 1) / DENOISE_DIRECT_BY),
+            hipLaunchKernelGGL(F.direct, dim3((W + DENOISE_BX - 1) / DENOISE_BX, (H + DENOISE_DIRECT_BY - 1) / DENOISE_DIRECT_BY),
                                dim3(DENOISE_BX, DENOISE_DIRECT_BY), 0, st, D);
         }
-        if (D.on_c) D.inv_c = D.inv_c * 4.f;             // the colour sigma halves per level
+        if (F.quarter && D.on_c) D.k_c = D.k_c * 4.f;    // the colour sigma halves per level
         if (timed) HIP_TRY(hipEventRecord(N->it[i + 1].get(), st));
     }
     HIP_TRY(hipGetLastError());
@@ -299,6 +380,21 @@ int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, 
     if (timed) N->timed_iterations = iterations;
     N->have_denoised = true;
     return CRT_OK;
+}
+
+// The filter on `st`: c0 from the sums, then the iterations.  The handle's guides and options were checked.
+// c0 non-null (crt_renderer_denoise_history): iteration 0 reads those rows' (x, y, z) instead and the sums are not read.
+int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, float scale, hipStream_t st, bool timed,
+                const float4* c0 = nullptr) {
+    const int W = R->width, n_pix = W * R->height;
+    const bool tile_scale = (o->flags & CRT_DENOISE_TILE_SCALE) != 0;
+    HIP_TRY(hipEventRecord(N->f0.get(), st));
+    if (!c0)
+        hipLaunchKernelGGL(crt_denoise_input_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, R->d_sum, N->col[0].get(),
+                           tile_scale ? R->adaptive->tile_spp.get() : nullptr, W, n_pix, (W + 7) / 8, scale);
+    const float sigma[3] = {o->sigma_color, o->sigma_normal, o->sigma_position};
+    const DenoiseFilter F{crt_denoise_tiled_kernel, crt_denoise_direct_kernel, &N->lds_raised, true};
+    return denoise_iterations(R, N, F, sigma, o->iterations, o->flags, c0, st, timed);
 }
 
 // The pixels whose guide is a hit: the pack kernel's per-wave counts, summed (N->counted).

@@ -35,8 +35,12 @@ __device__ __forceinline__ bool reproject_finite(float v) { return (__float_as_u
 // rows and output row are coalesced; the taps are a gather whose four addresses are neighbours of the neighbouring
 // lanes'.  The four previous (position, key) rows are loaded together from clamped, always valid addresses before any
 // of them is tested; the previous normal rows only with the normal term on, the history rows only for taps that passed.
+// MOMENTS: the first two luminance moments ride along.  They take exactly the taps the colours took, with the colours'
+// weights, sum and blend factor, and their rows are loaded with the history rows.
 constexpr int REPROJECT_BX = 64, REPROJECT_BY = 4;
-__global__ __launch_bounds__(REPROJECT_BX * REPROJECT_BY) void crt_reproject_kernel(ReprojectParams P) {
+template <bool MOMENTS>
+__device__ __forceinline__ void reproject_body(const ReprojectParams& P, const float2* __restrict__ mom_in,
+                                               float2* __restrict__ mom_out) {
     const int x = blockIdx.x * REPROJECT_BX + threadIdx.x, y = blockIdx.y * REPROJECT_BY + threadIdx.y;
     const int W = P.width, H = P.height;
     bool took = false;
@@ -45,6 +49,9 @@ __global__ __launch_bounds__(REPROJECT_BX * REPROJECT_BY) void crt_reproject_ker
         const float4 g1 = P.guides[2 * pix + 1];
         const float cx = P.scale * P.sum[3 * pix], cy = P.scale * P.sum[3 * pix + 1], cz = P.scale * P.sum[3 * pix + 2];
         float4 out = make_float4(cx, cy, cz, 1.f);
+        float l = 0.f, l2 = 0.f;
+        if constexpr (MOMENTS) { l = variance_lum(cx, cy, cz); l2 = l * l; }
+        float2 om = make_float2(l, l2);
         const int key = __float_as_int(g1.w);
         if (P.valid && key != DENOISE_MISS_KEY && reproject_finite(cx) && reproject_finite(cy) && reproject_finite(cz)) {
             const float dx = g1.x - P.o[0], dy = g1.y - P.o[1], dz = g1.z - P.o[2];
@@ -87,16 +94,22 @@ __global__ __launch_bounds__(REPROJECT_BX * REPROJECT_BY) void crt_reproject_ker
                         if (ok[k]) ok[k] = reproject_dot(g0.x, g0.y, g0.z, p0[k].x, p0[k].y, p0[k].z) >= P.normal_min;
                 }
                 float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+                float2 am = make_float2(0.f, 0.f);
                 float sw = 0.f;
                 float4 hr[4];
+                float2 mr[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k)                      // the rows of the taps that passed, issued together
-                    if (ok[k]) hr[k] = P.hist_in[q[k]];
+                    if (ok[k]) {
+                        hr[k] = P.hist_in[q[k]];
+                        if constexpr (MOMENTS) mr[k] = mom_in[q[k]];
+                    }
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     if (ok[k] && reproject_finite(hr[k].x) && reproject_finite(hr[k].y) && reproject_finite(hr[k].z)) {
                         acc.x = acc.x + w[k] * hr[k].x; acc.y = acc.y + w[k] * hr[k].y;
                         acc.z = acc.z + w[k] * hr[k].z; acc.w = acc.w + w[k] * hr[k].w;
+                        if constexpr (MOMENTS) { am.x = am.x + w[k] * mr[k].x; am.y = am.y + w[k] * mr[k].y; }
                         sw = sw + w[k];
                     }
                 if (sw > 0.f) {
@@ -104,14 +117,33 @@ __global__ __launch_bounds__(REPROJECT_BX * REPROJECT_BY) void crt_reproject_ker
                     const float m = fminf(hl + 1.f, P.max_history);
                     const float a = 1.f / m;
                     out = make_float4(hx + (cx - hx) * a, hy + (cy - hy) * a, hz + (cz - hz) * a, m);
+                    if constexpr (MOMENTS) {
+                        const float h1 = am.x / sw, h2 = am.y / sw;
+                        om = make_float2(h1 + (l - h1) * a, h2 + (l2 - h2) * a);
+                    }
                     took = true;
                 }
             }
         }
         P.hist_out[pix] = out;
+        if constexpr (MOMENTS) mom_out[pix] = om;
     }
     const unsigned long long taken = __ballot(took);
     if (threadIdx.x == 0 && y < H) P.wave_taken[(size_t)y * P.blocks_x + blockIdx.x] = (uint32_t)__popcll(taken);
+}
+
+__global__ __launch_bounds__(REPROJECT_BX * REPROJECT_BY) void crt_reproject_kernel(ReprojectParams P) {
+    reproject_body<false>(P, nullptr, nullptr);
+}
+
+struct ReprojectMomentsParams {
+    ReprojectParams P;
+    const float2* __restrict__ mom_in;      // the previous moments, 1 row per pixel
+    float2* __restrict__ mom_out;
+};
+
+__global__ __launch_bounds__(REPROJECT_BX * REPROJECT_BY) void crt_reproject_moments_kernel(ReprojectMomentsParams M) {
+    reproject_body<true>(M.P, M.mom_in, M.mom_out);
 }
 
 // writeColor of rows (r, g, b, *) with scale 1: crt_resolve_kernel's operations on 16-B rows.
@@ -167,8 +199,19 @@ int reproject_check_options(const crt_reproject_options* o, const char* who) {
     return CRT_OK;
 }
 
-// The kernel's parameters for one call (crt_reproject_kernel and, with the moments beside them,
-// crt_reproject_moments_kernel of crt_variance.h).  Options, guides and state were checked.
+// The variance state (crt_variance.h) with its moment buffers, for a reprojection that carries the moments.
+int reproject_moments_state(crt_renderer* R, VarianceState** out) {
+    if (!R->variance) {
+        R->variance.reset(new (std::nothrow) VarianceState);     // whatever it comes to hold is freed with the handle
+        if (!R->variance) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+    }
+    for (DevBuf<float2>& b : R->variance->mom)
+        if (!b) HIP_TRY(b.alloc((size_t)R->width * R->height));
+    *out = R->variance.get();
+    return CRT_OK;
+}
+
+// The kernels' parameters for one call.  Options, guides and state were checked.
 ReprojectParams reproject_params(crt_renderer* R, DenoiseState* N, ReprojectState* S, const crt_reproject_options* o,
                                  float scale) {
     const float inf = __builtin_inff();
@@ -212,16 +255,25 @@ void reproject_advance(DenoiseState* N, ReprojectState* S) {
 }
 
 // One reprojection on `st`: the launch, then the current frame becomes the previous one.  Options, guides and state
-// were checked.
-int reproject_run(crt_renderer* R, DenoiseState* N, ReprojectState* S, const crt_reproject_options* o, float scale,
-                  hipStream_t st) {
-    const ReprojectParams P = reproject_params(R, N, S, o, scale);
+// were checked.  V non-null: the moments ride beside the history (its buffers exist); null: this history has none.
+int reproject_run(crt_renderer* R, DenoiseState* N, ReprojectState* S, VarianceState* V, const crt_reproject_options* o,
+                  float scale, hipStream_t st) {
+    ReprojectMomentsParams M{};
+    M.P = reproject_params(R, N, S, o, scale);
+    const dim3 grid(M.P.blocks_x, (R->height + REPROJECT_BY - 1) / REPROJECT_BY), block(REPROJECT_BX, REPROJECT_BY);
     HIP_TRY(hipEventRecord(S->e0.get(), st));
-    hipLaunchKernelGGL(crt_reproject_kernel, dim3(P.blocks_x, (R->height + REPROJECT_BY - 1) / REPROJECT_BY),
-                       dim3(REPROJECT_BX, REPROJECT_BY), 0, st, P);
+    if (V) {
+        M.P.valid = S->valid && V->moments_valid;            // a history without moments starts over as a whole
+        M.mom_in = V->mom[V->mi].get();
+        M.mom_out = V->mom[V->mi ^ 1].get();
+        hipLaunchKernelGGL(crt_reproject_moments_kernel, grid, block, 0, st, M);
+    } else {
+        hipLaunchKernelGGL(crt_reproject_kernel, grid, block, 0, st, M.P);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(S->e1.get(), st));
     reproject_advance(N, S);
+    if (V) { V->mi ^= 1; V->moments_valid = true; }
     return CRT_OK;
 }
 
@@ -239,25 +291,84 @@ int reproject_stats(crt_renderer* R, DenoiseState* N, ReprojectState* S, crt_rep
     return CRT_OK;
 }
 
+// crt_renderer_reproject and, with `moments`, crt_renderer_reproject_moments; `who` prefixes the refusals.
+int reproject_entry(crt_renderer* R, const char* who, bool moments, const crt_reproject_options* o, float scale,
+                    crt_reproject_stats* stats_out, void* stream) {
+    const std::string w = who;
+    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": null renderer");
+    if (int rc = reproject_check_options(o, who)) return rc;
+    if (!(scale > 0.f)) return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": scale must be > 0");
+    if (R->tile_shards > 1) return set_error(CRT_ERR_UNSUPPORTED, w + ": a pixel shard other than (0, 1)");
+    if (!R->denoise || !R->denoise->have_guides)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": no guides computed yet (crt_renderer_compute_guides)");
+    HIP_TRY(hipSetDevice(R->device));
+    DenoiseState* N = R->denoise.get();
+    ReprojectState* S = nullptr;
+    if (int rc = reproject_state(R, &S)) return rc;
+    VarianceState* V = nullptr;
+    if (moments) {
+        if (int rc = reproject_moments_state(R, &V)) return rc;
+    } else if (R->variance) {
+        R->variance->moments_valid = false;                  // this history has no moments (crt_variance.h)
+    }
+    if (int rc = reproject_run(R, N, S, V, o, scale, (hipStream_t)stream)) return rc;
+    return stats_out ? reproject_stats(R, N, S, stats_out) : CRT_OK;
+}
+
+// crt_selftest_reproject and, with `moments`, crt_selftest_reproject_moments: the reprojection on caller-supplied
+// buffers, through the renderer's own state and the host function the entries above call, on the null stream.  The
+// colours go into the renderer's linear buffer and are taken with scale 1.
+int reproject_selftest(crt_renderer* R, const char* who, bool moments, const float* color, const float* guides,
+                       const float* prev_guides, const float* prev_history, const float* prev_moments,
+                       const crt_camera_desc* prev_camera, const crt_reproject_options* o, float* out_history,
+                       float* out_moments) {
+    const std::string w = who;
+    if (!R || !color || !guides || !prev_guides || !prev_camera || !out_history || (moments && !out_moments))
+        return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (moments && prev_history && !prev_moments)
+        return set_error(CRT_ERR_INVALID_ARGUMENT, w + ": null prev_moments with a previous history");
+    if (int rc = reproject_check_options(o, who)) return rc;
+    HIP_TRY(hipSetDevice(R->device));
+    DenoiseState* N = nullptr;
+    if (int rc = denoise_state(R, &N)) return rc;
+    ReprojectState* S = nullptr;
+    if (int rc = reproject_state(R, &S)) return rc;
+    VarianceState* V = nullptr;
+    if (moments)
+        if (int rc = reproject_moments_state(R, &V)) return rc;
+    const size_t n_pix = (size_t)R->width * R->height;
+    N->keep = false;
+    S->prev_gi = N->gi ^ 1;
+    HIP_TRY(hipMemcpy(R->d_sum, color, n_pix * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->guides[N->gi].get(), guides, n_pix * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->guides[S->prev_gi].get(), prev_guides, n_pix * 32, hipMemcpyHostToDevice));
+    if (prev_history) HIP_TRY(hipMemcpy(S->hist[S->hi].get(), prev_history, n_pix * 16, hipMemcpyHostToDevice));
+    if (V && prev_history) HIP_TRY(hipMemcpy(V->mom[V->mi].get(), prev_moments, n_pix * 8, hipMemcpyHostToDevice));
+    N->have_guides = true;
+    N->counted = N->timed_guides = false;
+    N->guide_cam = *prev_camera;
+    S->prev_cam = *prev_camera;
+    S->valid = prev_history != nullptr;
+    if (V) V->moments_valid = S->valid;
+    if (int rc = reproject_run(R, N, S, V, o, 1.f, 0)) return rc;
+    HIP_TRY(hipStreamSynchronize(0));
+    HIP_TRY(hipMemcpy(out_history, S->hist[S->hi].get(), n_pix * 16, hipMemcpyDeviceToHost));
+    if (V) HIP_TRY(hipMemcpy(out_moments, V->mom[V->mi].get(), n_pix * 8, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int crt_renderer_reproject(crt_renderer* R, const crt_reproject_options* o, float scale, crt_reproject_stats* stats_out,
                            void* stream) {
-    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "reproject: null renderer");
-    if (int rc = reproject_check_options(o, "reproject")) return rc;
-    if (!(scale > 0.f)) return set_error(CRT_ERR_INVALID_ARGUMENT, "reproject: scale must be > 0");
-    if (R->tile_shards > 1) return set_error(CRT_ERR_UNSUPPORTED, "reproject: a pixel shard other than (0, 1)");
-    if (!R->denoise || !R->denoise->have_guides)
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "reproject: no guides computed yet (crt_renderer_compute_guides)");
-    HIP_TRY(hipSetDevice(R->device));
-    DenoiseState* N = R->denoise.get();
-    ReprojectState* S = nullptr;
-    if (int rc = reproject_state(R, &S)) return rc;
-    if (R->variance) R->variance->moments_valid = false;     // this history has no moments (crt_variance.h)
-    if (int rc = reproject_run(R, N, S, o, scale, (hipStream_t)stream)) return rc;
-    return stats_out ? reproject_stats(R, N, S, stats_out) : CRT_OK;
+    return reproject_entry(R, "reproject", false, o, scale, stats_out, stream);
+}
+
+int crt_renderer_reproject_moments(crt_renderer* R, const crt_reproject_options* o, float scale, crt_reproject_stats* stats_out,
+                                   void* stream) {
+    return reproject_entry(R, "reproject moments", true, o, scale, stats_out, stream);
 }
 
 int crt_renderer_reset_history(crt_renderer* R) {
@@ -306,35 +417,18 @@ float* crt_renderer_history_device_ptr(crt_renderer* R) {
                ? reinterpret_cast<float*>(R->reproject->hist[R->reproject->hi].get()) : nullptr;
 }
 
-// The reprojection on caller-supplied buffers: the renderer's own state and the host function crt_renderer_reproject
-// calls, on the null stream.  The colours go into the renderer's linear buffer and are taken with scale 1.
 int crt_selftest_reproject(crt_renderer* R, const float* color, const float* guides, const float* prev_guides,
                            const float* prev_history, const crt_camera_desc* prev_camera, const crt_reproject_options* o,
                            float* out_history) {
-    if (!R || !color || !guides || !prev_guides || !prev_camera || !out_history)
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "selftest reproject: null argument");
-    if (int rc = reproject_check_options(o, "selftest reproject")) return rc;
-    HIP_TRY(hipSetDevice(R->device));
-    DenoiseState* N = nullptr;
-    if (int rc = denoise_state(R, &N)) return rc;
-    ReprojectState* S = nullptr;
-    if (int rc = reproject_state(R, &S)) return rc;
-    const size_t n_pix = (size_t)R->width * R->height;
-    N->keep = false;
-    S->prev_gi = N->gi ^ 1;
-    HIP_TRY(hipMemcpy(R->d_sum, color, n_pix * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->guides[N->gi].get(), guides, n_pix * 32, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->guides[S->prev_gi].get(), prev_guides, n_pix * 32, hipMemcpyHostToDevice));
-    if (prev_history) HIP_TRY(hipMemcpy(S->hist[S->hi].get(), prev_history, n_pix * 16, hipMemcpyHostToDevice));
-    N->have_guides = true;
-    N->counted = N->timed_guides = false;
-    N->guide_cam = *prev_camera;
-    S->prev_cam = *prev_camera;
-    S->valid = prev_history != nullptr;
-    if (int rc = reproject_run(R, N, S, o, 1.f, 0)) return rc;
-    HIP_TRY(hipStreamSynchronize(0));
-    HIP_TRY(hipMemcpy(out_history, S->hist[S->hi].get(), n_pix * 16, hipMemcpyDeviceToHost));
-    return CRT_OK;
+    return reproject_selftest(R, "selftest reproject", false, color, guides, prev_guides, prev_history, nullptr, prev_camera, o,
+                              out_history, nullptr);
+}
+
+int crt_selftest_reproject_moments(crt_renderer* R, const float* color, const float* guides, const float* prev_guides,
+                                   const float* prev_history, const float* prev_moments, const crt_camera_desc* prev_camera,
+                                   const crt_reproject_options* o, float* out_history, float* out_moments) {
+    return reproject_selftest(R, "selftest reproject moments", true, color, guides, prev_guides, prev_history, prev_moments,
+                              prev_camera, o, out_history, out_moments);
 }
 
 }  // extern "C"

@@ -56,10 +56,13 @@ def inverse_sigmas(sigma_color, sigma_normal, sigma_position):
     return out
 
 
-def iteration(c, normal, position, key, stride, inv_c, inv_n, inv_x):
-    """c_i [H, W, 3] -> c_{i+1}.  normal, position [H, W, 3] float32, key [H, W] int32."""
+def tap_walk(c, v, normal, position, key, stride, colour_term, inv_n, inv_x):
+    """The tap loop of both filters: (c_i [H, W, 3], v_i [H, W] or None) -> (c_{i+1}, v_{i+1} or None).  normal, position
+    [H, W, 3] float32, key [H, W] int32.  colour_term(at) is the colour (or luminance) term [H, W] of one tap, at(a)
+    being `a` at that tap; None: the term is off.  v is accumulated beside the colours with the squared weights."""
     h, w, _ = c.shape
     acc = np.zeros((h, w, 3), F32)
+    av = None if v is None else np.zeros((h, w), F32)
     sw = np.zeros((h, w), F32)
     ys, xs = np.mgrid[0:h, 0:w]
     with np.errstate(all="ignore"):
@@ -68,24 +71,36 @@ def iteration(c, normal, position, key, stride, inv_c, inv_n, inv_x):
                 k = F32(H5[dy + 2] * H5[dx + 2])
                 if dy == 0 and dx == 0:
                     acc = (acc + (k * c).astype(F32)).astype(F32)
+                    if v is not None:
+                        av = (av + (F32(k * k) * v).astype(F32)).astype(F32)
                     sw = (sw + k).astype(F32)
                     continue
                 qy, qx = ys + dy * stride, xs + dx * stride
                 inside = (qy >= 0) & (qy < h) & (qx >= 0) & (qx < w)
                 qy, qx = np.clip(qy, 0, h - 1), np.clip(qx, 0, w - 1)
-                qc = c[qy, qx]
-                take = inside & (key[qy, qx] == key)
+
+                def at(a):                                # a at the tap; where the tap is outside, anything (masked)
+                    return a[qy, qx]
+
+                take = inside & (at(key) == key)
                 zero = np.zeros((h, w), F32)
-                xc = zero if inv_c is None else (dist2(c, qc) * inv_c).astype(F32)
-                xn = zero if inv_n is None else (dist2(normal, normal[qy, qx]) * inv_n).astype(F32)
-                xx = zero if inv_x is None else (dist2(position, position[qy, qx]) * inv_x).astype(F32)
+                xc = zero if colour_term is None else colour_term(at)
+                xn = zero if inv_n is None else (dist2(normal, at(normal)) * inv_n).astype(F32)
+                xx = zero if inv_x is None else (dist2(position, at(position)) * inv_x).astype(F32)
                 X = ((xc + xn).astype(F32) + xx).astype(F32)
                 take &= X < F32(80)                       # a NaN compares false: skipped
                 kw = (k * exp_neg(np.where(take, X, F32(0)))).astype(F32)
-                term = (kw[..., None] * qc).astype(F32)
-                acc = np.where(take[..., None], (acc + term).astype(F32), acc)
+                acc = np.where(take[..., None], (acc + (kw[..., None] * at(c)).astype(F32)).astype(F32), acc)
+                if v is not None:
+                    av = np.where(take, (av + ((kw * kw).astype(F32) * at(v)).astype(F32)).astype(F32), av)
                 sw = np.where(take, (sw + kw).astype(F32), sw)
-        return (acc / sw[..., None]).astype(F32)
+        return (acc / sw[..., None]).astype(F32), None if v is None else (av / (sw * sw).astype(F32)).astype(F32)
+
+
+def iteration(c, normal, position, key, stride, inv_c, inv_n, inv_x):
+    """c_i [H, W, 3] -> c_{i+1}."""
+    term = None if inv_c is None else lambda at: (dist2(c, at(c)) * inv_c).astype(F32)
+    return tap_walk(c, None, normal, position, key, stride, term, inv_n, inv_x)[0]
 
 
 def split_guides(guides):

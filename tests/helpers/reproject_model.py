@@ -9,6 +9,7 @@ from denoise_model import F32, MISS_KEY, canon, centre_rays, dist2, pack_guides,
 
 INF = float("inf")
 ONE, HALF = F32(1), F32(0.5)
+LR, LG, LB = F32(0.2126), F32(0.7152), F32(0.0722)
 
 
 def dot(a, b):
@@ -54,9 +55,27 @@ def project(pos, cam, w, h):
     return s, fx, fy
 
 
-def reproject(c, guides, prev_guides, prev_history, prev_cam, position_tolerance, normal_min, max_history):
+def lum(c):
+    """(0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z over the last axis."""
+    c = np.asarray(c, F32)
+    with np.errstate(all="ignore"):
+        a = ((LR * c[..., 0]).astype(F32) + (LG * c[..., 1]).astype(F32)).astype(F32)
+        return (a + (LB * c[..., 2]).astype(F32)).astype(F32)
+
+
+def frame_moments(c):
+    """(l, l * l) of a frame [H, W, 3]."""
+    with np.errstate(all="ignore"):
+        l = lum(c)
+        return np.stack([l, (l * l).astype(F32)], axis=-1)
+
+
+def reproject(c, guides, prev_guides, prev_history, prev_cam, position_tolerance, normal_min, max_history,
+              prev_moments=None):
     """One call.  c [H, W, 3] = scale * sum; guides, prev_guides [H, W, 8]; prev_history [H, W, 4] or None (the state is
-    not valid).  Returns (history [H, W, 4], taken [H, W] bool: the pixels with sw > 0)."""
+    not valid).  Returns (history [H, W, 4], taken [H, W] bool: the pixels with sw > 0).  With prev_moments [H, W, 2]
+    (crt_renderer_reproject_moments: they take the history's taps, weights, sum and blend factor) it returns
+    (history, moments [H, W, 2], taken)."""
     c = np.ascontiguousarray(c, F32)
     h, w, _ = c.shape
     out = np.concatenate([c, np.ones((h, w, 1), F32)], axis=-1)
@@ -64,6 +83,7 @@ def reproject(c, guides, prev_guides, prev_history, prev_cam, position_tolerance
     if prev_history is None:
         return out, taken
     ph = np.ascontiguousarray(prev_history, F32)
+    pm = None if prev_moments is None else np.ascontiguousarray(prev_moments, F32)
     n, pos, key = split_guides(guides)
     pn, ppos, pkey = split_guides(prev_guides)
     o, L, N, hor, ver, LN, hh, vv, tol2 = host_constants(prev_cam, position_tolerance)
@@ -82,6 +102,7 @@ def reproject(c, guides, prev_guides, prev_history, prev_cam, position_tolerance
             d = (pos - o).astype(F32)
             lim = (tol2 * dot(d, d)).astype(F32)
         acc = np.zeros((h, w, 4), F32)
+        am = np.zeros((h, w, 2), F32)
         sw = np.zeros((h, w), F32)
         for j in (0, 1):
             for i in (0, 1):
@@ -99,14 +120,21 @@ def reproject(c, guides, prev_guides, prev_history, prev_cam, position_tolerance
                 row = ph[ty, tx]
                 ok &= np.isfinite(row[..., 0:3]).all(axis=-1)
                 acc = np.where(ok[..., None], (acc + (wgt[..., None] * row).astype(F32)).astype(F32), acc)
+                if pm is not None:
+                    am = np.where(ok[..., None], (am + (wgt[..., None] * pm[ty, tx]).astype(F32)).astype(F32), am)
                 sw = np.where(ok, (sw + wgt).astype(F32), sw)
         taken = sw > 0
-        hist = (acc / np.where(taken, sw, ONE)[..., None]).astype(F32)
+        div = np.where(taken, sw, ONE)[..., None]
+        hist = (acc / div).astype(F32)
         m = np.fmin((hist[..., 3] + ONE).astype(F32), cap).astype(F32)
         a = (ONE / m).astype(F32)
         col = (hist[..., 0:3] + ((c - hist[..., 0:3]).astype(F32) * a[..., None]).astype(F32)).astype(F32)
         blended = np.concatenate([col, m[..., None]], axis=-1)
         out = np.where(taken[..., None], blended, out).astype(F32)
+        if pm is not None:
+            new_m, hm = frame_moments(c), (am / div).astype(F32)
+            mom = (hm + ((new_m - hm).astype(F32) * a[..., None]).astype(F32)).astype(F32)
+            return out, np.where(taken[..., None], mom, new_m).astype(F32), taken
     return out, taken
 
 

@@ -7,94 +7,25 @@ sqrt is correctly rounded, as the build's is).
 """
 import numpy as np
 
-from denoise_model import F32, H5, MISS_KEY, canon, dist2, exp_neg, split_guides  # noqa: F401
-from reproject_model import dot, host_constants, project
+from denoise_model import F32, H5, MISS_KEY, canon, dist2, exp_neg, split_guides, tap_walk  # noqa: F401
+from reproject_model import dot, frame_moments, host_constants, lum, project  # noqa: F401
 import reproject_model as rm
 
 INF = float("inf")
 ONE, ZERO = F32(1), F32(0)
-LR, LG, LB = F32(0.2126), F32(0.7152), F32(0.0722)
 HG = (F32(0.25), F32(0.5), F32(0.25))
 EPS_DEN = F32(2.0 ** -20)
-
-
-def lum(c):
-    """(0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z over the last axis."""
-    c = np.asarray(c, F32)
-    with np.errstate(all="ignore"):
-        a = ((LR * c[..., 0]).astype(F32) + (LG * c[..., 1]).astype(F32)).astype(F32)
-        return (a + (LB * c[..., 2]).astype(F32)).astype(F32)
-
-
-def frame_moments(c):
-    """(l, l * l) of a frame [H, W, 3]."""
-    with np.errstate(all="ignore"):
-        l = lum(c)
-        return np.stack([l, (l * l).astype(F32)], axis=-1)
 
 
 def reproject_moments(c, guides, prev_guides, prev_history, prev_moments, prev_cam, position_tolerance, normal_min,
                       max_history):
     """One crt_renderer_reproject_moments.  As reproject_model.reproject, with prev_moments [H, W, 2] (None together with
     prev_history: the state is not valid).  Returns (history [H, W, 4], moments [H, W, 2], taken [H, W])."""
-    c = np.ascontiguousarray(c, F32)
-    h, w, _ = c.shape
-    new_m = frame_moments(c)
-    out = np.concatenate([c, np.ones((h, w, 1), F32)], axis=-1)
-    taken = np.zeros((h, w), bool)
     if prev_history is None:
-        return out, new_m, taken
-    ph = np.ascontiguousarray(prev_history, F32)
-    pm = np.ascontiguousarray(prev_moments, F32)
-    n, pos, key = split_guides(guides)
-    pn, ppos, pkey = split_guides(prev_guides)
-    o, L, N, hor, ver, LN, hh, vv, tol2 = host_constants(prev_cam, position_tolerance)
-    nmin = F32(normal_min)
-    on_n = nmin != -INF
-    cap = F32(max_history)
-    with np.errstate(all="ignore"):
-        cand = (key != MISS_KEY) & np.isfinite(c).all(axis=-1)
-        s, fx, fy = project(pos, prev_cam, w, h)
-        cand &= (s > 0) & (fx > F32(-1)) & (fx < F32(w)) & (fy > F32(-1)) & (fy < F32(h))     # a NaN fails
-        fx, fy = np.where(cand, fx, ZERO), np.where(cand, fy, ZERO)
-        x0f, y0f = np.floor(fx), np.floor(fy)
-        ax, ay = (fx - x0f).astype(F32), (fy - y0f).astype(F32)
-        x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
-        if tol2 is not None:
-            d = (pos - o).astype(F32)
-            lim = (tol2 * dot(d, d)).astype(F32)
-        acc = np.zeros((h, w, 4), F32)
-        am = np.zeros((h, w, 2), F32)
-        sw = np.zeros((h, w), F32)
-        for j in (0, 1):
-            for i in (0, 1):
-                wx = ax if i else (ONE - ax).astype(F32)
-                wy = ay if j else (ONE - ay).astype(F32)
-                wgt = (wx * wy).astype(F32)
-                tx, ty = x0 + i, y0 + j
-                ok = cand & (tx >= 0) & (tx < w) & (ty >= 0) & (ty < h) & (wgt > 0)
-                tx, ty = np.clip(tx, 0, w - 1), np.clip(ty, 0, h - 1)
-                ok &= pkey[ty, tx] == key
-                if tol2 is not None:
-                    ok &= dist2(pos, ppos[ty, tx]) <= lim
-                if on_n:
-                    ok &= dot(n, pn[ty, tx]) >= nmin
-                row, mrow = ph[ty, tx], pm[ty, tx]
-                ok &= np.isfinite(row[..., 0:3]).all(axis=-1)
-                acc = np.where(ok[..., None], (acc + (wgt[..., None] * row).astype(F32)).astype(F32), acc)
-                am = np.where(ok[..., None], (am + (wgt[..., None] * mrow).astype(F32)).astype(F32), am)
-                sw = np.where(ok, (sw + wgt).astype(F32), sw)
-        taken = sw > 0
-        div = np.where(taken, sw, ONE)[..., None]
-        hist = (acc / div).astype(F32)
-        m = np.fmin((hist[..., 3] + ONE).astype(F32), cap).astype(F32)
-        a = (ONE / m).astype(F32)
-        col = (hist[..., 0:3] + ((c - hist[..., 0:3]).astype(F32) * a[..., None]).astype(F32)).astype(F32)
-        hm = (am / div).astype(F32)
-        mom = (hm + ((new_m - hm).astype(F32) * a[..., None]).astype(F32)).astype(F32)
-        out = np.where(taken[..., None], np.concatenate([col, m[..., None]], axis=-1), out).astype(F32)
-        mom = np.where(taken[..., None], mom, new_m).astype(F32)
-    return out, mom, taken
+        out, taken = rm.reproject(c, guides, prev_guides, None, prev_cam, position_tolerance, normal_min, max_history)
+        return out, frame_moments(np.ascontiguousarray(c, F32)), taken
+    return rm.reproject(c, guides, prev_guides, prev_history, prev_cam, position_tolerance, normal_min, max_history,
+                        prev_moments)
 
 
 def estimate(history, moments, key, min_history):
@@ -147,44 +78,17 @@ def prefilter(v, key):
 
 def iteration(c, v, normal, position, key, stride, sigma_l, inv_n, inv_x):
     """(c_i [H, W, 3], v_i [H, W]) -> (c_{i+1}, v_{i+1}).  sigma_l None: the luminance term is off."""
-    h, w, _ = c.shape
-    acc = np.zeros((h, w, 3), F32)
-    av = np.zeros((h, w), F32)
-    sw = np.zeros((h, w), F32)
-    ys, xs = np.mgrid[0:h, 0:w]
-    with np.errstate(all="ignore"):
-        if sigma_l is not None:
+    term = None
+    if sigma_l is not None:
+        with np.errstate(all="ignore"):
             g = prefilter(v, key)
             den = ((F32(sigma_l) * np.sqrt(g).astype(F32)).astype(F32) + EPS_DEN).astype(F32)
             inv_den = (ONE / den).astype(F32)
-        lc = lum(c)
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                k = F32(H5[dy + 2] * H5[dx + 2])
-                if dy == 0 and dx == 0:
-                    acc = (acc + (k * c).astype(F32)).astype(F32)
-                    av = (av + (F32(k * k) * v).astype(F32)).astype(F32)
-                    sw = (sw + k).astype(F32)
-                    continue
-                qy, qx = ys + dy * stride, xs + dx * stride
-                inside = (qy >= 0) & (qy < h) & (qx >= 0) & (qx < w)
+            lc = lum(c)
 
-                def at(a):                                # a at the tap; where the tap is outside, anything (masked)
-                    return np.roll(a, (-dy * stride, -dx * stride), axis=(0, 1))
-
-                qc, qv = at(c), at(v)
-                take = inside & (at(key) == key)
-                zero = np.zeros((h, w), F32)
-                xc = zero if sigma_l is None else (np.abs((lc - at(lc)).astype(F32)) * inv_den).astype(F32)   # lum(qc)
-                xn = zero if inv_n is None else (dist2(normal, at(normal)) * inv_n).astype(F32)
-                xx = zero if inv_x is None else (dist2(position, at(position)) * inv_x).astype(F32)
-                X = ((xc + xn).astype(F32) + xx).astype(F32)
-                take &= X < F32(80)                       # a NaN compares false: skipped
-                kw = (k * exp_neg(np.where(take, X, ZERO))).astype(F32)
-                acc = np.where(take[..., None], (acc + (kw[..., None] * qc).astype(F32)).astype(F32), acc)
-                av = np.where(take, (av + ((kw * kw).astype(F32) * qv).astype(F32)).astype(F32), av)
-                sw = np.where(take, (sw + kw).astype(F32), sw)
-        return (acc / sw[..., None]).astype(F32), (av / (sw * sw).astype(F32)).astype(F32)
+        def term(at):                                     # at(lc): lum(qc)
+            return (np.abs((lc - at(lc)).astype(F32)) * inv_den).astype(F32)
+    return tap_walk(c, v, normal, position, key, stride, term, inv_n, inv_x)
 
 
 def filter_steps(c0, v0, guides, sigma_luminance, sigma_normal, sigma_position, steps):

@@ -198,6 +198,24 @@ def test_reproject_moments_on_crafted_buffers(w, h):
             assert b > a > c3 > 0, (previous, taken_by)
 
 
+@pytest.mark.parametrize("w,h", [(65, 5), (37, 19)])
+def test_reproject_moments_history_is_the_plain_entrys_raw_bits(w, h):
+    """Both kernels are one body (crt_reproject.h reproject_body): the history rows agree as raw uint32, the payload of
+    every NaN included (the test above maps the NaNs to one pattern first)."""
+    r = crt_amd.Renderer(w, h)
+    nans = 0
+    for pi, previous in enumerate(PREVIOUS):
+        c, guides, prev_guides, hist, mom, prev_cam = _crafted_reproject(w, h, 2000 + 31 * w + h + 7 * pi, previous)
+        for opts in OPTION_SETS:
+            plain = r.selftest_reproject(c, guides, prev_guides, hist, prev_cam, opts[0], opts[1], max_history=opts[2])
+            got_h = r.selftest_reproject_moments(c, guides, prev_guides, hist, mom, prev_cam, opts[0], opts[1],
+                                                 max_history=opts[2])[0]
+            diff = got_h.view(np.uint32) != plain.view(np.uint32)
+            assert not diff.any(), (w, h, previous, opts, int(diff.sum()), np.argwhere(diff)[:4].tolist())
+            nans += int(np.isnan(plain).sum())
+    assert nans > 0                                                                    # there were NaNs to compare
+
+
 # ------------------------------------------------------------------------------------------ 3. a real sequence
 @pytest.fixture(scope="module")
 def bunny_w4(device_scenes):
