@@ -215,7 +215,8 @@ int  crt_scene_create(const crt_scene_desc* desc, int device, crt_scene** out);
  * spheres are tested once per ray behind the reference's own box test for them; with more, the spheres of radius
  * below 1 go into the tree's leaves and those of radius >= 1 stay per ray, of which there may then be at most 8
  * (more: CRT_ERR_INVALID_ARGUMENT; width 2 takes any number).  Only per ray is a sphere's reference box replayed,
- * which a large sphere needs: its f32 roots can land outside its own box. */
+ * which a large sphere needs: its f32 roots can land outside its own box.
+ * Both create calls return after the uploads have completed on the device: the scene may be used on any stream at once. */
 int  crt_scene_create_ex(const crt_scene_desc* desc, int device, const crt_scene_options* opts, crt_scene** out);
 int  crt_scene_get_stats(const crt_scene* scene, crt_scene_stats* out);
 void crt_scene_destroy(crt_scene* scene);
@@ -711,11 +712,18 @@ int crt_scene_export_shade_rows(const crt_scene_desc* desc, float* out, int64_t*
  * destroyed mean the sequence released what it allocated, whatever other processes do on the device. */
 int crt_debug_live_allocations(int64_t* buffers, int64_t* bytes);
 
-/* ---- renderer (CUDARenderer) ---- */
+/* ---- renderer (CUDARenderer) ----
+ * Streams: every entry that takes `stream` enqueues all its device work on that stream (NULL = the null stream), a
+ * non-blocking stream included, and nothing on any other.  Unless its comment says that it waits, an entry only
+ * enqueues and returns; the first use of a path on a handle may allocate.  DESIGN.md section 5d lists which entries
+ * wait on the host and why. */
+/* Returns after the handle's buffers have been initialised on the device: its first call may come on any stream. */
 int  crt_renderer_create(int width, int height, int device, crt_renderer** out);
 void crt_renderer_destroy(crt_renderer* r);
 /* curand_init(seed, subsequence_base + y*width + x, 0) per pixel (CUDAKernels.h:18-26).
- * subsequence_base = shard * width * height for spp sharding. */
+ * subsequence_base = shard * width * height for spp sharding.  Asynchronous, except that the first call on a handle that
+ * computes a state waits for the stream once (it allocates the cache of the initialised state); a repeated
+ * (seed, base) is a device copy of that cache. */
 int  crt_renderer_init_rand(crt_renderer* r, unsigned long long seed, unsigned long long subsequence_base, void* stream);
 /* CRT_ERR_INVALID_ARGUMENT for a non-finite origin or lens radius, or |origin| >= 2^59 / lens_radius >= 2^58 (the
  * rebuilt tree's slab test needs |o| * 2^64 finite; every real scene is many orders of magnitude inside it). */
@@ -794,12 +802,17 @@ int  crt_renderer_set_stack_lds(crt_renderer* r, int entries);
  * waves, 12 at 6 and 8 at 7+ (LDS is allocated in 1-KiB steps per workgroup). */
 int  crt_renderer_set_occupancy_target(crt_renderer* r, int waves_per_simd);
 /* Trace `spp` samples per pixel continuing each pixel's RNG stream; the per-pixel
- * linear sum (pixel_color, CUDAKernels.h:157-162) is kept in an fp32 W*H*3 buffer. */
+ * linear sum (pixel_color, CUDAKernels.h:157-162) is kept in an fp32 W*H*3 buffer.  Asynchronous, except that it waits
+ * for the stream once where it allocates (the first use of variants 7, 8 and 10 on a handle, the first variant-7 frame
+ * with the temporal order, a grown overflow stack), and for the probe and the tile sort where variant 8's automatic
+ * occupancy reads the probe's statistics (crt_renderer_set_occupancy_target). */
 int  crt_renderer_render(crt_renderer* r, const crt_scene* scene, int spp, int max_bounces, unsigned flags, void* stream);
-/* RGBA8 = writeColor(scale * sum) (CRTUtility.cuh:14-32); row 0 is the bottom row. */
+/* RGBA8 = writeColor(scale * sum) (CRTUtility.cuh:14-32); row 0 is the bottom row.  Asynchronous, as are
+ * crt_renderer_resolve_adaptive, crt_renderer_resolve_denoised and crt_renderer_resolve_history. */
 int  crt_renderer_resolve(crt_renderer* r, float scale, void* stream);
-/* The reference's CUDARenderer::render: fresh sum, camera spp, 20 bounces, resolve, synchronize. */
+/* The reference's CUDARenderer::render: fresh sum, camera spp, 20 bounces, resolve, synchronize.  Synchronous. */
 int  crt_renderer_render_frame(crt_renderer* r, const crt_scene* scene, void* stream);
+/* Waits for `stream`, then reports the device error word of the renders before it (CRT_ERR_HIP) and clears it. */
 int  crt_renderer_synchronize(crt_renderer* r, void* stream);
 int  crt_renderer_read_linear(crt_renderer* r, float* host_out);        /* W*H*3 floats */
 int  crt_renderer_read_rgba8(crt_renderer* r, uint8_t* host_out);        /* W*H*4 bytes */

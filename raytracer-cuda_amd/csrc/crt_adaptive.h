@@ -132,7 +132,8 @@ namespace {
 
 int adaptive_tiles(const crt_renderer* R) { return ((R->width + 7) / 8) * ((R->height + 7) / 8); }
 
-int adaptive_state(crt_renderer* R, AdaptiveState** out) {
+// The state is allocated on first use and initialised on `st`, the stream its first user goes on to enqueue on.
+int adaptive_state(crt_renderer* R, hipStream_t st, AdaptiveState** out) {
     if (!R->adaptive) {
         R->adaptive.reset(new (std::nothrow) AdaptiveState);   // whatever is allocated below is freed with the handle
         AdaptiveState* A = R->adaptive.get();
@@ -147,11 +148,11 @@ int adaptive_state(crt_renderer* R, AdaptiveState** out) {
         HIP_TRY(A->list.alloc(n_tiles));
         HIP_TRY(A->d_count.alloc(1));
         HIP_TRY(A->h_count.alloc(1));
-        HIP_TRY(hipMemset(A->prev.get(), 0, n_pix * 3 * sizeof(float)));
-        HIP_TRY(hipMemset(A->tile_spp.get(), 0, n_tiles * 4));
-        HIP_TRY(hipMemset(A->tile_error.get(), 0, n_tiles * 4));
-        HIP_TRY(hipMemset(A->list.get(), 0xff, n_tiles * 4));
-        HIP_TRY(hipMemset(A->d_count.get(), 0, 4));
+        HIP_TRY(hipMemsetAsync(A->prev.get(), 0, n_pix * 3 * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(A->tile_spp.get(), 0, n_tiles * 4, st));
+        HIP_TRY(hipMemsetAsync(A->tile_error.get(), 0, n_tiles * 4, st));
+        HIP_TRY(hipMemsetAsync(A->list.get(), 0xff, n_tiles * 4, st));
+        HIP_TRY(hipMemsetAsync(A->d_count.get(), 0, 4, st));
         HIP_TRY(A->ev0.create());
         HIP_TRY(A->ev1.create());
         A->ready = true;
@@ -234,7 +235,7 @@ int crt_renderer_render_adaptive(crt_renderer* R, const crt_scene* S, const crt_
     HIP_TRY(hipSetDevice(R->device));
     hipStream_t st = (hipStream_t)stream;
     AdaptiveState* A = nullptr;
-    if (int rc = adaptive_state(R, &A)) return rc;
+    if (int rc = adaptive_state(R, st, &A)) return rc;
     const size_t n_pix = (size_t)R->width * R->height;
     const int tiles_x = (R->width + 7) / 8, n_tiles = adaptive_tiles(R);
     if (!R->n_cus) HIP_TRY(hipDeviceGetAttribute(&R->n_cus, hipDeviceAttributeMultiprocessorCount, R->device));
@@ -310,7 +311,7 @@ int crt_selftest_adaptive_plan(crt_renderer* R, const float* sum, const float* p
     if (tolerance != tolerance) return set_error(CRT_ERR_INVALID_ARGUMENT, "selftest adaptive plan: tolerance is NaN");
     HIP_TRY(hipSetDevice(R->device));
     AdaptiveState* A = nullptr;
-    if (int rc = adaptive_state(R, &A)) return rc;
+    if (int rc = adaptive_state(R, 0, &A)) return rc;
     const size_t n_pix = (size_t)R->width * R->height, n_tiles = (size_t)adaptive_tiles(R);
     HIP_TRY(hipMemcpy(R->d_sum, sum, n_pix * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(A->prev.get(), prev, n_pix * 12, hipMemcpyHostToDevice));

@@ -272,7 +272,8 @@ __global__ __launch_bounds__(DENOISE_BX * DENOISE_TY) void crt_denoise_variance_
 
 namespace {
 
-int denoise_state(crt_renderer* R, DenoiseState** out) {
+// The state is allocated on first use and initialised on `st`, the stream its first user goes on to enqueue on.
+int denoise_state(crt_renderer* R, hipStream_t st, DenoiseState** out) {
     if (!R->denoise) {
         R->denoise.reset(new (std::nothrow) DenoiseState);   // whatever is allocated below is freed with the handle
         DenoiseState* N = R->denoise.get();
@@ -285,7 +286,7 @@ int denoise_state(crt_renderer* R, DenoiseState** out) {
         HIP_TRY(N->col[1].alloc(n_pix));
         HIP_TRY(N->denoised.alloc(n_pix * 3));
         HIP_TRY(N->wave_hits.alloc((n_pix + 63) / 64));
-        HIP_TRY(hipMemset(N->denoised.get(), 0, n_pix * 12));
+        HIP_TRY(hipMemsetAsync(N->denoised.get(), 0, n_pix * 12, st));
         for (DevEvent* e : {&N->g0, &N->g1, &N->f0, &N->f1}) HIP_TRY(e->create());
         for (DevEvent& e : N->it) HIP_TRY(e.create());
         N->ready = true;
@@ -435,7 +436,7 @@ int crt_renderer_compute_guides(crt_renderer* R, const crt_scene* S, const crt_t
     HIP_TRY(hipSetDevice(R->device));
     hipStream_t st = (hipStream_t)stream;
     DenoiseState* N = nullptr;
-    if (int rc = denoise_state(R, &N)) return rc;
+    if (int rc = denoise_state(R, st, &N)) return rc;
     const int n_pix = R->width * R->height;
     N->have_guides = N->counted = false;
     denoise_next_guides(N);
@@ -469,7 +470,7 @@ int crt_renderer_denoise(crt_renderer* R, const crt_denoise_options* o, float sc
         return set_error(CRT_ERR_INVALID_ARGUMENT, "denoise: no guides computed yet (crt_renderer_compute_guides)");
     HIP_TRY(hipSetDevice(R->device));
     DenoiseState* N = nullptr;
-    if (int rc = denoise_state(R, &N)) return rc;
+    if (int rc = denoise_state(R, (hipStream_t)stream, &N)) return rc;
     if (int rc = denoise_run(R, N, o, scale, (hipStream_t)stream, stats_out != nullptr)) return rc;
     return stats_out ? denoise_stats(R, N, o, stats_out) : CRT_OK;
 }
@@ -524,7 +525,7 @@ int crt_selftest_denoise(crt_renderer* R, const float* color, const float* guide
         return set_error(CRT_ERR_INVALID_ARGUMENT, "selftest denoise: takes the colours as they are (no tile scale)");
     HIP_TRY(hipSetDevice(R->device));
     DenoiseState* N = nullptr;
-    if (int rc = denoise_state(R, &N)) return rc;
+    if (int rc = denoise_state(R, 0, &N)) return rc;
     const size_t n_pix = (size_t)R->width * R->height;
     HIP_TRY(hipMemcpy(R->d_sum, color, n_pix * 12, hipMemcpyHostToDevice));
     denoise_next_guides(N);

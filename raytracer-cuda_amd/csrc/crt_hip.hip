@@ -3291,6 +3291,12 @@ int crt_scene_create_ex(const crt_scene_desc* D, int device, const crt_scene_opt
         return set_error(CRT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
     }
     tr.lap("uploads");
+    // the uploads above are null-stream copies: wait for them here, once per handle, so that a caller may trace or
+    // render over the scene on any stream (a non-blocking one too) as soon as it holds the handle
+    if ((e = hipStreamSynchronize(0)) != hipSuccess) {
+        crt_scene_destroy(S);
+        return set_error(CRT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
+    }
     *out = S;
     return CRT_OK;
 }
@@ -3387,6 +3393,12 @@ int crt_renderer_create(int width, int height, int device, crt_renderer** out) {
     R->rcp_w = 1.0f / (float)width;
     R->rcp_h = 1.0f / (float)height;
     R->fast_uv = bad_w == 0 && bad_h == 0;
+    // the table's copy, the three clears and the division checks ran on the null stream: wait for them here, once per
+    // handle, so that the first call may come on any stream (a non-blocking one too)
+    if ((e = hipStreamSynchronize(0)) != hipSuccess) {
+        crt_renderer_destroy(R);
+        return set_error(CRT_ERR_HIP, std::string("renderer initialisation: ") + hipGetErrorString(e));
+    }
     *out = R;
     return CRT_OK;
 }
@@ -4049,7 +4061,10 @@ int crt_renderer_render_frame(crt_renderer* R, const crt_scene* S, void* stream)
 // fault, at the synchronisation after the launch (CUDARenderer.cuh:59, CUDA_CHECK(cudaDeviceSynchronize())).
 static int take_device_error(crt_renderer* R, unsigned long long word) {
     if (!word) return CRT_OK;
+    // the callers waited for the stream before they read the word; the clear is a null-stream operation and is waited
+    // for, so that a render the caller enqueues next on any stream cannot have its report cleared
     HIP_TRY(hipMemset(R->d_counters.get() + ERR_WORD, 0, sizeof(unsigned long long)));
+    HIP_TRY(hipStreamSynchronize(0));
     std::string m = "render kernel reported an internal error:";
     if (word & 1u) m += " primitive index out of range;";
     if (word & 2u) m += " traversal stack deeper than the scene's stack bound (entries dropped);";

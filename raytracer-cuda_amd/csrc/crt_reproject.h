@@ -330,7 +330,7 @@ int reproject_selftest(crt_renderer* R, const char* who, bool moments, const flo
     if (int rc = reproject_check_options(o, who)) return rc;
     HIP_TRY(hipSetDevice(R->device));
     DenoiseState* N = nullptr;
-    if (int rc = denoise_state(R, &N)) return rc;
+    if (int rc = denoise_state(R, 0, &N)) return rc;
     ReprojectState* S = nullptr;
     if (int rc = reproject_state(R, &S)) return rc;
     VarianceState* V = nullptr;

@@ -124,14 +124,15 @@ constexpr int TRACE4_STACK = 64;             // trace4's per-lane stack (int sta
 
 namespace {
 
-int trace_scratch(crt_scene* S, TraceScratch** out) {
+// The scratch is allocated on first use and initialised on `st`, the stream its first user goes on to enqueue on.
+int trace_scratch(crt_scene* S, hipStream_t st, TraceScratch** out) {
     if (!S->trace) {
         S->trace.reset(new (std::nothrow) TraceScratch);   // whatever is allocated below is freed with the handle
         TraceScratch* X = S->trace.get();
         if (!X) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
         HIP_TRY(X->d_next.alloc(1));
         HIP_TRY(X->d_stats.alloc(TRACE_STAT_WORDS));
-        HIP_TRY(hipMemset(X->d_stats.get(), 0, TRACE_STAT_WORDS * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(X->d_stats.get(), 0, TRACE_STAT_WORDS * sizeof(unsigned long long), st));
         HIP_TRY(X->ev0.create());
         HIP_TRY(X->ev1.create());
         HIP_TRY(hipDeviceGetAttribute(&X->n_cus, hipDeviceAttributeMultiprocessorCount, S->device));
@@ -179,7 +180,7 @@ int trace_enqueue(crt_scene* S, const crt_ray* d_rays, int64_t n, const crt_trac
         return set_error(CRT_ERR_INVALID_ARGUMENT, "ray and hit arrays must be 16-byte aligned");
     HIP_TRY(hipSetDevice(S->device));
     TraceScratch* X = nullptr;
-    if (int rc = trace_scratch(S, &X)) return rc;
+    if (int rc = trace_scratch(S, st, &X)) return rc;
     const bool cnt = (flags & CRT_TRACE_COUNT_WORK) != 0;
 
     TraceParams T{};
@@ -270,7 +271,10 @@ int trace_take_error(TraceScratch* X) {
     unsigned long long word = 0;
     HIP_TRY(hipMemcpy(&word, X->d_stats.get() + TRACE_ERR_WORD, sizeof word, hipMemcpyDeviceToHost));
     if (!word) return CRT_OK;
+    // the callers waited for their stream before this read; the clear is a null-stream operation and is waited for, so
+    // that a query the caller enqueues next on any stream cannot have its report cleared
     HIP_TRY(hipMemset(X->d_stats.get() + TRACE_ERR_WORD, 0, sizeof word));
+    HIP_TRY(hipStreamSynchronize(0));
     std::string m = "trace kernel reported an internal error:";
     if (word & 1u) m += " primitive index out of range;";
     if (word & 2u) m += " traversal stack deeper than the scene's stack bound (entries dropped);";
@@ -288,7 +292,7 @@ int trace_host(const crt_scene* Sc, const crt_ray* rays, int64_t n, const crt_tr
     crt_scene* S = const_cast<crt_scene*>(Sc);   // the scratch belongs to the handle (handles are not thread-safe)
     HIP_TRY(hipSetDevice(S->device));
     TraceScratch* X = nullptr;
-    if (int rc = trace_scratch(S, &X)) return rc;
+    if (int rc = trace_scratch(S, 0, &X)) return rc;
     const int64_t chunk = std::min(n, TRACE_STAGE_RAYS);
     const size_t c = (size_t)chunk;
     if (c > X->d_rays.size() || c > X->d_hits.size() || c > X->d_occ.size()) {   // the three grow together

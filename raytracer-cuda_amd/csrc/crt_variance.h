@@ -133,7 +133,7 @@ int crt_selftest_denoise_variance(crt_renderer* R, const float* history, const f
     if (int rc = variance_check_options(o, "selftest denoise variance")) return rc;
     HIP_TRY(hipSetDevice(R->device));
     DenoiseState* N = nullptr;
-    if (int rc = denoise_state(R, &N)) return rc;
+    if (int rc = denoise_state(R, 0, &N)) return rc;
     ReprojectState* S = nullptr;
     if (int rc = reproject_state(R, &S)) return rc;
     VarianceState* V = nullptr;

@@ -2,6 +2,7 @@
 the loop of Scene.trace and paths.advance that runs until the count is 0, and by one paths.finish call."""
 import numpy as np
 
+import stream_gate
 import wavefront_batches as wb
 from crt_amd import _lib, paths
 
@@ -60,14 +61,18 @@ def loop(b, scene, rays, pth, rem, max_bounces=BOUNCES, **opts):
 
 def finish(b, scene, rays, pth, rem, count=None, totals=(0, 0), max_bounces=BOUNCES, stream_count=False):
     """One paths.finish.  count: the value of count_in as an int32 (None: no count_in); stream_count: the count is produced by a
-    kernel on a side stream just before the call, which then runs on that stream."""
+    kernel on a side stream just before the call, which then runs on that stream; the stream is held back first
+    (stream_gate), and the batch is copied on it behind the gate."""
     import torch
     s = State(b, rays, pth, rem)
     t = torch.tensor(list(totals), dtype=torch.int64, device="cuda:0")
     if stream_count:
-        side = torch.cuda.Stream()
+        side = stream_gate.side_stream()
+        torch.cuda.synchronize()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
+            stream_gate.gate(side)
+            s.rays, s.pth = s.rays.clone(), s.pth.clone()
             c = torch.zeros((1,), dtype=torch.int32, device="cuda:0") + count
             res = scene.path_finish(b.r, s.rays, s.pth, max_bounces, s.rem, rng=s.rng, linear=s.lin, count_in=c, totals=t)
         side.synchronize()

@@ -28,6 +28,7 @@ from crt_amd import _lib, paths
 
 sys.path.insert(0, str(Path(__file__).resolve().parent / "helpers"))
 import custom_scene  # noqa: E402
+import stream_gate  # noqa: E402
 import wavefront_batches as wb  # noqa: E402
 from wavefront_batches import H, W, bits, same  # noqa: E402
 
@@ -160,8 +161,12 @@ def test_count_is_read_on_the_stream(batches, bunny_w4, query):
     flags = torch.zeros((N,), dtype=torch.int32, device="cuda:0")
     flags[:1025] = 1
     torch.cuda.synchronize()
-    side = torch.cuda.Stream()
+    side = stream_gate.side_stream()
+    source, rays = rays, torch.zeros_like(rays)             # what a query on another stream would trace
+    torch.cuda.synchronize()
     with torch.cuda.stream(side):
+        stream_gate.gate(side)
+        rays.copy_(source)                                   # the rays arrive on this stream, behind the gate
         count = torch.zeros((1,), dtype=torch.int32, device="cuda:0")
         out = torch.full((N, 8), SENTINEL, dtype=torch.int32, device="cuda:0")
         count += flags.sum().to(torch.int32)
@@ -216,12 +221,17 @@ def test_indirect_advance(batches, world, pattern):
 
 
 # ------------------------------------------------------------------------------------------ 4. chains without host reads
-def _chain(scene, r, rng0, iterations, indirect, opts):
+def _chain(scene, r, rng0, iterations, indirect, opts, gated=False):
     """Camera rays, then `iterations` rounds of trace and advance on ping-pong batches and the caller's own state, 3
     more samples per pixel.  indirect: every size comes from the device and nothing is read back before the end;
-    otherwise the direct calls with int(count) between them, which stop when no entry is left."""
+    otherwise the direct calls with int(count) between them, which stop when no entry is left.  gated: the current
+    stream is held back first (helpers/stream_gate.py), and the state and the first count are made on it behind the gate."""
     import torch
-    rng = dev(rng0.view(np.int32))
+    rng, first_count = dev(rng0.view(np.int32)), count_tensor(N)
+    if gated:
+        torch.cuda.synchronize()
+        stream_gate.gate(torch.cuda.current_stream())
+        rng, first_count = rng.clone(), first_count.clone()
     lin = torch.zeros((N, 3), dtype=torch.float32, device="cuda:0")
     rem = torch.full((N,), 3, dtype=torch.int32, device="cuda:0")
     totals = torch.zeros((2,), dtype=torch.int64, device="cuda:0")
@@ -229,7 +239,7 @@ def _chain(scene, r, rng0, iterations, indirect, opts):
     batch = [crt_amd.camera_rays(r, rng=rng), (torch.empty((N, 8), dtype=torch.float32, device="cuda:0"),
                                                torch.empty((N, 8), dtype=torch.int32, device="cuda:0"))]
     hits = torch.empty((N, 8), dtype=torch.float32, device="cuda:0")
-    count, m, cur, done = count_tensor(N), N, 0, 0
+    count, m, cur, done = first_count, N, 0, 0
     for _ in range(iterations):
         rays, pth = batch[cur]
         if indirect:
@@ -482,15 +492,18 @@ def test_side_stream(bunny_w4, chain_state):
     opts = dict(mode=2, grid_waves=8)
     base = _chain(bunny_w4, r, rng0, 6, True, opts)
     torch.cuda.synchronize()
-    side = torch.cuda.Stream()
+    side = stream_gate.side_stream()
     with torch.cuda.stream(side):
         assert torch.cuda.current_stream() == side and side != torch.cuda.default_stream()
-        got = _chain(bunny_w4, r, rng0, 6, True, opts)
+        got = _chain(bunny_w4, r, rng0, 6, True, opts, gated=True)
     wb.assert_equal_results(got, base, "side stream")
     assert got["totals"] == base["totals"] and base["totals"] == [6 * N, 6] and base["lin"].any()
     # the library's loop on a side stream
     a, b = wb.renderer(crt_amd.camera(4)), wb.renderer(crt_amd.camera(4))
+    b.init_rand(7)                                          # what a loop on another stream would start from
     torch.cuda.synchronize()
+    stream_gate.gate(side)
+    b.init_rand(41, stream=side.cuda_stream)                # a's state, made on the side stream behind the gate
     res = [a.render_wavefront(bunny_w4, 4, 20, sync_every=3),
            b.render_wavefront(bunny_w4, 4, 20, sync_every=3, stream=side.cuda_stream)]
     side.synchronize()

@@ -29,6 +29,7 @@ from crt_amd import _lib, paths
 
 sys.path.insert(0, str(Path(__file__).resolve().parent / "helpers"))
 import custom_scene  # noqa: E402
+import stream_gate  # noqa: E402
 import synth_scenes as synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -458,11 +459,16 @@ def test_hand_built_hits(device_scenes):
 
 
 # ------------------------------------------------------------------------------------------ 8. side stream
-def _fixed_rounds(scene, r, rng0, rounds):
+def _fixed_rounds(scene, r, rng0, rounds, gated=False):
     """camera rays and `rounds` trace / step rounds on the current stream, on the caller's own state tensors, without
-    compaction (ended entries stay in the batch and are skipped) and without any synchronisation."""
+    compaction (ended entries stay in the batch and are skipped) and without any synchronisation.  gated: the current
+    stream is held back first (helpers/stream_gate.py), and the state tensors are made on it behind the gate."""
     import torch
     rng = torch.from_numpy(rng0.view(np.int32).copy()).to("cuda:0", non_blocking=False)
+    if gated:
+        torch.cuda.synchronize()
+        stream_gate.gate(torch.cuda.current_stream())
+        rng = rng.clone()
     lin = torch.zeros((W * H, 3), dtype=torch.float32, device="cuda:0")
     stream = torch.cuda.current_stream()
     stream.wait_stream(torch.cuda.default_stream())
@@ -480,10 +486,10 @@ def test_side_stream(bunny_w4):
     rng0 = r.rng_state().reshape(-1, 6)
     base = _fixed_rounds(bunny_w4, r, rng0, 6)
     torch.cuda.synchronize()
-    side = torch.cuda.Stream()
+    side = stream_gate.side_stream()
     with torch.cuda.stream(side):
         assert torch.cuda.current_stream() == side and side != torch.cuda.default_stream()
-        got = _fixed_rounds(bunny_w4, r, rng0, 6)
+        got = _fixed_rounds(bunny_w4, r, rng0, 6, gated=True)
     side.synchronize()
     for a, b, k in zip(got, base, ("rays", "paths", "rng", "sums")):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32)), k

@@ -31,6 +31,7 @@ from crt_amd import _lib
 
 sys.path.insert(0, str(Path(__file__).resolve().parent / "helpers"))
 import custom_scene  # noqa: E402
+import stream_gate  # noqa: E402
 from bvh_emulation import _best, _is_sphere, _prim_ranks, _prim_t  # noqa: E402
 from custom_scene import world_offset  # noqa: E402
 from test_image_io import _decode_png  # noqa: E402
@@ -345,15 +346,22 @@ def test_occlusion(worlds, name, tree):
 def test_torch_tensors_on_a_side_stream(bunny):
     import torch
     sc, o, d, base = bunny
-    rays = torch.from_numpy(crt_amd.pack_rays(o, d)).to("cuda:0")
-    stream = torch.cuda.Stream()
+    source = torch.from_numpy(crt_amd.pack_rays(o, d)).to("cuda:0")
+    rays = torch.zeros_like(source)                            # what a query on another stream would trace
+    stream = stream_gate.side_stream()
+    torch.cuda.synchronize()
     stream.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(stream):
         assert torch.cuda.current_stream() == stream and stream != torch.cuda.default_stream()
+        stream_gate.gate(stream)
+        rays.copy_(source)                                     # the rays arrive on this stream, behind the gate
         hits = sc.trace(rays, mode=2, count_work=True)         # the stream kernel: the step counts are its own
         stats = sc.trace_stats()
         again = sc.trace(rays, mode=2, count_work=True)
         stats2 = sc.trace_stats()
+        rays.zero_()
+        stream_gate.gate(stream)                               # trace_stats waited: a gate again, and the rays behind it
+        rays.copy_(source)
         auto = sc.trace(rays)                                  # automatic: the lane kernel at this size
         occ = sc.occluded(rays, mode=2)
         occ1 = sc.occluded(rays, mode=1)

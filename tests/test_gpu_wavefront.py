@@ -29,6 +29,7 @@ from crt_amd import _lib, paths
 
 sys.path.insert(0, str(Path(__file__).resolve().parent / "helpers"))
 import custom_scene  # noqa: E402
+import stream_gate  # noqa: E402
 import wavefront_batches as wb  # noqa: E402
 from wavefront_batches import H, W, bits, same  # noqa: E402
 
@@ -361,12 +362,17 @@ def test_on_bounce_can_end_the_frame(frames):
 
 
 # ------------------------------------------------------------------------------------------ 5. side stream
-def _fixed_rounds(scene, r, rng0, rounds):
+def _fixed_rounds(scene, r, rng0, rounds, gated=False):
     """camera rays and `rounds` trace / advance rounds on the current stream, on the caller's own state tensors, without
     any synchronisation: every pixel has more samples left than rounds, so every round's count is the frame's pixels and
-    the next batch is the whole output pair."""
+    the next batch is the whole output pair.  gated: the current stream is held back first (helpers/stream_gate.py), and
+    the state tensors are made on it behind the gate."""
     import torch
     rng = torch.from_numpy(rng0.view(np.int32).copy()).to("cuda:0", non_blocking=False)
+    if gated:
+        torch.cuda.synchronize()
+        stream_gate.gate(torch.cuda.current_stream())
+        rng = rng.clone()
     lin = torch.zeros((W * H, 3), dtype=torch.float32, device="cuda:0")
     rem = torch.full((W * H,), rounds + 1, dtype=torch.int32, device="cuda:0")
     stream = torch.cuda.current_stream()
@@ -388,10 +394,10 @@ def test_side_stream(frames):
     rng0 = r.rng_state().reshape(-1, 6)
     base = _fixed_rounds(scene, r, rng0, 6)
     torch.cuda.synchronize()
-    side = torch.cuda.Stream()
+    side = stream_gate.side_stream()
     with torch.cuda.stream(side):
         assert torch.cuda.current_stream() == side and side != torch.cuda.default_stream()
-        got = _fixed_rounds(scene, r, rng0, 6)
+        got = _fixed_rounds(scene, r, rng0, 6, gated=True)
     side.synchronize()
     assert base[5].tolist() == [W * H] * 6 and got[5].tolist() == [W * H] * 6
     key = lambda t: wb.keyed(t[0].cpu().numpy(), t[1].cpu().numpy(), W * H)   # noqa: E731
