@@ -164,74 +164,158 @@ class DenoiseVarianceOptions(C.Structure):   # crt_hip.h crt_denoise_variance_op
 DENOISE_TILE_SCALE = 1               # crt_denoise_options.flags
 DENOISE_DIRECT_ONLY = 0x80000000     # measurement switch: every iteration through the direct kernel
 
-# exported symbol lists (checked by tests against include/*.h)
-HIP_SYMBOLS = [
-    "crt_abi_version", "crt_build_flags", "crt_last_error", "crt_device_count", "crt_scene_create", "crt_scene_create_ex", "crt_scene_get_stats", "crt_scene_compare", "crt_scene_compare_dump", "crt_scene_export",
-    "crt_renderer_set_stack_lds", "crt_renderer_get_section_profile", "crt_renderer_get_section_profile_ex",
-    "crt_scene_destroy", "crt_renderer_create", "crt_renderer_destroy", "crt_renderer_init_rand",
-    "crt_renderer_set_camera", "crt_renderer_render", "crt_renderer_resolve", "crt_renderer_render_frame",
-    "crt_renderer_synchronize", "crt_renderer_read_linear", "crt_renderer_read_rgba8", "crt_renderer_read_rng",
-    "crt_renderer_write_linear", "crt_renderer_get_counters", "crt_renderer_linear_device_ptr",
-    "crt_renderer_rgba_device_ptr", "crt_renderer_rng_device_ptr", "crt_renderer_last_kernel_ms",
-    "crt_renderer_last_kernel_name", "crt_renderer_last_timings", "crt_renderer_last_schedule", "crt_renderer_timing_history",
-    "crt_renderer_set_leaf_carry", "crt_renderer_set_xcd_regions", "crt_renderer_set_temporal_order",
-    "crt_renderer_set_drain_threshold", "crt_renderer_set_wave_drain",
-    "crt_renderer_attach_linear", "crt_renderer_set_kernel_variant", "crt_renderer_get_schedule_stats",
-    "crt_renderer_set_regen_threshold", "crt_renderer_set_occupancy_target",
-    "crt_build_mesh_bvh", "crt_renderer_set_schedule", "crt_renderer_set_critical_tiles", "crt_renderer_set_pixel_shard",
-    "crt_renderer_set_top_levels",
-    "crt_selftest_math", "crt_selftest_rng", "crt_selftest_geometry", "crt_selftest_scan", "crt_selftest_rcp",
-    "crt_selftest_uv_div", "crt_selftest_sqrt", "crt_selftest_unit",
-    "crt_trace_validate_rays", "crt_scene_export_identity", "crt_scene_trace", "crt_scene_occluded",
-    "crt_scene_trace_device", "crt_scene_trace_last_stats",
-    "crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
-    "crt_scene_path_advance_device", "crt_path_advance_entries", "crt_renderer_render_wavefront",
-    "crt_scene_trace_indirect_device", "crt_scene_path_advance_indirect_device", "crt_renderer_render_wavefront_queued",
-    "crt_scene_path_finish_device", "crt_renderer_render_wavefront_finish",
-    "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer",
-    "crt_renderer_render_adaptive", "crt_renderer_resolve_adaptive", "crt_renderer_read_tile_spp",
-    "crt_renderer_read_tile_error", "crt_renderer_read_adaptive_prev", "crt_selftest_adaptive_plan",
-    "crt_renderer_compute_guides", "crt_renderer_denoise", "crt_renderer_resolve_denoised",
-    "crt_renderer_read_denoised", "crt_renderer_read_guides", "crt_renderer_denoised_device_ptr", "crt_selftest_denoise",
-    "crt_renderer_denoise_iteration_ms", "crt_debug_live_allocations", "crt_renderer_last_launch_frozen",
-    "crt_renderer_reproject", "crt_renderer_reset_history", "crt_renderer_denoise_history", "crt_renderer_resolve_history",
-    "crt_renderer_read_history", "crt_renderer_history_device_ptr", "crt_selftest_reproject",
-    "crt_renderer_set_tail_fill", "crt_renderer_last_tail_fill", "crt_selftest_shade",
-    "crt_renderer_reproject_moments", "crt_renderer_read_moments", "crt_renderer_denoise_history_variance",
-    "crt_renderer_read_variance", "crt_selftest_reproject_moments", "crt_selftest_denoise_variance",
-]
-# Entries that joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, the
-# schedule self-tests, the path finish, adaptive sampling, the denoiser, the live-allocation count, then which twin of a
-# variant-8 kernel ran, then the reprojection, then variant 8's tail fill, then the material self-test, then the variance-guided filter): bound when the loaded
-# library has them, so an older build of the same ABI still loads; their Python front-ends raise CrtError through
-# require() otherwise.
-OPTIONAL_SYMBOLS = ("crt_renderer_camera_rays_device", "crt_scene_path_step_device", "crt_scene_export_shade_rows",
-                    "crt_scene_path_advance_device", "crt_path_advance_entries", "crt_renderer_render_wavefront",
-                    "crt_scene_trace_indirect_device", "crt_scene_path_advance_indirect_device",
-                    "crt_renderer_render_wavefront_queued",
-                    "crt_scene_path_finish_device", "crt_renderer_render_wavefront_finish",
-                    "crt_selftest_tile_schedule", "crt_selftest_pixel_order", "crt_selftest_schedule_buffer",
-                    "crt_renderer_render_adaptive", "crt_renderer_resolve_adaptive", "crt_renderer_read_tile_spp",
-                    "crt_renderer_read_tile_error", "crt_renderer_read_adaptive_prev", "crt_selftest_adaptive_plan",
-                    "crt_renderer_compute_guides", "crt_renderer_denoise", "crt_renderer_resolve_denoised",
-                    "crt_renderer_read_denoised", "crt_renderer_read_guides", "crt_renderer_denoised_device_ptr",
-                    "crt_selftest_denoise", "crt_renderer_denoise_iteration_ms", "crt_debug_live_allocations",
-                    "crt_renderer_last_launch_frozen",
-                    "crt_renderer_reproject", "crt_renderer_reset_history", "crt_renderer_denoise_history",
-                    "crt_renderer_resolve_history", "crt_renderer_read_history", "crt_renderer_history_device_ptr",
-                    "crt_selftest_reproject",
-                    "crt_renderer_set_tail_fill", "crt_renderer_last_tail_fill", "crt_selftest_shade",
-                    "crt_renderer_reproject_moments", "crt_renderer_read_moments",
-                    "crt_renderer_denoise_history_variance", "crt_renderer_read_variance",
-                    "crt_selftest_reproject_moments", "crt_selftest_denoise_variance")
+_P, _i32, _u32, _i64, _u64, _f32 = C.c_void_p, C.c_int, C.c_uint32, C.c_int64, C.c_ulonglong, C.c_float
 
-HOST_SYMBOLS = [
-    "crth_scene_load", "crth_scene_load_ex", "crth_scene_build_ms", "crth_scene_destroy", "crth_scene_desc", "crth_scene_upload", "crth_scene_upload_ex", "crth_scene_counts",
-    "crth_scene_loader_arrays", "crth_camera", "crth_last_error", "crth_encode_image", "crth_write_image",
-    "crth_build_mesh_bvh", "crth_camera_create", "crth_camera_update", "crth_camera_get", "crth_camera_destroy",
-    "crth_viewer_create", "crth_viewer_frame", "crth_viewer_camera", "crth_viewer_renderer", "crth_viewer_destroy",
-    "crth_viewer_set_reproject", "crth_viewer_set_denoise_variance",
-]
+# Every entry of libcrt_hip.so, named here and nowhere else: name -> (argtypes, restype, optional).  hip() binds from this
+# table and the exported symbol lists below are read off it (tests check them against include/*.h).  optional: the entry
+# joined ABI version 3 after its first release (the path steps, the path queues, the indirect calls, the schedule
+# self-tests, the path finish, adaptive sampling, the denoiser, the live-allocation count, which twin of a variant-8 kernel
+# ran, the reprojection, variant 8's tail fill, the material self-test, the variance-guided filter): bound when the loaded
+# library has it, so an older build of the same ABI still loads; its Python front-end raises CrtError through require().
+HIP_SIG = {
+    "crt_abi_version": ([], _i32, False),
+    "crt_build_flags": ([], _i32, False),
+    "crt_last_error": ([], C.c_char_p, False),
+    "crt_device_count": ([_P], _i32, False),
+    "crt_scene_create": ([_P, _i32, _P], _i32, False),
+    "crt_scene_create_ex": ([_P, _i32, _P, _P], _i32, False),
+    "crt_scene_get_stats": ([_P, _P], _i32, False),
+    "crt_scene_compare": ([_P, _P, _P, _i32, _i32, _P], _i32, False),
+    "crt_scene_compare_dump": ([_P, _P, _P, _i32, _i32, _P, _P, _i32], _i32, False),
+    "crt_scene_export": ([_P, _P, _P, _P, _P, _P], _i32, False),
+    "crt_renderer_set_stack_lds": ([_P, _i32], _i32, False),
+    "crt_renderer_get_section_profile": ([_P, _P], _i32, False),
+    "crt_renderer_get_section_profile_ex": ([_P, _P, _i32], _i32, False),
+    "crt_scene_destroy": ([_P], None, False),
+    "crt_renderer_create": ([_i32, _i32, _i32, _P], _i32, False),
+    "crt_renderer_destroy": ([_P], None, False),
+    "crt_renderer_init_rand": ([_P, _u64, _u64, _P], _i32, False),
+    "crt_renderer_set_camera": ([_P, _P], _i32, False),
+    "crt_renderer_render": ([_P, _P, _i32, _i32, C.c_uint, _P], _i32, False),
+    "crt_renderer_resolve": ([_P, _f32, _P], _i32, False),
+    "crt_renderer_render_frame": ([_P, _P, _P], _i32, False),
+    "crt_renderer_synchronize": ([_P, _P], _i32, False),
+    "crt_renderer_read_linear": ([_P, _P], _i32, False),
+    "crt_renderer_read_rgba8": ([_P, _P], _i32, False),
+    "crt_renderer_read_rng": ([_P, _P], _i32, False),
+    "crt_renderer_write_linear": ([_P, _P], _i32, False),
+    "crt_renderer_get_counters": ([_P, _P], _i32, False),
+    "crt_renderer_linear_device_ptr": ([_P], _P, False),
+    "crt_renderer_rgba_device_ptr": ([_P], _P, False),
+    "crt_renderer_rng_device_ptr": ([_P], _P, False),
+    "crt_renderer_last_kernel_ms": ([_P], _f32, False),
+    "crt_renderer_last_kernel_name": ([_P], C.c_char_p, False),
+    "crt_renderer_last_timings": ([_P, _P], _i32, False),
+    "crt_renderer_last_schedule": ([_P, _P], _i32, False),
+    "crt_renderer_timing_history": ([_P, _i32, _P], _i32, False),
+    "crt_renderer_set_leaf_carry": ([_P, _i32, _i32], _i32, False),
+    "crt_renderer_set_xcd_regions": ([_P, _i32], _i32, False),
+    "crt_renderer_set_temporal_order": ([_P, _i32], _i32, False),
+    "crt_renderer_set_drain_threshold": ([_P, _i32], _i32, False),
+    "crt_renderer_set_wave_drain": ([_P, _i32], _i32, False),
+    "crt_renderer_attach_linear": ([_P, _P], _i32, False),
+    "crt_renderer_set_kernel_variant": ([_P, _i32], _i32, False),
+    "crt_renderer_get_schedule_stats": ([_P, _P], _i32, False),
+    "crt_renderer_set_regen_threshold": ([_P, _i32], _i32, False),
+    "crt_renderer_set_occupancy_target": ([_P, _i32], _i32, False),
+    "crt_build_mesh_bvh": ([_i32, _P, _u32, _P, _P, _u32, _P, _P, _P, _P], _i32, False),
+    "crt_renderer_set_schedule": ([_P, _i32, _i32, _i32], _i32, False),
+    "crt_renderer_set_critical_tiles": ([_P, _i32, _i32], _i32, False),
+    "crt_renderer_set_pixel_shard": ([_P, _i32, _i32], _i32, False),
+    "crt_renderer_set_top_levels": ([_P, _i32], _i32, False),
+    "crt_selftest_math": ([_P, _P, _i32, _P, _P], _i32, False),
+    "crt_selftest_rng": ([_u64, _P, _i32, _i32, _P, _P], _i32, False),
+    "crt_selftest_geometry": ([_i32, _P, _i32, _P, _i32, _i32, _P, _P], _i32, False),
+    "crt_selftest_scan": ([_P, _i32, _P], _i32, False),
+    "crt_selftest_rcp": ([_u32, _u32, _P, _P], _i32, False),
+    "crt_selftest_uv_div": ([_i32, _P], _i32, False),
+    "crt_selftest_sqrt": ([_u32, _u32, _P, _P], _i32, False),
+    "crt_selftest_unit": ([_P, _i32, _P], _i32, False),
+    "crt_trace_validate_rays": ([_P, _i64, _P], _i32, False),
+    "crt_scene_export_identity": ([_P, _P, _P, _P], _i32, False),
+    "crt_scene_trace": ([_P, _P, _i64, _P, _P], _i32, False),
+    "crt_scene_occluded": ([_P, _P, _i64, _P, _P], _i32, False),
+    "crt_scene_trace_device": ([_P, _P, _i64, _P, _P, _P, C.c_uint, _P], _i32, False),
+    "crt_scene_trace_last_stats": ([_P, _P], _i32, False),
+    "crt_renderer_camera_rays_device": ([_P, _P, _i64, _P, _P, _P, _P], _i32, True),
+    "crt_scene_path_step_device": ([_P, _P, _P, _P, _i64, _i32, _P, _P, _i64, _P], _i32, True),
+    "crt_scene_export_shade_rows": ([_P, _P, _P], _i32, True),
+    "crt_scene_path_advance_device": ([_P, _P, _P, _P, _P, _i64, _i32, _P, _P, _P, _P, _P, _P, _P], _i32, True),
+    "crt_path_advance_entries": ([], _i32, True),
+    "crt_renderer_render_wavefront": ([_P, _P, _i32, _i32, C.c_uint, _P, _P, _P], _i32, True),
+    "crt_scene_trace_indirect_device": ([_P, _P, _P, _i64, _P, _P, _P, C.c_uint, _P], _i32, True),
+    "crt_scene_path_advance_indirect_device": ([_P, _P, _P, _P, _P, _P, _i64, _i32, _P, _P, _P, _P, _P, _P, _P, _P], _i32, True),
+    "crt_renderer_render_wavefront_queued": ([_P, _P, _i32, _i32, C.c_uint, _P, _i32, _P, _P], _i32, True),
+    "crt_scene_path_finish_device": ([_P, _P, _P, _P, _P, _i64, _i32, _P, _P, _P, _P, _P], _i32, True),
+    "crt_renderer_render_wavefront_finish": ([_P, _P, _i32, _i32, C.c_uint, _P, _i32, _i64, _P, _P], _i32, True),
+    "crt_selftest_tile_schedule": ([_P, _P, _i32, _i32, _i32, _i32, _i32, _P], _i32, True),
+    "crt_selftest_pixel_order": ([_P, _i32, _P, _i32, _i32], _i32, True),
+    "crt_selftest_schedule_buffer": ([_P, _i32, _P, _i64, _P], _i32, True),
+    "crt_renderer_render_adaptive": ([_P, _P, _P, _i32, C.c_uint, _P, _P], _i32, True),
+    "crt_renderer_resolve_adaptive": ([_P, _P], _i32, True),
+    "crt_renderer_read_tile_spp": ([_P, _P], _i32, True),
+    "crt_renderer_read_tile_error": ([_P, _P], _i32, True),
+    "crt_renderer_read_adaptive_prev": ([_P, _P], _i32, True),
+    "crt_selftest_adaptive_plan": ([_P, _P, _P, _P, _i32, _i32, _f32, _P, _P], _i32, True),
+    "crt_renderer_compute_guides": ([_P, _P, _P, _P], _i32, True),
+    "crt_renderer_denoise": ([_P, _P, _f32, _P, _P], _i32, True),
+    "crt_renderer_resolve_denoised": ([_P, _P], _i32, True),
+    "crt_renderer_read_denoised": ([_P, _P], _i32, True),
+    "crt_renderer_read_guides": ([_P, _P], _i32, True),
+    "crt_renderer_denoised_device_ptr": ([_P], _P, True),
+    "crt_selftest_denoise": ([_P, _P, _P, _P, _P], _i32, True),
+    "crt_renderer_denoise_iteration_ms": ([_P, _P], _i32, True),
+    "crt_debug_live_allocations": ([_P, _P], _i32, True),
+    "crt_renderer_last_launch_frozen": ([_P], _i32, True),
+    "crt_renderer_reproject": ([_P, _P, _f32, _P, _P], _i32, True),
+    "crt_renderer_reset_history": ([_P], _i32, True),
+    "crt_renderer_denoise_history": ([_P, _P, _P, _P], _i32, True),
+    "crt_renderer_resolve_history": ([_P, _P], _i32, True),
+    "crt_renderer_read_history": ([_P, _P], _i32, True),
+    "crt_renderer_history_device_ptr": ([_P], _P, True),
+    "crt_selftest_reproject": ([_P, _P, _P, _P, _P, _P, _P, _P], _i32, True),
+    "crt_renderer_set_tail_fill": ([_P, _i32, _i32], _i32, True),
+    "crt_renderer_last_tail_fill": ([_P, _P], _i32, True),
+    "crt_selftest_shade": ([_P, _i32, _P], _i32, True),
+    "crt_renderer_reproject_moments": ([_P, _P, _f32, _P, _P], _i32, True),
+    "crt_renderer_read_moments": ([_P, _P], _i32, True),
+    "crt_renderer_denoise_history_variance": ([_P, _P, _P, _P], _i32, True),
+    "crt_renderer_read_variance": ([_P, _P], _i32, True),
+    "crt_selftest_reproject_moments": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _i32, True),
+    "crt_selftest_denoise_variance": ([_P, _P, _P, _P, _P, _P, _P], _i32, True),
+}
+HIP_SYMBOLS = list(HIP_SIG)
+OPTIONAL_SYMBOLS = tuple(name for name, sig in HIP_SIG.items() if sig[2])
+
+# Every entry of libcrt_host.so: name -> (argtypes, restype).
+HOST_SIG = {
+    "crth_scene_load": ([_P, _i32, _P], _i32),
+    "crth_scene_load_ex": ([_P, _i32, _i32, _P], _i32),
+    "crth_scene_build_ms": ([_P], C.c_double),
+    "crth_scene_destroy": ([_P], None),
+    "crth_scene_desc": ([_P, _P], _i32),
+    "crth_scene_upload": ([_P, _i32, _P], _i32),
+    "crth_scene_upload_ex": ([_P, _i32, _P, _P], _i32),
+    "crth_scene_counts": ([_P, _P], _i32),
+    "crth_scene_loader_arrays": ([_P, _P, _P, _P, _P, _P], _i32),
+    "crth_camera": ([_f32, _f32, _P, _P, _f32, _f32, _f32, _f32, _i32, _P], _i32),
+    "crth_last_error": ([], C.c_char_p),
+    "crth_encode_image": ([_i32, _P, _i32, _i32, _i32, _P, _P], _i32),
+    "crth_write_image": ([C.c_char_p, _P, _i32, _i32, _i32], _i32),
+    "crth_build_mesh_bvh": ([_P, _u32, _P, _P, _u32, _P, _P, _P], _i32),
+    "crth_camera_create": ([_f32, _f32, _P, _P, _f32, _f32, _P], _i32),
+    "crth_camera_update": ([_P, _f32, _i32, _i32, _P], _i32),
+    "crth_camera_get": ([_P, _P, _P], _i32),
+    "crth_camera_destroy": ([_P], None),
+    "crth_viewer_create": ([_P, _i32, _i32, _P, _i32, _i32, _f32, _f32, _f32, _P, _f32, _u64, _i32, _P], _i32),
+    "crth_viewer_frame": ([_P, _f32, _P, _P], _i32),
+    "crth_viewer_camera": ([_P, _P], _i32),
+    "crth_viewer_renderer": ([_P], _P),
+    "crth_viewer_destroy": ([_P], None),
+    "crth_viewer_set_reproject": ([_P, _P, _P], _i32),
+    "crth_viewer_set_denoise_variance": ([_P, _P], _i32),
+}
+HOST_SYMBOLS = list(HOST_SIG)
 
 _hip = None
 _host = None
@@ -252,6 +336,17 @@ def _bind_single_runtime() -> None:
         pass
 
 
+def _bind(L, table, may_lack=()) -> None:
+    """Give L's entries the argtypes and restype of `table`.  Those in `may_lack` may be absent (an older build of this ABI
+    version: require() reports one when it is used), and any under CRT_SKIP_ABI_CHECK (an A/B build of an older revision)."""
+    any_absent = bool(os.environ.get("CRT_SKIP_ABI_CHECK"))
+    for name, sig in table.items():
+        if (any_absent or name in may_lack) and not hasattr(L, name):
+            continue
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = sig[0], sig[1]
+
+
 def hip():
     global _hip
     if _hip is None:
@@ -259,112 +354,7 @@ def hip():
         if not HIP_LIB.exists():
             raise CrtError(f"{HIP_LIB} not built (run `make -C {PKG_ROOT}` or __graft_entry__.build())")
         L = C.CDLL(str(HIP_LIB), mode=C.RTLD_GLOBAL)
-        P, i32, u64, f32 = C.c_void_p, C.c_int, C.c_ulonglong, C.c_float
-        sig = {
-            "crt_abi_version": ([], i32), "crt_build_flags": ([], i32), "crt_last_error": ([], C.c_char_p),
-            "crt_device_count": ([P], i32),
-            "crt_scene_create": ([P, i32, P], i32), "crt_scene_create_ex": ([P, i32, P, P], i32),
-            "crt_scene_compare": ([P, P, P, i32, i32, P], i32),
-            "crt_scene_compare_dump": ([P, P, P, i32, i32, P, P, i32], i32),
-            "crt_scene_export": ([P, P, P, P, P, P], i32), "crt_renderer_set_stack_lds": ([P, i32], i32),
-            "crt_renderer_get_section_profile": ([P, P], i32),
-            "crt_renderer_get_section_profile_ex": ([P, P, i32], i32),
-            "crt_scene_get_stats": ([P, P], i32),
-            "crt_scene_destroy": ([P], None),
-            "crt_renderer_create": ([i32, i32, i32, P], i32), "crt_renderer_destroy": ([P], None),
-            "crt_renderer_init_rand": ([P, u64, u64, P], i32), "crt_renderer_set_camera": ([P, P], i32),
-            "crt_renderer_render": ([P, P, i32, i32, C.c_uint, P], i32),
-            "crt_renderer_resolve": ([P, f32, P], i32), "crt_renderer_render_frame": ([P, P, P], i32),
-            "crt_renderer_set_pixel_shard": ([P, i32, i32], i32),
-            "crt_renderer_synchronize": ([P, P], i32), "crt_renderer_last_timings": ([P, P], i32), "crt_renderer_last_schedule": ([P, P], i32),
-            "crt_renderer_timing_history": ([P, i32, P], i32),
-            "crt_renderer_set_leaf_carry": ([P, i32, i32], i32),
-            "crt_renderer_set_xcd_regions": ([P, i32], i32),
-            "crt_renderer_set_temporal_order": ([P, i32], i32),
-            "crt_renderer_set_drain_threshold": ([P, i32], i32),
-            "crt_renderer_set_wave_drain": ([P, i32], i32),
-            "crt_renderer_read_linear": ([P, P], i32), "crt_renderer_read_rgba8": ([P, P], i32),
-            "crt_renderer_read_rng": ([P, P], i32), "crt_renderer_write_linear": ([P, P], i32),
-            "crt_renderer_get_counters": ([P, P], i32),
-            "crt_renderer_linear_device_ptr": ([P], P), "crt_renderer_rgba_device_ptr": ([P], P),
-            "crt_renderer_rng_device_ptr": ([P], P), "crt_renderer_last_kernel_ms": ([P], f32),
-            "crt_renderer_last_kernel_name": ([P], C.c_char_p),
-            "crt_renderer_attach_linear": ([P, P], i32),
-            "crt_renderer_set_kernel_variant": ([P, i32], i32),
-            "crt_renderer_get_schedule_stats": ([P, P], i32),
-            "crt_renderer_set_regen_threshold": ([P, i32], i32),
-            "crt_renderer_set_occupancy_target": ([P, i32], i32),
-            "crt_renderer_set_schedule": ([P, i32, i32, i32], i32),
-            "crt_renderer_set_critical_tiles": ([P, i32, i32], i32),
-            "crt_renderer_set_top_levels": ([P, i32], i32),
-            "crt_build_mesh_bvh": ([i32, P, C.c_uint32, P, P, C.c_uint32, P, P, P, P], i32),
-            "crt_selftest_math": ([P, P, i32, P, P], i32),
-            "crt_selftest_geometry": ([i32, P, i32, P, i32, i32, P, P], i32),
-            "crt_selftest_rng": ([u64, P, i32, i32, P, P], i32),
-            "crt_selftest_scan": ([P, i32, P], i32),
-            "crt_selftest_rcp": ([C.c_uint32, C.c_uint32, P, P], i32),
-            "crt_selftest_uv_div": ([i32, P], i32),
-            "crt_selftest_sqrt": ([C.c_uint32, C.c_uint32, P, P], i32),
-            "crt_selftest_unit": ([P, i32, P], i32),
-            "crt_trace_validate_rays": ([P, C.c_int64, P], i32),
-            "crt_scene_export_identity": ([P, P, P, P], i32),
-            "crt_scene_trace": ([P, P, C.c_int64, P, P], i32),
-            "crt_scene_occluded": ([P, P, C.c_int64, P, P], i32),
-            "crt_scene_trace_device": ([P, P, C.c_int64, P, P, P, C.c_uint, P], i32),
-            "crt_scene_trace_last_stats": ([P, P], i32),
-            "crt_renderer_camera_rays_device": ([P, P, C.c_int64, P, P, P, P], i32),
-            "crt_scene_path_step_device": ([P, P, P, P, C.c_int64, i32, P, P, C.c_int64, P], i32),
-            "crt_scene_export_shade_rows": ([P, P, P], i32),
-            "crt_scene_path_advance_device": ([P, P, P, P, P, C.c_int64, i32, P, P, P, P, P, P, P], i32),
-            "crt_path_advance_entries": ([], i32),
-            "crt_renderer_render_wavefront": ([P, P, i32, i32, C.c_uint, P, P, P], i32),
-            "crt_scene_trace_indirect_device": ([P, P, P, C.c_int64, P, P, P, C.c_uint, P], i32),
-            "crt_scene_path_advance_indirect_device": ([P, P, P, P, P, P, C.c_int64, i32, P, P, P, P, P, P, P, P], i32),
-            "crt_renderer_render_wavefront_queued": ([P, P, i32, i32, C.c_uint, P, i32, P, P], i32),
-            "crt_scene_path_finish_device": ([P, P, P, P, P, C.c_int64, i32, P, P, P, P, P], i32),
-            "crt_renderer_render_wavefront_finish": ([P, P, i32, i32, C.c_uint, P, i32, C.c_int64, P, P], i32),
-            "crt_selftest_tile_schedule": ([P, P, i32, i32, i32, i32, i32, P], i32),
-            "crt_selftest_pixel_order": ([P, i32, P, i32, i32], i32),
-            "crt_selftest_schedule_buffer": ([P, i32, P, C.c_int64, P], i32),
-            "crt_renderer_render_adaptive": ([P, P, P, i32, C.c_uint, P, P], i32),
-            "crt_renderer_resolve_adaptive": ([P, P], i32),
-            "crt_renderer_read_tile_spp": ([P, P], i32), "crt_renderer_read_tile_error": ([P, P], i32),
-            "crt_renderer_read_adaptive_prev": ([P, P], i32),
-            "crt_selftest_adaptive_plan": ([P, P, P, P, i32, i32, f32, P, P], i32),
-            "crt_renderer_compute_guides": ([P, P, P, P], i32),
-            "crt_renderer_denoise": ([P, P, f32, P, P], i32),
-            "crt_renderer_resolve_denoised": ([P, P], i32),
-            "crt_renderer_read_denoised": ([P, P], i32), "crt_renderer_read_guides": ([P, P], i32),
-            "crt_renderer_denoised_device_ptr": ([P], P),
-            "crt_selftest_denoise": ([P, P, P, P, P], i32),
-            "crt_renderer_denoise_iteration_ms": ([P, P], i32),
-            "crt_debug_live_allocations": ([P, P], i32),
-            "crt_renderer_last_launch_frozen": ([P], i32),
-            "crt_renderer_set_tail_fill": ([P, i32, i32], i32),
-            "crt_renderer_last_tail_fill": ([P, P], i32),
-            "crt_renderer_reproject": ([P, P, f32, P, P], i32),
-            "crt_renderer_reset_history": ([P], i32),
-            "crt_renderer_denoise_history": ([P, P, P, P], i32),
-            "crt_renderer_resolve_history": ([P, P], i32),
-            "crt_renderer_read_history": ([P, P], i32),
-            "crt_renderer_history_device_ptr": ([P], P),
-            "crt_selftest_reproject": ([P, P, P, P, P, P, P, P], i32),
-            "crt_selftest_shade": ([P, i32, P], i32),
-            "crt_renderer_reproject_moments": ([P, P, f32, P, P], i32),
-            "crt_renderer_read_moments": ([P, P], i32),
-            "crt_renderer_denoise_history_variance": ([P, P, P, P], i32),
-            "crt_renderer_read_variance": ([P, P], i32),
-            "crt_selftest_reproject_moments": ([P, P, P, P, P, P, P, P, P, P], i32),
-            "crt_selftest_denoise_variance": ([P, P, P, P, P, P, P], i32),
-        }
-        for name, (args, res) in sig.items():
-            if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):
-                continue   # an A/B build of an older revision: self-tests added since then are absent
-            if name in OPTIONAL_SYMBOLS and not hasattr(L, name):
-                continue   # an older build of this ABI version: require() reports the missing entry when it is used
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = res
+        _bind(L, HIP_SIG, OPTIONAL_SYMBOLS)
         # every library is checked, CRT_HIP_LIB overrides included (a stale build would silently misread newer
         # fields); A/B runs against an older revision's build opt out explicitly with CRT_SKIP_ABI_CHECK=1
         if L.crt_abi_version() != ABI_VERSION and not os.environ.get("CRT_SKIP_ABI_CHECK"):
@@ -381,33 +371,7 @@ def host():
         if not HOST_LIB.exists():
             raise CrtError(f"{HOST_LIB} not built")
         L = C.CDLL(str(HOST_LIB))
-        P, i32, f32 = C.c_void_p, C.c_int, C.c_float
-        sig = {
-            "crth_scene_load": ([P, i32, P], i32), "crth_scene_load_ex": ([P, i32, i32, P], i32),
-            "crth_scene_build_ms": ([P], C.c_double), "crth_scene_destroy": ([P], None),
-            "crth_scene_desc": ([P, P], i32), "crth_scene_upload": ([P, i32, P], i32),
-            "crth_scene_upload_ex": ([P, i32, P, P], i32),
-            "crth_scene_counts": ([P, P], i32), "crth_scene_loader_arrays": ([P, P, P, P, P, P], i32),
-            "crth_camera": ([f32, f32, P, P, f32, f32, f32, f32, i32, P], i32),
-            "crth_last_error": ([], C.c_char_p),
-            "crth_encode_image": ([i32, P, i32, i32, i32, P, P], i32),
-            "crth_write_image": ([C.c_char_p, P, i32, i32, i32], i32),
-            "crth_camera_create": ([f32, f32, P, P, f32, f32, P], i32),
-            "crth_build_mesh_bvh": ([P, C.c_uint32, P, P, C.c_uint32, P, P, P], i32),
-            "crth_camera_update": ([P, f32, i32, i32, P], i32),
-            "crth_camera_get": ([P, P, P], i32), "crth_camera_destroy": ([P], None),
-            "crth_viewer_create": ([P, i32, i32, P, i32, i32, f32, f32, f32, P, f32, C.c_ulonglong, i32, P], i32),
-            "crth_viewer_frame": ([P, f32, P, P], i32), "crth_viewer_camera": ([P, P], i32),
-            "crth_viewer_renderer": ([P], P), "crth_viewer_destroy": ([P], None),
-            "crth_viewer_set_reproject": ([P, P, P], i32),
-            "crth_viewer_set_denoise_variance": ([P, P], i32),
-        }
-        for name, (args, res) in sig.items():
-            if os.environ.get("CRT_SKIP_ABI_CHECK") and not hasattr(L, name):
-                continue   # an A/B build of an older revision (CRT_HOST_LIB): entries added since then are absent
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = res
+        _bind(L, HOST_SIG)
         _host = L
     return _host
 

@@ -130,15 +130,10 @@ __global__ __launch_bounds__(256) void crt_resolve_adaptive_kernel(const float* 
 
 namespace {
 
-int adaptive_tiles(const crt_renderer* R) { return ((R->width + 7) / 8) * ((R->height + 7) / 8); }
-
 // The state is allocated on first use and initialised on `st`, the stream its first user goes on to enqueue on.
 int adaptive_state(crt_renderer* R, hipStream_t st, AdaptiveState** out) {
-    if (!R->adaptive) {
-        R->adaptive.reset(new (std::nothrow) AdaptiveState);   // whatever is allocated below is freed with the handle
-        AdaptiveState* A = R->adaptive.get();
-        if (!A) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-        const size_t n_pix = (size_t)R->width * R->height, n_tiles = (size_t)adaptive_tiles(R);
+    return first_use(R->adaptive, "the adaptive state of this renderer could not be allocated", out, [&](AdaptiveState* A) -> int {
+        const size_t n_pix = (size_t)R->width * R->height, n_tiles = (size_t)R->n_tiles();
         HIP_TRY(A->prev.alloc(n_pix * 3));
         HIP_TRY(A->tile_spp.alloc(n_tiles));
         HIP_TRY(A->tile_error.alloc(n_tiles));
@@ -155,19 +150,15 @@ int adaptive_state(crt_renderer* R, hipStream_t st, AdaptiveState** out) {
         HIP_TRY(hipMemsetAsync(A->d_count.get(), 0, 4, st));
         HIP_TRY(A->ev0.create());
         HIP_TRY(A->ev1.create());
-        A->ready = true;
-    }
-    if (!R->adaptive->ready)
-        return set_error(CRT_ERR_OUT_OF_MEMORY, "the adaptive state of this renderer could not be allocated");
-    *out = R->adaptive.get();
-    return CRT_OK;
+        return CRT_OK;
+    });
 }
 
 // One plan step on `st`: errors, keys, tile_spp and prev of the tiles at n samples, then the listed tiles and their
 // count.  Returns the list through *list: by error, or (by_error false) the compacted tiles in tile order.
 int adaptive_plan(crt_renderer* R, AdaptiveState* A, hipStream_t st, int n, int next, float tolerance, bool by_error,
                   const uint32_t** list) {
-    const int tiles_x = (R->width + 7) / 8, n_tiles = adaptive_tiles(R);
+    const int tiles_x = R->tiles_x(), n_tiles = R->n_tiles();
     hipLaunchKernelGGL(crt_adaptive_plan_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, st, R->d_sum, A->prev.get(), A->tile_spp.get(),
                        A->tile_error.get(), A->key.get(), R->width, R->height, tiles_x, n_tiles, n, next, tolerance);
     hipLaunchKernelGGL(crt_adaptive_compact_kernel, dim3(1), dim3(ADAPT_COMPACT_THREADS), 0, st, A->key.get(), n_tiles, A->ctile.get(),
@@ -192,16 +183,13 @@ int adaptive_pass(crt_renderer* R, const crt_scene* S, hipStream_t st, const uin
                   : variant == 8 ? ((size_t)count >= (size_t)4 * R->n_cus * 4 * 7 ? 7 : 6) : 6;
     P.stack_lds = stack_lds_for(R, S, occ);
     if (int rc = ensure_overflow_stack(R, S, st, P)) return rc;
-    P.tiles_x = (R->width + 7) / 8;
+    P.tiles_x = R->tiles_x();
     P.order = list;
     if (critical && variant == 8) {   // measurement only: the list's first tiles at the critical threshold
         P.crit_tiles = R->crit_tiles < 0 ? 4 * R->n_cus : R->crit_tiles;
         P.crit_threshold = R->crit_threshold;
     }
-    {   // the render's slot of the timing ring, as crt_renderer_render takes it
-        const DevEvent* slot = R->ring[R->n_timed % (CRT_TIMING_RING + 1)];
-        R->ev0 = slot[0].get(); R->ev_main = slot[1].get(); R->ev1 = slot[2].get();
-    }
+    take_timing_slot(R);
     HIP_TRY(hipEventRecord(R->ev0, st));
     R->last_schedule[0] = R->last_schedule[2] = R->last_schedule[3] = 0.f;
     R->last_schedule[1] = variant == 8 ? (float)occ : 0.f;
@@ -237,7 +225,7 @@ int crt_renderer_render_adaptive(crt_renderer* R, const crt_scene* S, const crt_
     AdaptiveState* A = nullptr;
     if (int rc = adaptive_state(R, st, &A)) return rc;
     const size_t n_pix = (size_t)R->width * R->height;
-    const int tiles_x = (R->width + 7) / 8, n_tiles = adaptive_tiles(R);
+    const int tiles_x = R->tiles_x(), n_tiles = R->n_tiles();
     if (!R->n_cus) HIP_TRY(hipDeviceGetAttribute(&R->n_cus, hipDeviceAttributeMultiprocessorCount, R->device));
     crt_adaptive_stats stats{};
     HIP_TRY(hipEventRecord(A->ev0.get(), st));
@@ -281,7 +269,7 @@ int crt_renderer_resolve_adaptive(crt_renderer* R, void* stream) {
     HIP_TRY(hipSetDevice(R->device));
     const int n = R->width * R->height;
     hipLaunchKernelGGL(crt_resolve_adaptive_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, R->d_sum,
-                       R->d_rgba.get(), R->adaptive->tile_spp.get(), R->width, n, (R->width + 7) / 8);
+                       R->d_rgba.get(), R->adaptive->tile_spp.get(), R->width, n, R->tiles_x());
     HIP_TRY(hipGetLastError());
     return CRT_OK;
 }
@@ -289,12 +277,12 @@ int crt_renderer_resolve_adaptive(crt_renderer* R, void* stream) {
 int crt_renderer_read_tile_spp(crt_renderer* R, int32_t* out) {
     if (!R || !R->adaptive || !R->adaptive->tile_spp)
         return set_error(CRT_ERR_INVALID_ARGUMENT, "read tile spp: no adaptive render on this renderer yet");
-    return read_dev(R, out, R->adaptive->tile_spp.get(), (size_t)adaptive_tiles(R) * 4);
+    return read_dev(R, out, R->adaptive->tile_spp.get(), (size_t)R->n_tiles() * 4);
 }
 int crt_renderer_read_tile_error(crt_renderer* R, float* out) {
     if (!R || !R->adaptive || !R->adaptive->tile_error)
         return set_error(CRT_ERR_INVALID_ARGUMENT, "read tile error: no adaptive render on this renderer yet");
-    return read_dev(R, out, R->adaptive->tile_error.get(), (size_t)adaptive_tiles(R) * 4);
+    return read_dev(R, out, R->adaptive->tile_error.get(), (size_t)R->n_tiles() * 4);
 }
 int crt_renderer_read_adaptive_prev(crt_renderer* R, float* out) {
     if (!R || !R->adaptive || !R->adaptive->prev)
@@ -312,7 +300,7 @@ int crt_selftest_adaptive_plan(crt_renderer* R, const float* sum, const float* p
     HIP_TRY(hipSetDevice(R->device));
     AdaptiveState* A = nullptr;
     if (int rc = adaptive_state(R, 0, &A)) return rc;
-    const size_t n_pix = (size_t)R->width * R->height, n_tiles = (size_t)adaptive_tiles(R);
+    const size_t n_pix = (size_t)R->width * R->height, n_tiles = (size_t)R->n_tiles();
     HIP_TRY(hipMemcpy(R->d_sum, sum, n_pix * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(A->prev.get(), prev, n_pix * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(A->tile_spp.get(), tile_spp, n_tiles * 4, hipMemcpyHostToDevice));

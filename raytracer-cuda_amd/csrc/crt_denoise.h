@@ -274,10 +274,7 @@ namespace {
 
 // The state is allocated on first use and initialised on `st`, the stream its first user goes on to enqueue on.
 int denoise_state(crt_renderer* R, hipStream_t st, DenoiseState** out) {
-    if (!R->denoise) {
-        R->denoise.reset(new (std::nothrow) DenoiseState);   // whatever is allocated below is freed with the handle
-        DenoiseState* N = R->denoise.get();
-        if (!N) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+    return first_use(R->denoise, "the denoiser state of this renderer could not be allocated", out, [&](DenoiseState* N) -> int {
         const size_t n_pix = (size_t)R->width * R->height;
         HIP_TRY(N->rays.alloc(n_pix * 2));
         HIP_TRY(N->hits.alloc(n_pix * 2));
@@ -289,12 +286,8 @@ int denoise_state(crt_renderer* R, hipStream_t st, DenoiseState** out) {
         HIP_TRY(hipMemsetAsync(N->denoised.get(), 0, n_pix * 12, st));
         for (DevEvent* e : {&N->g0, &N->g1, &N->f0, &N->f1}) HIP_TRY(e->create());
         for (DevEvent& e : N->it) HIP_TRY(e.create());
-        N->ready = true;
-    }
-    if (!R->denoise->ready)
-        return set_error(CRT_ERR_OUT_OF_MEMORY, "the denoiser state of this renderer could not be allocated");
-    *out = R->denoise.get();
-    return CRT_OK;
+        return CRT_OK;
+    });
 }
 
 // Before new guides are written: a buffer the reprojection keeps as its previous frame is left alone.
@@ -392,7 +385,7 @@ int denoise_run(crt_renderer* R, DenoiseState* N, const crt_denoise_options* o, 
     HIP_TRY(hipEventRecord(N->f0.get(), st));
     if (!c0)
         hipLaunchKernelGGL(crt_denoise_input_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, st, R->d_sum, N->col[0].get(),
-                           tile_scale ? R->adaptive->tile_spp.get() : nullptr, W, n_pix, (W + 7) / 8, scale);
+                           tile_scale ? R->adaptive->tile_spp.get() : nullptr, W, n_pix, R->tiles_x(), scale);
     const float sigma[3] = {o->sigma_color, o->sigma_normal, o->sigma_position};
     const DenoiseFilter F{crt_denoise_tiled_kernel, crt_denoise_direct_kernel, &N->lds_raised, true};
     return denoise_iterations(R, N, F, sigma, o->iterations, o->flags, c0, st, timed);

@@ -11,7 +11,7 @@
 namespace crt {
 
 // ---------------------------------------------------------------- layout
-// Flattened scene in HBM (built by crt_hip.hip from the host-built reference BVHs):
+// Flattened scene in HBM (built by crt_scene.h from the host-built reference BVHs):
 //
 // nodes: 2 x float4 (32 B) per node, DFS preorder over the scene BVH with every
 // mesh BVH spliced in after its scene leaf ("threaded" BVH: left child = next
@@ -174,7 +174,7 @@ __device__ __forceinline__ V3 rand_in_unit_sphere(Rng& s) {
 
 // Material.cuh:132-137 with pow(float,int) restated as exponentiation by squaring.  r0 = ((1 - ref_idx) /
 // (1 + ref_idx))^2 depends on the material and the face only: the shading record carries it (schlick_r0 in
-// crt_hip.hip's shading_records, IEEE f32 on the host, the same bits), so a hit pays no division for it.
+// crt_scene.h's shading_records, IEEE f32 on the host, the same bits), so a hit pays no division for it.
 __device__ __forceinline__ float schlick_r0(float cosine, float r0) {
     float a = 1 - cosine;
     float r = 1.0f * a;          // e = 5: bit0

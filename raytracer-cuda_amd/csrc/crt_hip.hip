@@ -2244,2299 +2244,14 @@ __global__ void crt_order_tiles_kernel(uint32_t* __restrict__ order, int width, 
     order[s] = (x < width && y < height) ? (uint32_t)(y * width + x) : 0xffffffffu;
 }
 
-// ------------------------------------------------------------------ host side
-namespace {
-
-// XORWOW single-step linear map and its 2^67*4^k powers (160 columns x 5 words).
-void xw_step(uint32_t v[5]) {
-    uint32_t t = v[0] ^ (v[0] >> 2);
-    v[0] = v[1]; v[1] = v[2]; v[2] = v[3]; v[3] = v[4];
-    v[4] = (v[4] ^ (v[4] << 4)) ^ (t ^ (t << 1));
-}
-void mv(const uint32_t* m, uint32_t v[5]) {
-    uint32_t r[5] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < 160; ++i)
-        if (v[i / 32] & (1u << (i % 32)))
-            for (int k = 0; k < 5; ++k) r[k] ^= m[i * 5 + k];
-    std::memcpy(v, r, sizeof r);
-}
-void mm(const uint32_t* b, const uint32_t* a, uint32_t* c) {   // c = b o a
-    for (int col = 0; col < 160; ++col) {
-        uint32_t v[5];
-        std::memcpy(v, a + 5 * col, sizeof v);
-        mv(b, v);
-        std::memcpy(c + 5 * col, v, sizeof v);
-    }
-}
-const std::vector<uint32_t>& seq_tables() {
-    static std::vector<uint32_t> tab;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        tab.assign(32 * 800, 0);
-        std::vector<uint32_t> m(800), t(800);
-        for (int col = 0; col < 160; ++col) {
-            uint32_t v[5] = {0, 0, 0, 0, 0};
-            v[col / 32] = 1u << (col % 32);
-            xw_step(v);
-            std::memcpy(&m[5 * col], v, sizeof v);
-        }
-        for (int s = 0; s < 67; ++s) { mm(m.data(), m.data(), t.data()); m.swap(t); }
-        std::memcpy(&tab[0], m.data(), 800 * 4);
-        for (int k = 1; k < 32; ++k) {
-            mm(&tab[800 * (k - 1)], &tab[800 * (k - 1)], t.data());
-            mm(t.data(), t.data(), &tab[800 * k]);
-        }
-    });
-    return tab;
-}
-
-inline float i2f(int v) { float f; std::memcpy(&f, &v, 4); return f; }
-inline int i2i_host(float f) { int v; std::memcpy(&v, &f, 4); return v; }
-
-inline bool zero_thickness(const float bmin[3], const float bmax[3]) {
-    // AABB::hit can never report such a box (the slab of that axis is empty: tmax <= tmin)
-    return bmin[0] == bmax[0] || bmin[1] == bmax[1] || bmin[2] == bmax[2];
-}
-
-// CRT_SETUP_TRACE=1: the host stages of scene creation timed on stderr (tools/setup_breakdown.py).
-struct SetupTrace {
-    bool on = std::getenv("CRT_SETUP_TRACE") != nullptr;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char* stage) {
-        if (!on) return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[crt setup] %-28s %8.2f ms\n", stage, std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-    }
-};
-
-// The host loops of scene creation that gather or fill one record per primitive run on up to 16 threads
-// (CRT::parallel_ranges; on config E's million triangles they took ~120 ms of its 0.34-s scene creation on one,
-// profiles/r05k).
-using CRT::parallel_ranges;
-
-// Flattens the reference's scene + mesh BVHs into the threaded layout and records, per primitive,
-// its reference DFS rank (the order BVHNode::hit / Mesh::hit visit primitives) and whether any box
-// on its path is zero-thickness (then the reference never reports it).
-struct Flattener {
-    const crt_scene_desc* D;
-    std::vector<float4> nodes, prims;
-    std::vector<int> mesh_prim_base;
-    std::vector<int> rank_of;        // per prim
-    std::vector<char> reachable;     // per prim
-    std::vector<int> rank_code;      // per rank: prim code
-    std::vector<int> sphere_of;      // per sphere prim, in prim order after the triangles: its index in D->spheres
-    int max_depth = 0;
-    std::string err;
-
-    void visit_prim(int p, int code, bool thin) {
-        if (rank_of[p] >= 0) return;
-        rank_of[p] = (int)rank_code.size();
-        rank_code.push_back(code);
-        reachable[p] = !thin;
-    }
-    // Primitives no leaf references get the remaining ranks (never hit); ranks go into the records.
-    void finalize_ranks() {
-        const int n = (int)(prims.size() / 3);
-        for (int p = 0; p < n; ++p) {
-            if (rank_of[p] < 0) {
-                rank_of[p] = (int)rank_code.size();
-                rank_code.push_back(p);
-                reachable[p] = 0;
-            }
-            const bool sphere = (rank_code[rank_of[p]] & SPHERE_BIT) != 0;
-            if (sphere) prims[3 * p + 1].z = i2f(rank_of[p]);
-            prims[3 * p + 2].z = i2f(rank_of[p]);
-        }
-    }
-
-    int push_node(const float bmin[3], const float bmax[3], int a, int b) {
-        nodes.push_back(make_float4(bmin[0], bmin[1], bmin[2], bmax[0]));
-        nodes.push_back(make_float4(bmax[1], bmax[2], i2f(a), i2f(b)));
-        return (int)(nodes.size() / 2) - 1;
-    }
-    void set_a(int idx, int a) { nodes[2 * idx + 1].z = i2f(a); }
-    int count() const { return (int)(nodes.size() / 2); }
-
-    bool emit_mesh(int m, int ni, int depth, bool thin) {
-        const crt_mesh_desc& M = D->meshes[m];
-        if (ni < 0 || ni >= M.node_count) { err = "mesh node index out of range"; return false; }
-        if (depth > 4096) { err = "mesh BVH too deep"; return false; }
-        max_depth = std::max(max_depth, depth);
-        const crt_bvh_node_desc& N = M.nodes[ni];
-        thin = thin || zero_thickness(N.bmin, N.bmax);
-        if (!N.is_leaf) {
-            int idx = push_node(N.bmin, N.bmax, 0, NODE_MESH_INNER);
-            if (!emit_mesh(m, N.left, depth + 1, thin) || !emit_mesh(m, N.right, depth + 1, thin)) return false;
-            set_a(idx, count());
-        } else {
-            if (N.obj_index < 0 || N.obj_count < 0 || N.obj_index % 3 || N.obj_count % 3 ||
-                (uint64_t)N.obj_index + N.obj_count > M.index_count) { err = "bad mesh leaf range"; return false; }
-            long first = mesh_prim_base[m] + N.obj_index / 3;
-            if (first >= SPHERE_BIT) { err = "too many primitives"; return false; }
-            push_node(N.bmin, N.bmax, N.obj_count / 3, (int)first);
-            for (int k = 0; k < (int)N.obj_count / 3; ++k) visit_prim((int)first + k, (int)first + k, thin);
-        }
-        return true;
-    }
-    bool emit_scene(int ni, int depth, bool thin) {
-        if (ni < 0 || ni >= D->n_scene_nodes) { err = "scene node index out of range"; return false; }
-        if (depth > 4096) { err = "scene BVH too deep"; return false; }
-        max_depth = std::max(max_depth, depth);
-        const crt_bvh_node_desc& N = D->scene_nodes[ni];
-        thin = thin || zero_thickness(N.bmin, N.bmax);
-        if (!N.is_leaf) {
-            int idx = push_node(N.bmin, N.bmax, 0, NODE_SCENE_INNER);
-            if (!emit_scene(N.left, depth + 1, thin) || !emit_scene(N.right, depth + 1, thin)) return false;
-            set_a(idx, count());
-            return true;
-        }
-        if (N.obj_index < 0 || N.obj_index >= D->n_objects) { err = "scene leaf object out of range"; return false; }
-        const crt_object_desc& O = D->objects[N.obj_index];
-        if (O.kind == CRT_OBJECT_MESH) {
-            if (O.index < 0 || O.index >= D->n_meshes) { err = "mesh object index out of range"; return false; }
-            int idx = push_node(N.bmin, N.bmax, 0, NODE_SCENE_INNER);
-            if (D->meshes[O.index].node_count > 0 && !emit_mesh(O.index, 0, depth + 1, thin)) return false;
-            set_a(idx, count());
-        } else if (O.kind == CRT_OBJECT_SPHERE) {
-            if (O.index < 0 || O.index >= D->n_spheres) { err = "sphere object index out of range"; return false; }
-            const crt_sphere_desc& S = D->spheres[O.index];
-            int p = (int)(prims.size() / 3);
-            if (p >= SPHERE_BIT) { err = "too many primitives"; return false; }
-            prims.push_back(make_float4(S.center[0], S.center[1], S.center[2], S.radius));
-            prims.push_back(make_float4(S.radius * S.radius, i2f(S.material), 0.f, 0.f));   // Sphere.cuh:21
-            prims.push_back(make_float4(0.f, i2f(S.material), 0.f, i2f(1)));                  // word 11 = 1: sphere
-            rank_of.push_back(-1);
-            reachable.push_back(0);
-            sphere_of.push_back(O.index);
-            visit_prim(p, SPHERE_BIT | p, thin);
-            push_node(N.bmin, N.bmax, 0, SPHERE_BIT | p);
-        } else {
-            err = "unknown object kind";
-            return false;
-        }
-        return true;
-    }
-    bool build_triangles() {
-        mesh_prim_base.assign(D->n_meshes, 0);
-        size_t total = 0;
-        for (int m = 0; m < D->n_meshes; ++m) {
-            const crt_mesh_desc& M = D->meshes[m];
-            if ((uint64_t)M.index_offset + M.index_count > D->n_indices ||
-                (uint64_t)M.vertex_offset + M.vertex_count > D->n_positions ||
-                (uint64_t)M.face_offset + M.index_count / 3 > D->n_faces || M.index_count % 3) {
-                err = "mesh ranges exceed the scene arrays";
-                return false;
-            }
-            mesh_prim_base[m] = (int)total;
-            total += M.index_count / 3;
-        }
-        prims.reserve(3 * (total + (size_t)std::max(D->n_spheres, 0)));   // emit_scene appends the spheres
-        prims.assign(3 * total, make_float4(0.f, 0.f, 0.f, 0.f));
-        bool bad_index = false;
-        for (int m = 0; m < D->n_meshes; ++m) {
-            const crt_mesh_desc& M = D->meshes[m];
-            float4* out = prims.data() + 3 * (size_t)mesh_prim_base[m];
-            std::atomic<bool> bad{false};
-            parallel_ranges(M.index_count / 3, [&](size_t b, size_t e) {
-                for (size_t t = b; t < e; ++t) {
-                    uint32_t iv[3];
-                    for (int c = 0; c < 3; ++c) {
-                        iv[c] = D->indices[M.index_offset + 3 * t + c];
-                        if (iv[c] >= M.vertex_count) { bad.store(true, std::memory_order_relaxed); iv[c] = 0; }   // reported below
-                    }
-                    const float* p0 = D->positions + 3 * ((size_t)M.vertex_offset + iv[0]);
-                    const float* p1 = D->positions + 3 * ((size_t)M.vertex_offset + iv[1]);
-                    const float* p2 = D->positions + 3 * ((size_t)M.vertex_offset + iv[2]);
-                    const float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};   // Mesh.cuh:277
-                    const float e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};   // Mesh.cuh:278
-                    const uint32_t mat = (uint32_t)(D->face_materials[M.face_offset + t] + (int32_t)M.material_id_offset);
-                    out[3 * t] = make_float4(p0[0], p0[1], p0[2], e1[0]);
-                    out[3 * t + 1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
-                    out[3 * t + 2] = make_float4(e2[2], i2f((int)mat), 0.f, 0.f);
-                }
-            });
-            bad_index = bad_index || bad.load();
-        }
-        if (bad_index) { err = "vertex index out of range"; return false; }
-        rank_of.assign(prims.size() / 3, -1);
-        reachable.assign(prims.size() / 3, 0);
-        return true;
-    }
-};
-
-// CRT_BVH_REBUILT: binned-SAH tree over the reachable primitives of a flattened reference scene,
-// emitted as `layouts` threaded arrays (crt_sah.h).  Primitive records keep their rank.
-struct Rebuilt {
-    std::vector<float4> nodes, prims;
-    std::vector<int> rank_code;
-    int n_nodes = 0, max_depth = 0;
-    long excluded = 0;
-    std::string err;
-
-    int width = 2;
-    int stack_bound = 0;   // width 4: most stack entries any traversal can hold
-    int sphere_first = 0, n_ray_spheres = 0;   // width 4: spheres kept out of the tree (tested per ray)
-    std::vector<float4> chain;                 // their reference scene-level leaf boxes (2 float4 per box)
-    static constexpr int kMaxRaySpheres = 8;
-    // With more than kMaxRaySpheres spheres the small ones go into the tree's leaves, but a sphere of at least this
-    // radius stays per ray: only there is its reference scene-level box replayed (ray_spheres).  The f32 roots of
-    // Sphere::hit err by about ulp(r^2) / |oc . d|; for the radius-999 ground sphere that puts a spurious root of a
-    // ray leaving the surface above t = 0.001 while the reference's box test has already rejected the ray
-    // (tests/golden/ground_sphere_rays.json), and a leaf's padded box is too wide to reject it.  Below radius 1 the
-    // same needs a ray within 3e-5 rad of the tangent plane that also starts within 0.001 |d| of the box face.
-    static constexpr float kRaySphereRadius = 1.0f;
-
-    // gpu_device >= 0: the binned-SAH tree is built on that GPU (crtx_build_sah_gpu, crt_bvh_build.hip)
-    long spatial_splits = 0;   // SBVH: nodes cut by a plane, and primitive references in the leaves
-    long references = 0;
-
-    // gpu_device >= 0: the binned-SAH tree is built on that GPU (crtx_build_sah_gpu, crt_bvh_build.hip); spatial:
-    // SBVH on the host (crt_sah::SpatialBuilder), width 4 only
-    bool build(const Flattener& F, int leaf_size, int layouts, float trav_cost, int wide, int gpu_device = -1,
-               bool spatial = false, float alpha = 1e-5f, float max_dup = 1.f) {
-        SetupTrace tr;
-        width = wide;
-        const int n = (int)(F.prims.size() / 3);
-        std::vector<crt_sah::Item> items;
-        items.reserve(n);
-        std::vector<int> ray_sph;
-        std::vector<crt_sah::TriVerts> verts;
-        if (spatial && width != 4) { err = "spatial splits need width 4"; return false; }
-        int n_sph = 0, n_large = 0;
-        for (int p = 0; p < n; ++p)
-            if (F.rank_code[F.rank_of[p]] & SPHERE_BIT) {
-                ++n_sph;
-                n_large += F.reachable[p] && !(std::fabs(F.prims[3 * (size_t)p].w) < kRaySphereRadius);
-            }
-        const bool all_per_ray = width == 4 && n_sph <= kMaxRaySpheres;
-        if (width == 4 && !all_per_ray && n_large > kMaxRaySpheres) {
-            err = "more than 8 spheres of radius >= 1 among more than 8 spheres: large spheres are tested per ray, "
-                  "at most 8 of them (width 2 takes any number)";
-            return false;
-        }
-        for (int p = 0; p < n; ++p) {
-            const bool sphere = (F.rank_code[F.rank_of[p]] & SPHERE_BIT) != 0;
-            if (!F.reachable[p]) { excluded += !sphere; continue; }
-            const float4 f0 = F.prims[3 * p], f1 = F.prims[3 * p + 1], f2 = F.prims[3 * p + 2];
-            const bool spheres_per_ray = all_per_ray || (width == 4 && !(std::fabs(f0.w) < kRaySphereRadius));
-            if (sphere && spheres_per_ray) {
-                // a per-ray sphere's hit point becomes a ray origin too: the same 2^60 bound as the tree's boxes
-                // (wide_boxes: |o| * 2^64 must stay finite)
-                const float c[3] = {f0.x, f0.y, f0.z}, r = std::fabs(f0.w);
-                for (int a = 0; a < 3; ++a)
-                    if (!(std::fabs(c[a] - r) < 0x1p60f && std::fabs(c[a] + r) < 0x1p60f)) {
-                        err = "sphere bounds non-finite or beyond 2^60";
-                        return false;
-                    }
-                ray_sph.push_back(p);
-                continue;
-            }
-            crt_sah::Item it;
-            it.src = p;
-            it.sphere = sphere;
-            if (sphere) {
-                const float c[3] = {f0.x, f0.y, f0.z}, r = std::fabs(f0.w);
-                for (int a = 0; a < 3; ++a) { it.lo[a] = c[a] - r; it.hi[a] = c[a] + r; }
-            } else {
-                const float v0[3] = {f0.x, f0.y, f0.z};
-                const float e1[3] = {f0.w, f1.x, f1.y}, e2[3] = {f1.z, f1.w, f2.x};
-                for (int a = 0; a < 3; ++a) {
-                    const float v1 = v0[a] + e1[a], v2 = v0[a] + e2[a];
-                    it.lo[a] = std::min(v0[a], std::min(v1, v2));
-                    it.hi[a] = std::max(v0[a], std::max(v1, v2));
-                }
-            }
-            if (spatial && !sphere) {   // the triangle's vertices for clipping, v0 + e1 and v0 + e2 exact in double
-                crt_sah::TriVerts T;
-                const double v0[3] = {f0.x, f0.y, f0.z};
-                const double e1[3] = {f0.w, f1.x, f1.y}, e2[3] = {f1.z, f1.w, f2.x};
-                for (int a = 0; a < 3; ++a) {
-                    T.v[0][a] = v0[a];
-                    T.v[1][a] = v0[a] + e1[a];
-                    T.v[2][a] = v0[a] + e2[a];
-                }
-                it.tri = (int)verts.size();
-                verts.push_back(T);
-            }
-            bool finite = true;
-            for (int a = 0; a < 3; ++a) {
-                it.c[a] = 0.5f * it.lo[a] + 0.5f * it.hi[a];
-                // box_inv's clamp (2^64) keeps |coord| * inv finite only below 2^60 (wide_boxes)
-                finite = finite && std::fabs(it.lo[a]) < 0x1p60f && std::fabs(it.hi[a]) < 0x1p60f;
-            }
-            if (!finite) { err = "primitive bounds non-finite or beyond 2^60"; return false; }
-            items.push_back(it);
-        }
-        rank_code.assign(F.rank_code.size(), 0);
-        auto append_ray_spheres = [&]() {
-            sphere_first = (int)(prims.size() / 3);
-            const int n_ref = F.count();
-            for (int p : ray_sph) {
-                const int np = (int)(prims.size() / 3);
-                for (int q = 0; q < 3; ++q) prims.push_back(F.prims[3 * p + q]);
-                rank_code[F.rank_of[p]] = SPHERE_BIT | np;
-                // the sphere's leaf in the flattened reference scene and every scene-level node enclosing it
-                int leaf = -1;
-                for (int i = 0; i < n_ref && leaf < 0; ++i)
-                    if (i2i(F.nodes[2 * (size_t)i + 1].w) == (SPHERE_BIT | p)) leaf = i;
-                const float4 B = F.nodes[2 * (size_t)leaf + 1];
-                prims[3 * (size_t)np + 1].w = i2f((int)(chain.size() / 2));
-                chain.push_back(F.nodes[2 * (size_t)leaf]);
-                chain.push_back(make_float4(B.x, B.y, 0.f, 0.f));
-            }
-            n_ray_spheres = (int)ray_sph.size();
-        };
-        if (items.empty()) {   // nothing hittable: one empty-box node that no ray enters
-            const float lo[3] = {0, 0, 0};
-            prims.assign(3, make_float4(0, 0, 0, 0));
-            for (int l = 0; l < layouts; ++l) {
-                nodes.push_back(make_float4(lo[0], lo[1], lo[2], lo[0]));
-                nodes.push_back(make_float4(lo[1], lo[2], i2f(1), i2f(NODE_MESH_INNER)));
-            }
-            n_nodes = 1;
-            if (width == 4) {   // a 4-wide root with no slots
-                nodes.clear();
-                for (int r = 0; r < 6; ++r) nodes.push_back(make_float4(1e30f, 1e30f, 1e30f, 1e30f));
-                nodes.push_back(make_float4(i2f(0), i2f(0), i2f(0), i2f(0)));
-                nodes.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
-                prims.clear();
-                append_ray_spheres();
-                stack_bound = 1;
-            }
-            return true;
-        }
-        tr.lap("  SAH items");
-        std::vector<crt_sah::Node> bnv;
-        std::vector<crt_sah::Item> its;
-        if (spatial) {
-            crt_sah::SpatialBuilder B(std::move(items), std::move(verts), leaf_size, trav_cost, alpha, max_dup);
-            B.build();
-            max_depth = B.max_depth();
-            spatial_splits = B.spatial_splits();
-            bnv = B.nodes();
-            its = B.items();
-        } else if (gpu_device >= 0) {
-            std::vector<int> order;
-            if (crtx_build_sah_gpu(gpu_device, items, leaf_size, trav_cost, &bnv, &order, &max_depth) != CRT_OK) {
-                err = std::string("GPU SAH build: ") + crt_last_error();
-                return false;
-            }
-            its.resize(order.size());
-            for (size_t i = 0; i < order.size(); ++i) its[i] = items[order[i]];
-        } else {
-            crt_sah::Builder B(std::move(items), leaf_size, trav_cost);
-            B.build();
-            max_depth = B.max_depth();
-            bnv = B.nodes();
-            its = B.items();
-        }
-        references = (long)its.size();
-        tr.lap(gpu_device >= 0 ? "  SAH build (GPU)" : "  SAH build (host)");
-        if (width == 4) {
-            if (!emit4(F, bnv, its, !spatial)) return false;
-            tr.lap("  4-wide collapse + emission");
-            append_ray_spheres();
-            tr.lap("  per-ray spheres");
-            return true;
-        }
-        prims.resize(3 * its.size());
-        for (size_t i = 0; i < its.size(); ++i) {
-            const int p = its[i].src;
-            for (int q = 0; q < 3; ++q) prims[3 * i + q] = F.prims[3 * p + q];
-            rank_code[F.rank_of[p]] = its[i].sphere ? (SPHERE_BIT | (int)i) : (int)i;
-        }
-        const auto& bn = bnv;
-        n_nodes = (int)bn.size();
-        nodes.reserve(2 * (size_t)n_nodes * layouts);
-        for (int l = 0; l < layouts; ++l) {
-            const size_t base = nodes.size() / 2;
-            emit(bn, its, 0, l, layouts, base);
-        }
-        return true;
-    }
-
-private:
-    // 4-wide nodes in BFS order (internal children of a node consecutive), primitives re-laid out so the
-    // leaf children of every node are consecutive in slot order.  See the node format at wide_boxes().
-    bool emit4(const Flattener& F, const std::vector<crt_sah::Node>& bn, const std::vector<crt_sah::Item>& its,
-               bool unique_items) {
-        prims.clear();
-        SetupTrace tr;
-        // a 4-wide node step costs about one triangle test (the cost probe's weights); node costs 0.5
-        // and 2 measured the same (profiles/r02ax)
-        const crt_sah::Collapse col(bn, 1.0);
-        tr.lap("    collapse DP");
-        // BFS one level at a time: the level's cuts (Collapse::open, a few dependent reads of the binary tree each) in
-        // parallel, then its child and primitive offsets in order
-        std::vector<int> queue{0}, first_child_of, leaf_first_of;
-        std::vector<crt_sah::Wide> wide;
-        size_t n_items = 0;
-        for (size_t lb = 0; lb < queue.size();) {
-            const size_t le = queue.size();
-            wide.resize(le);
-            parallel_ranges(le - lb, [&](size_t b, size_t e) {
-                for (size_t qi = lb + b; qi < lb + e; ++qi) wide[qi] = col.open(queue[qi]);
-            }, 4096);
-            for (size_t qi = lb; qi < le; ++qi) {
-                const crt_sah::Wide& w = wide[qi];
-                first_child_of.push_back((int)queue.size());
-                for (int s = 0; s < w.n_internal; ++s) queue.push_back(w.bin[s]);
-                leaf_first_of.push_back((int)n_items);
-                int total_leaf = 0;
-                for (int s = w.n_internal; s < w.n_slots; ++s) {
-                    if (bn[w.bin[s]].count > 255) { err = "leaf too large"; return false; }
-                    total_leaf += bn[w.bin[s]].count;
-                }
-                // node_step4 takes the leaf span from counts * 0x01010101 (byte-wise running sums)
-                if (total_leaf > 255) { err = "leaf children of one node hold more than 255 primitives"; return false; }
-                n_items += (size_t)total_leaf;
-                // prim_test addresses a record as __umul24(index, 48): the 4-wide tree holds fewer than 2^24 primitives
-                if (n_items >= ((size_t)1 << 24)) { err = "the 4-wide tree holds at most 2^24 - 1 primitives"; return false; }
-            }
-            lb = le;
-        }
-        const size_t n_wide = queue.size();
-        tr.lap("    node cuts (BFS)");
-        // node records and each primitive position's item (item_at), then the primitive records: every node and every
-        // position is written once.  Every span node_step4 can form (leaf_first + the node's leaf counts) lies inside
-        // the primitive array by construction; the fast kernel relies on it (the checked build re-checks it on the
-        // device).
-        nodes.assign(8 * n_wide, make_float4(0.f, 0.f, 0.f, 0.f));
-        std::vector<int> item_at(n_items);
-        parallel_ranges(n_wide, [&](size_t b, size_t e) {
-            for (size_t qi = b; qi < e; ++qi) {
-                const crt_sah::Wide& w = wide[qi];
-                uint32_t counts = 0;
-                int at = leaf_first_of[qi];
-                for (int s = w.n_internal; s < w.n_slots; ++s) {
-                    const crt_sah::Node& L = bn[w.bin[s]];
-                    counts |= (uint32_t)L.count << (8 * s);
-                    for (int i = L.first; i < L.first + L.count; ++i) item_at[at++] = i;
-                }
-                float4* row = nodes.data() + 8 * qi;
-                for (int a = 0; a < 3; ++a) {
-                    float lo[4], hi[4];
-                    for (int s = 0; s < 4; ++s) {
-                        lo[s] = hi[s] = 1e30f;   // empty slot: zero-thickness, never hit
-                        if (s < w.n_slots) { lo[s] = bn[w.bin[s]].lo[a]; hi[s] = bn[w.bin[s]].hi[a]; }
-                    }
-                    row[2 * a] = make_float4(lo[0], lo[1], lo[2], lo[3]);
-                    row[2 * a + 1] = make_float4(hi[0], hi[1], hi[2], hi[3]);
-                }
-                row[6] = make_float4(i2f(first_child_of[qi]), i2f(w.n_internal | (w.n_slots << 8)), i2f(leaf_first_of[qi]),
-                                     i2f((int)counts));
-            }
-        }, 4096);
-        tr.lap("    node records");
-        prims.reserve(3 * (n_items + kMaxRaySpheres));   // append_ray_spheres adds at most kMaxRaySpheres records
-        prims.resize(3 * n_items);
-        // a primitive referenced by several leaves (spatial splits) keeps the rank code of its last position, as the
-        // sequential emission did; unique items (the binned builders) have one position each, so any order will do
-        auto gather = [&](size_t b, size_t e) {
-            for (size_t np = b; np < e; ++np) {
-                const crt_sah::Item& it = its[item_at[np]];
-                for (int q = 0; q < 3; ++q) prims[3 * np + q] = F.prims[3 * (size_t)it.src + q];
-                rank_code[F.rank_of[it.src]] = it.sphere ? (SPHERE_BIT | (int)np) : (int)np;
-            }
-        };
-        if (unique_items) parallel_ranges(n_items, gather);
-        else gather(0, n_items);
-        n_nodes = (int)queue.size();
-        tr.lap("    primitive gather");
-        // stack bound: visiting a node with 2+ hit internal children pushes ONE entry (its remaining children)
-        if (n_nodes >= (1 << 24)) { err = "too many nodes for 24-bit stack entries"; return false; }
-        std::vector<int> bound(n_nodes, 0);
-        for (int n = n_nodes - 1; n >= 0; --n) {
-            const int fc = i2i(nodes[8 * (size_t)n + 6].x), m = wide[n].n_internal;
-            int b = 0;
-            for (int s = 0; s < m; ++s) b = std::max(b, bound[fc + s]);
-            bound[n] = b + (m >= 2 ? 1 : 0);
-        }
-        stack_bound = bound[0] + 1;
-        return true;
-    }
-    static int i2i(float f) { int v; std::memcpy(&v, &f, 4); return v; }
-
-    void emit(const std::vector<crt_sah::Node>& bn, const std::vector<crt_sah::Item>& its, int ni, int layout,
-              int layouts, size_t base) {
-        const crt_sah::Node& N = bn[ni];
-        const size_t idx = nodes.size() / 2;
-        int a = 0, b;
-        if (N.child[0] < 0) {
-            if (its[N.first].sphere) b = SPHERE_BIT | N.first;
-            else { a = N.count; b = N.first; }
-        } else {
-            b = NODE_MESH_INNER;
-        }
-        nodes.push_back(make_float4(N.lo[0], N.lo[1], N.lo[2], N.hi[0]));
-        nodes.push_back(make_float4(N.hi[1], N.hi[2], i2f(a), i2f(b)));
-        if (N.child[0] < 0) return;
-        int first = N.child[0], second = N.child[1];
-        if (layouts == 6) {   // near child first along the layout's direction
-            const int ax = layout / 2;
-            const bool neg = layout & 1;
-            const float c0 = bn[first].lo[ax] + bn[first].hi[ax], c1 = bn[second].lo[ax] + bn[second].hi[ax];
-            if (neg ? (c1 > c0) : (c1 < c0)) std::swap(first, second);
-        }
-        emit(bn, its, first, layout, layouts, base);
-        emit(bn, its, second, layout, layouts, base);
-        nodes[2 * idx + 1].z = i2f((int)(nodes.size() / 2 - base));   // skip, relative to the layout
-    }
-};
-
-}  // namespace
-
-// The per-handle states of the later entries, each allocated by the first call that needs it and freed with its handle.
-// `ready` is set once everything in the state is allocated: a state that is not ready could not be allocated.
-
-// Ray queries (crt_trace.h).
-struct TraceScratch {
-    DevBuf<uint32_t> d_next;
-    DevBuf<unsigned long long> d_stats;
-    DevBuf<uint32_t> d_ovf;                  // stack entries beyond the LDS part, per grid lane
-    DevBuf<crt_ray> d_rays;                  // staging of the host-pointer entries
-    DevBuf<crt_hit> d_hits;
-    DevBuf<uint8_t> d_occ;
-    DevEvent ev0, ev1;
-    bool ready = false;
-    bool traced = false;
-    int n_cus = 0, wg_per_cu = 0;
-};
-
-// The wavefront loop's scratch (crt_paths.h).
-struct WavefrontScratch {
-    DevBuf<crt_ray> rays[2];
-    DevBuf<crt_path> paths[2];
-    DevBuf<crt_hit> hits;
-    DevBuf<int32_t> remaining;
-    DevBuf<uint32_t> d_count;
-    PinnedBuf<uint32_t> h_count;            // [0] the count, [2..3] the trace error word
-    // the queued loop (crt_renderer_render_wavefront_queued): 8 device words and their pinned copy
-    DevBuf<uint32_t> d_queue;               // [0], [1] the ping-pong counts, [2] the sticky error word, [4..7] the totals
-    PinnedBuf<uint32_t> h_queue;
-    DevEvent ev0, ev1;
-    bool ready = false;
-};
-
-// The renderer's adaptive state (crt_adaptive.h).
-struct AdaptiveState {
-    DevBuf<float> prev;             // W*H*3: the sums after the first half of the samples a candidate tile holds
-    DevBuf<int32_t> tile_spp;       // per tile: samples every pixel of the tile has received
-    DevBuf<float> tile_error;       // per tile: the last error estimate
-    DevBuf<uint32_t> key;           // per tile: 0 = not listed, else the error as an ordered integer
-    DevBuf<uint32_t> ctile;         // the unconverged tiles of the last plan in tile order, n_tiles entries
-    DevBuf<uint32_t> ckey;          // their keys
-    DevBuf<uint32_t> list;          // the same tiles, largest error first
-    DevBuf<uint32_t> d_count;       // their number
-    PinnedBuf<uint32_t> h_count;
-    DevEvent ev0, ev1;
-    bool ready = false;
-};
-
-// The renderer's denoiser state (crt_denoise.h).
-// Bytes per pixel: rays 32 + hits 32 (compute_guides only) + guides 32 + two colour buffers 2 x 16 + denoised 12 = 140,
-// plus one word per 64 pixels (the hit counts).
-struct DenoiseState {
-    DevBuf<float4> rays;            // 2 rows per pixel: the pixel-centre rays (crt_ray)
-    DevBuf<float4> hits;            // 2 rows per pixel: their closest hits (crt_hit)
-    DevBuf<float4> guides[2];       // 2 rows per pixel: (normal.xyz, t) (position.xyz, key); [gi] is the current one,
-                                    // [1] exists only once the reprojection keeps previous guides (crt_reproject.h)
-    int gi = 0;
-    bool keep = false;              // guides[gi] is also the reprojection's previous frame: the next guides go to [gi ^ 1]
-    crt_camera_desc guide_cam{};    // the camera guides[gi]'s rays were made from (compute_guides)
-    DevBuf<float4> col[2];          // 1 row per pixel: (c.xyz, 0)
-    DevBuf<float> denoised;         // W*H*3
-    DevBuf<uint32_t> wave_hits;     // per 64 pixels: how many of them hit something
-    bool ready = false;
-    bool have_guides = false;       // guides hold a compute_guides or self-test result
-    bool counted = false;           // wave_hits belongs to the guides (compute_guides; not the self-test's upload)
-    bool have_denoised = false;
-    bool timed_guides = false;
-    DevEvent g0, g1, f0, f1;
-    DevEvent it[9];                 // a timed run: after the input kernel, then after every iteration
-    bool lds_raised = false;        // the tiled kernel's dynamic LDS limit was raised for this device
-    int timed_iterations = 0;       // iterations of the last timed run (crt_renderer_denoise_iteration_ms), 0: none
-};
-
-// The renderer's reprojection state (crt_reproject.h).  Bytes per pixel: two history buffers of 16-byte rows 32 + the
-// second guide buffer 32 = 64, plus one word per wave of the reprojection kernel's grid.
-struct ReprojectState {
-    DevBuf<float4> hist[2];         // 1 row per pixel: (r, g, b, len); [hi] holds the latest history
-    DevBuf<uint32_t> wave_taken;    // per wave of the kernel's grid: how many of its pixels took history
-    int hi = 0;
-    int prev_gi = 0;                // DenoiseState::guides[prev_gi]: the guides of the frame hist[hi] belongs to
-    crt_camera_desc prev_cam{};     // and their guide camera
-    bool ready = false;
-    bool valid = false;             // hist[hi], guides[prev_gi] and prev_cam describe one earlier frame
-    bool have_history = false;      // hist[hi] holds a reprojection's result
-    DevEvent e0, e1;
-};
-
-// The renderer's variance state (crt_variance.h).  Bytes per pixel: two moment buffers of 8-byte rows 16, allocated by
-// the first crt_renderer_reproject_moments, + the variance 4, allocated by the first crt_renderer_denoise_history_variance.
-struct VarianceState {
-    DevBuf<float2> mom[2];          // 1 row per pixel: (m1, m2) of the luminance; [mi] belongs to ReprojectState::hist[hi]
-    DevBuf<float> variance;         // W*H: the estimate kernel's v (crt_renderer_read_variance)
-    int mi = 0;
-    bool moments_valid = false;     // mom[mi] and hist[hi] describe the same frames (a plain reprojection or a reset ends it)
-    bool have_variance = false;
-    bool lds_raised = false;        // the variance tiled kernel's dynamic LDS limit was raised for this device
-};
-
-struct crt_scene {
-    int device = 0;
-    DevBuf<float4> d_nodes, d_prims, d_mats;
-    DevBuf<float4> d_chain;        // width 4: reference scene-level boxes on the per-ray spheres' paths
-    int n_chain = 0;
-    DevBuf<float4> d_shade;        // shading record per rank (crt_device.h)
-    int n_nodes = 0, n_prims = 0, n_mats = 0, n_ranks = 0;   // n_nodes per layout
-    int max_depth = 0;
-    int bvh = CRT_BVH_REFERENCE, layouts = 1;
-    int width = 2;                 // 2: threaded layouts (variants 0-3); 4: 4-wide nodes (variant 4)
-    int stack_cap = 0;             // width 4: traversal-stack entries a ray can need
-    int stack_bound = 0;           // width 4: the tree's own bound (stack_cap without the testing override)
-    long spatial_splits = 0, references = 0;   // rebuilt tree: SBVH cuts, leaf references
-    int sphere_first = 0, n_ray_spheres = 0;   // width 4: spheres tested per ray, prims [first, first + n)
-    float sph2[2][12] = {};                    // width 4 with exactly two per-ray spheres: their kernel-argument copy
-    int tree_spheres = 1;                      // width 4: some leaf holds a sphere
-    long excluded = 0;
-    DevBuf<int4> d_ident;          // ray queries: per rank (object, primitive, material, 0), see identity_table
-    std::unique_ptr<TraceScratch> trace;    // ray queries: scratch of the handle, allocated on first use (crt_trace.h)
-    DevBuf<float4> d_mat_rows;     // path steps: per material (code, 0, 0, 0) (payload), see material_shade_rows
-};
-
-constexpr int ERR_WORD = 15;      // d_counters word of the device error flags (RenderParams::err)
-
-struct crt_renderer {
-    int device = 0, width = 0, height = 0;
-    DevBuf<uint32_t> d_rng;
-    float* d_sum = nullptr;       // active linear framebuffer (own or attached)
-    DevBuf<float> d_sum_own;
-    DevBuf<uint8_t> d_rgba;
-    DevBuf<uint32_t> d_seq;
-    DevBuf<unsigned long long> d_counters;
-    crt_camera_desc cam{};
-    bool has_camera = false;
-    // HIP events of the current render: ev0 before the cost probe, ev_main just before the main render kernel (after
-    // the probe and the tile sort), ev1 after it.  They point into a ring of CRT_TIMING_RING frames, so a caller that
-    // renders K frames back to back without synchronising can read every frame's phases afterwards
-    // (crt_renderer_timing_history).  The ring has one slot more than the history reaches: a render records into slot
-    // n_timed % (CRT_TIMING_RING + 1), which none of the last CRT_TIMING_RING complete frames occupies, so a render that
-    // fails after its first event (an allocation, the overflow-region check) leaves every readable slot intact.
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_main = nullptr;
-    DevEvent ring[CRT_TIMING_RING + 1][3];
-    unsigned long long n_timed = 0;   // renders whose three events were all recorded
-    char kernel_name[64] = "";     // instantiation of the last render launch, rocprof's spelling
-    int last_frozen = 0;           // that launch ran a frozen twin (crt_renderer_last_launch_frozen)
-    // variant 7: pixel order, slot queue, probe costs, sort scratch (allocated on first use)
-    DevBuf<uint32_t> d_order, d_queue;
-    DevBuf<uint32_t> d_tile_cost;      // per-pixel probe costs
-    DevBuf<uint32_t> d_order_hist;
-    DevBuf<uint32_t> d_tile_key;       // variant 8: per-tile keys
-    DevBuf<unsigned long long> d_probe_stats;      // crt_tile_cost_kernel's stats: largest tile work, total work
-    PinnedBuf<unsigned long long> h_probe_stats;   // their pinned host copy
-    float last_schedule[4] = {0.f, 0.f, 0.f, 0.f};  // crt_renderer_last_schedule
-    DevBuf<uint32_t> d_rng_cache;      // curand_init result of (rng_cache_seed, rng_cache_base)
-    unsigned long long rng_cache_seed = 0, rng_cache_base = 0;
-    bool rng_cache_valid = false;
-    int probe_spp = -1;            // samples per pixel of the cost probe; 0 = no probe (8x8-tile order),
-                                   // -1 = automatic: 4 for renders of >= 1000 spp, else 2 (profiles/r01ad)
-    int probe_min_spp = 64;        // renders with fewer samples per pixel skip the probe
-    int tile_key_mode = 2;         // variant 8: see crt_tile_cost_kernel (2: measured best, profiles/r01ac)
-    int n_cus = 0;
-    int variant = -1;              // see crt_renderer_set_kernel_variant; -1 = automatic
-    unsigned long long diag[3] = {0, 0, 0};
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // COUNT-mode section profile (variant 4)
-    int regen_threshold = 24;      // variants 2/3
-    int regen_threshold_wide = REGEN_THRESHOLD_WIDE;   // variants 4/7/8
-    int crit_tiles = -1;           // variant 8: leading tiles of the cost order regenerating at crit_threshold; -1 = 4 per CU
-    int tile_shard = 0, tile_shards = 1;   // pixel sharding (crt_renderer_set_pixel_shard)
-    int crit_threshold = 16;       // (measured: profiles/r02h, r02i)
-    int top_levels = -1;           // 4-wide variants: new rays' first node steps from LDS; -1 = CRT_TOP_LEVELS
-    int xcd_regions = 0;           // variant 8: XCD groups render screen strips (crt_xcd_order_kernel)
-    int probe_stride = 0;          // variant 8's cost probe: every probe_stride-th pixel in x and y (0 = automatic)
-    int temporal = 0;              // variant 7: tiles ordered by the previous variant-7 frame's rays per pixel
-    int drain_threshold = 0;       // variant 7: regeneration threshold once the pixel queue is empty (0 = unchanged)
-    int wave_drain = WAVE_DRAIN;   // variants 4/8: sixty-fourths of its live lanes a draining wave passes at
-    // variant 8, tail fill (crt_renderer_set_tail_fill): fill_tiles < 0 = automatic, 0 = off, else K with fill_spp = delta
-    int fill_tiles = -1, fill_spp = 0;
-    DevBuf<uint32_t> d_fill;           // the tail parts rendered by the main launch and by the sweep, then one flag per tile rank
-    PinnedBuf<uint32_t> h_fill;        // those two counts of the last render with tail fill (copied on its stream before ev1)
-    int last_fill[2] = {0, 0};         // K and delta of the last render (0, 0: rendered without tail fill)
-    hipEvent_t last_fill_ev = nullptr; // that render's ev1
-    DevBuf<uint32_t> d_pix_rays;     // variant 7 with the temporal order: rays per pixel of the last frame
-    DevBuf<uint32_t> d_tile_order;    // its tiles, most expensive first
-    bool pix_rays_valid = false;
-    int min_waves = 0;             // occupancy target (waves/SIMD); 0 = auto: 7 for variant 8 over >= 4 tiles per wave
-                                   // slot, 6 for the other 4-wide launches and variants 3 and 10, 5 for variants 0-2
-    DevBuf<uint32_t> d_ovf;        // variant 4: stack entries beyond the LDS part, per pixel
-    int stack_lds = STACK_LDS;     // variant 4: per-lane stack entries kept in LDS
-    float rcp_w = 1.f, rcp_h = 1.f; // RN(1 / width), RN(1 / height)
-    int fast_uv = 0;               // next_ray divides by uv_div (verified for this size at creation, uv_div_mismatches)
-    std::unique_ptr<WavefrontScratch> wavefront;    // crt_renderer_render_wavefront: batches of the handle, allocated on first use (crt_paths.h)
-    std::unique_ptr<AdaptiveState> adaptive;        // crt_renderer_render_adaptive: per-tile state of the handle, allocated on first use (crt_adaptive.h)
-    std::unique_ptr<DenoiseState> denoise;          // crt_renderer_compute_guides / crt_renderer_denoise: guides and colour buffers of the handle, allocated on first use (crt_denoise.h)
-    std::unique_ptr<ReprojectState> reproject;      // crt_renderer_reproject: history buffers of the handle, allocated on first use (crt_reproject.h)
-    std::unique_ptr<VarianceState> variance;        // crt_renderer_reproject_moments / crt_renderer_denoise_history_variance: moments and variance of the handle, allocated on first use (crt_variance.h)
-};
-
-namespace {
-int use_device(int dev) {
-    int n = 0;
-    HIP_TRY(hipGetDeviceCount(&n));
-    if (n <= 0) return set_error(CRT_ERR_NO_DEVICE, "no HIP device visible");
-    if (dev < 0 || dev >= n) return set_error(CRT_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(dev));
-    return CRT_OK;
-}
-
-// The renderer's camera and frame, the inputs of cam_regs(), into any kernel's parameter struct that carries them
-// (RenderParams, crt_paths.h's CameraRaysParams and PathAdvanceParams).
-template <class Params>
-void set_camera_frame(Params& P, const crt_renderer* R) {
-    P.cam = R->cam;
-    P.width = R->width; P.height = R->height;
-    P.rcp_w = R->rcp_w; P.rcp_h = R->rcp_h; P.fast_uv = R->fast_uv;
-}
-}  // namespace
-
-extern "C" {
-
-int crt_abi_version(void) { return CRT_ABI_VERSION; }
-int crt_build_flags(void) {
-#ifdef CRT_CHECKED
-    return CRT_BUILD_CHECKED;
-#else
-    return 0;
-#endif
-}
-const char* crt_last_error(void) { return g_last_error.c_str(); }
-
-int crt_device_count(int* out) {
-    if (!out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null out");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    *out = (e == hipSuccess) ? n : 0;
-    return CRT_OK;
-}
-
-int crt_scene_create(const crt_scene_desc* D, int device, crt_scene** out) {
-    return crt_scene_create_ex(D, device, nullptr, out);
-}
-
-}  // extern "C"
-
-// Host half of scene creation: flatten the reference BVHs (ranks, reachability) and, for CRT_BVH_REBUILT,
-// build the SAH tree.  Shared by crt_scene_create_ex and crt_scene_export.
-static int build_scene_arrays(const crt_scene_desc* D, const crt_scene_options* opts, crt_scene_options& o,
-                              Flattener& F, Rebuilt& RB, int gpu_device) {
-    o = crt_scene_options{};
-    if (opts) o = *opts;
-    if (o.bvh != CRT_BVH_REFERENCE && o.bvh != CRT_BVH_REBUILT) return set_error(CRT_ERR_INVALID_ARGUMENT, "unknown bvh mode");
-    if (o.leaf_size == 0) o.leaf_size = 4;
-    if (o.layouts == 0) o.layouts = 6;
-    if (o.traversal_cost == 0.f) o.traversal_cost = 2.f;   // measured optimum for 4-wide leaves <= 4 (profiles/r01i)
-    if (o.width == 0) o.width = 4;
-    if (o.width != 2 && o.width != 4) return set_error(CRT_ERR_INVALID_ARGUMENT, "width must be 2 or 4");
-    if (!(o.traversal_cost > 0.f && o.traversal_cost <= 64.f)) return set_error(CRT_ERR_INVALID_ARGUMENT, "traversal_cost must be in (0, 64]");
-    if (o.leaf_size < 1 || o.leaf_size > 16) return set_error(CRT_ERR_INVALID_ARGUMENT, "leaf_size must be 1..16");
-    if (o.layouts != 1 && o.layouts != 6) return set_error(CRT_ERR_INVALID_ARGUMENT, "layouts must be 1 or 6");
-    if (D->n_scene_nodes <= 0 || !D->scene_nodes) return set_error(CRT_ERR_INVALID_ARGUMENT, "scene has no BVH nodes");
-    if (D->n_materials < 0 || (D->n_materials > 0 && !D->materials)) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad materials");
-    SetupTrace tr;
-    if (!F.build_triangles()) return set_error(CRT_ERR_INVALID_ARGUMENT, "scene: " + F.err);
-    tr.lap("triangle records");
-    if (!F.emit_scene(0, 0, false)) return set_error(CRT_ERR_INVALID_ARGUMENT, "scene: " + F.err);
-    tr.lap("flatten reference BVHs");
-    F.finalize_ranks();
-    tr.lap("ranks");
-    if (o.bvh == CRT_BVH_REBUILT) {
-        if (o.width == 4) o.layouts = 1;
-        if (o.spatial_alpha == 0.f) o.spatial_alpha = 1e-5f;
-        if (o.spatial_max_dup == 0.f) o.spatial_max_dup = 1.f;
-        if (o.spatial_splits != 0 && o.spatial_splits != 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "spatial_splits must be 0 or 1");
-        if (!(o.spatial_alpha > 0.f && o.spatial_alpha <= 1.f) || !(o.spatial_max_dup > 0.f && o.spatial_max_dup <= 8.f))
-            return set_error(CRT_ERR_INVALID_ARGUMENT, "spatial_alpha must be in (0, 1], spatial_max_dup in (0, 8]");
-        if (!RB.build(F, o.leaf_size, o.layouts, o.traversal_cost, o.width, o.gpu_build && !o.spatial_splits ? gpu_device : -1,
-                      o.spatial_splits != 0, o.spatial_alpha, o.spatial_max_dup))
-            return set_error(CRT_ERR_INVALID_ARGUMENT, "scene: " + RB.err);
-        tr.lap("rebuilt tree (all)");
-        if ((size_t)RB.n_nodes * o.layouts * (o.width == 4 ? 8 : 2) >= (size_t)1 << 31)
-            return set_error(CRT_ERR_INVALID_ARGUMENT, "scene too large");
-    }
-    return CRT_OK;
-}
-
-extern "C" {
-
-int crt_scene_export(const crt_scene_desc* D, const crt_scene_options* opts, float* nodes, float* prims,
-                     int32_t* rank_code, int64_t info[10]) {
-    if (!D || !info) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    crt_scene_options o;
-    Flattener F{D};
-    Rebuilt RB;
-    if (int rc = build_scene_arrays(D, opts, o, F, RB, 0)) return rc;
-    const bool rebuilt = o.bvh == CRT_BVH_REBUILT;
-    const std::vector<float4>& N = rebuilt ? RB.nodes : F.nodes;
-    const std::vector<float4>& Pr = rebuilt ? RB.prims : F.prims;
-    const std::vector<int>& rc = rebuilt ? RB.rank_code : F.rank_code;
-    info[0] = (int64_t)N.size();
-    info[1] = (int64_t)Pr.size();
-    info[2] = (int64_t)rc.size();
-    info[3] = rebuilt ? RB.n_nodes : F.count();
-    info[4] = rebuilt ? o.layouts : 1;
-    info[5] = rebuilt ? RB.width : 2;
-    info[6] = rebuilt ? RB.stack_bound : 0;
-    info[7] = rebuilt ? RB.excluded : 0;
-    info[8] = rebuilt ? RB.sphere_first : 0;
-    info[9] = rebuilt ? RB.n_ray_spheres : 0;
-    if (nodes) std::memcpy(nodes, N.data(), N.size() * sizeof(float4));
-    if (prims) std::memcpy(prims, Pr.data(), Pr.size() * sizeof(float4));
-    if (rank_code) std::memcpy(rank_code, rc.data(), rc.size() * sizeof(int));
-    return CRT_OK;
-}
-
-// Per-rank shading records (layout in crt_device.h).  The triangle normal is unit(cross(e1, e2)) in the
-// device's f32 operation order (the library is compiled with -ffp-contract=off and IEEE sqrt / division on
-// the host too), so the record holds exactly the value shade() used to compute per hit.
-// What shade() needs of material `mat`: its SHADE_* code and payload (crt_device.h); an index outside the scene's
-// materials is SHADE_INVALID.  The one source of the per-rank shading records and of the per-material rows of the path
-// steps (crt_paths.h), so both hold the same bits.
-static uint32_t material_shade_row(const crt_scene_desc* D, uint32_t mat, float4& pay) {
-    pay = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (mat >= (uint32_t)D->n_materials) return SHADE_INVALID;
-    const crt_material_desc& M = D->materials[mat];
-    switch (M.type) {
-        case CRT_LAMBERTIAN: pay = make_float4(M.albedo[0], M.albedo[1], M.albedo[2], 0.f); return SHADE_LAMBERT;
-        case CRT_METAL:
-            pay = make_float4(M.albedo[0], M.albedo[1], M.albedo[2], M.roughness < 1.f ? M.roughness : 1.f);
-            return SHADE_METAL;
-        case CRT_DIELECTRIC: {
-            // Material.cuh:113 ri = front ? 1.0f / ior : ior, and Schlick's r0 = ((1 - ri) / (1 + ri))^2
-            // (:133-134) for both faces, in IEEE f32 as the device would compute them per hit
-            auto r0 = [](float r) { const float x = (1 - r) / (1 + r); return x * x; };
-            const float inv = 1.0f / M.ior;
-            pay = make_float4(M.ior, inv, r0(inv), r0(M.ior));
-            return SHADE_DIELECTRIC;
-        }
-        case CRT_DIFFUSE_LIGHT: pay = make_float4(M.emission[0], M.emission[1], M.emission[2], 0.f); return SHADE_LIGHT;
-        default: return SHADE_NOEMIT;
-    }
-}
-
-// The path steps' per-material table: 2 x float4 per material, (code, 0, 0, 0) (payload).
-static std::vector<float4> material_shade_rows(const crt_scene_desc* D) {
-    std::vector<float4> out;
-    out.reserve(2 * (size_t)std::max(D->n_materials, 0));
-    for (int i = 0; i < D->n_materials; ++i) {
-        float4 pay;
-        const uint32_t code = material_shade_row(D, (uint32_t)i, pay);
-        out.push_back(make_float4(i2f((int)code), 0.f, 0.f, 0.f));
-        out.push_back(pay);
-    }
-    return out;
-}
-
-static std::vector<float4> shading_records(const std::vector<int>& rank_code, const std::vector<float4>& prims,
-                                           const crt_scene_desc* D) {
-    std::vector<float4> out(3 * rank_code.size(), make_float4(0.f, 0.f, 0.f, 0.f));
-    parallel_ranges(rank_code.size(), [&](size_t rb, size_t re) {
-        for (size_t r = rb; r < re; ++r) {
-            const bool sphere = (rank_code[r] & SPHERE_BIT) != 0;
-            const size_t p = (size_t)(rank_code[r] & ~SPHERE_BIT);
-            const float4 f0 = prims[3 * p], f1 = prims[3 * p + 1], f2 = prims[3 * p + 2];
-            const uint32_t mat = (uint32_t)i2i_host(sphere ? f1.y : f2.y);
-            float4 pay;
-            const uint32_t code = material_shade_row(D, mat, pay);
-            float4 a;
-            if (sphere) {
-                a = make_float4(f0.x, f0.y, f0.z, i2f((int)(code | SHADE_SPHERE)));
-                out[3 * r + 2] = make_float4(1 / f0.w, 0.f, 0.f, 0.f);
-            } else {
-                const float ux = f0.w, uy = f1.x, uz = f1.y, vx = f1.z, vy = f1.w, vz = f2.x;
-                const float cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
-                const float s = 1.0f / std::sqrt(cx * cx + cy * cy + cz * cz);
-                a = make_float4(s * cx, s * cy, s * cz, i2f((int)code));
-            }
-            out[3 * r] = a;
-            out[3 * r + 1] = pay;
-        }
-    });
-    return out;
-}
-
-// Per-rank identity of the ray queries' hit record: (object, primitive, material, 0) of the primitive with reference
-// DFS rank r.  Built from the Flattener alone, so it is the same table for every bvh mode of one description.
-// object = mesh index, or -1 - index in D->spheres; primitive = triangle within its mesh after the build permutation
-// (0 for a sphere); material = the record's material word (the index shade() uses, out of range or not).
-static std::vector<int32_t> identity_table(const Flattener& F) {
-    const size_t n_tri = F.prims.size() / 3 - F.sphere_of.size();
-    std::vector<int32_t> out(4 * F.rank_code.size(), 0);
-    for (size_t r = 0; r < F.rank_code.size(); ++r) {
-        const bool sphere = (F.rank_code[r] & SPHERE_BIT) != 0;
-        const size_t p = (size_t)(F.rank_code[r] & ~SPHERE_BIT);
-        int32_t* o = out.data() + 4 * r;
-        if (sphere) {
-            o[0] = -1 - F.sphere_of[p - n_tri];
-            o[1] = 0;
-            o[2] = i2i_host(F.prims[3 * p + 1].y);
-        } else {
-            const size_t m = (size_t)(std::upper_bound(F.mesh_prim_base.begin(), F.mesh_prim_base.end(), (int)p) -
-                                      F.mesh_prim_base.begin()) - 1;
-            o[0] = (int32_t)m;
-            o[1] = (int32_t)(p - (size_t)F.mesh_prim_base[m]);
-            o[2] = i2i_host(F.prims[3 * p + 2].y);
-        }
-    }
-    return out;
-}
-
-int crt_scene_export_identity(const crt_scene_desc* D, const crt_scene_options* opts, int32_t* out, int64_t* n_ranks) {
-    if (!D || !n_ranks) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    crt_scene_options o;
-    Flattener F{D};
-    Rebuilt RB;
-    if (int rc = build_scene_arrays(D, opts, o, F, RB, 0)) return rc;
-    const std::vector<int32_t> id = identity_table(F);
-    *n_ranks = (int64_t)F.rank_code.size();
-    if (out)
-        for (size_t r = 0; r < F.rank_code.size(); ++r) std::memcpy(out + 3 * r, id.data() + 4 * r, 3 * sizeof(int32_t));
-    return CRT_OK;
-}
-
-int crt_scene_create_ex(const crt_scene_desc* D, int device, const crt_scene_options* opts, crt_scene** out) {
-    if (!D || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    crt_scene_options o;
-    Flattener F{D};
-    Rebuilt RB;
-    if (int rc = build_scene_arrays(D, opts, o, F, RB, device)) return rc;
-    SetupTrace tr;
-    const bool rebuilt = o.bvh == CRT_BVH_REBUILT;
-    std::vector<float4> mats;
-    for (int i = 0; i < D->n_materials; ++i) {
-        const crt_material_desc& M = D->materials[i];
-        mats.push_back(make_float4(i2f(M.type), M.albedo[0], M.albedo[1], M.albedo[2]));
-        mats.push_back(make_float4(M.emission[0], M.emission[1], M.emission[2], M.roughness < 1.f ? M.roughness : 1.f));
-        mats.push_back(make_float4(M.ior, 0.f, 0.f, 0.f));
-    }
-    if (int rc = use_device(device)) return rc;
-    crt_scene* S = new (std::nothrow) crt_scene;
-    if (!S) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-    S->device = device;
-    S->bvh = o.bvh;
-    S->layouts = rebuilt ? o.layouts : 1;
-    S->n_nodes = rebuilt ? RB.n_nodes : F.count();
-    S->n_prims = (int)((rebuilt ? RB.prims : F.prims).size() / 3);
-    S->n_ranks = (int)F.rank_code.size();
-    S->n_mats = D->n_materials;
-    S->max_depth = rebuilt ? RB.max_depth : F.max_depth;
-    S->excluded = rebuilt ? RB.excluded : 0;
-    S->width = rebuilt ? RB.width : 2;
-    S->stack_cap = rebuilt ? (o.stack_cap > 0 ? o.stack_cap : RB.stack_bound) : 0;
-    S->stack_bound = rebuilt ? RB.stack_bound : 0;
-    S->sphere_first = rebuilt ? RB.sphere_first : 0;
-    S->spatial_splits = rebuilt ? RB.spatial_splits : 0;
-    S->references = rebuilt ? RB.references : 0;
-    {
-        int in_tree = 0;   // spheres the 4-wide tree itself holds (not tested per ray)
-        if (rebuilt)
-            for (int r = 0; r < (int)RB.rank_code.size(); ++r)
-                if ((RB.rank_code[r] & SPHERE_BIT) && (RB.rank_code[r] & ~SPHERE_BIT) < RB.sphere_first) ++in_tree;
-        S->tree_spheres = in_tree > 0 || !rebuilt;
-    }
-    if (rebuilt && RB.n_ray_spheres == 2) {
-        for (int s = 0; s < 2; ++s) {
-            const size_t q = 3 * (size_t)(RB.sphere_first + s);
-            const float4 f0 = RB.prims[q], f1 = RB.prims[q + 1];
-            const int k = i2i_host(f1.w);
-            const float4 A = RB.chain[2 * (size_t)k], B = RB.chain[2 * (size_t)k + 1];
-            const float v[12] = {f0.x, f0.y, f0.z, f1.x, f1.z, A.x, A.y, A.z, A.w, B.x, B.y, 0.f};
-            std::memcpy(S->sph2[s], v, sizeof v);
-        }
-    }
-    S->n_chain = rebuilt ? (int)(RB.chain.size() / 2) : 0;
-    S->n_ray_spheres = rebuilt ? RB.n_ray_spheres : 0;
-    auto up = [&](DevBuf<float4>& dst, const std::vector<float4>& src) -> hipError_t {
-        hipError_t e = dst.alloc(src.size());
-        if (e == hipSuccess && !src.empty())
-            e = hipMemcpy(dst.get(), src.data(), src.size() * sizeof(float4), hipMemcpyHostToDevice);
-        return e;
-    };
-    const std::vector<int>& rc = rebuilt ? RB.rank_code : F.rank_code;
-    std::vector<float4> swizzled;   // width 4: row k of node n at slot k ^ (n & 7) of its record (node_row)
-    if (S->width == 4) {
-        swizzled.resize(RB.nodes.size());
-        for (size_t n = 0; n < RB.nodes.size() / 8; ++n)
-            for (size_t k = 0; k < 8; ++k) swizzled[8 * n + (k ^ (n & 7))] = RB.nodes[8 * n + k];
-    }
-    tr.lap("node swizzle");
-    const std::vector<float4> shade = shading_records(rc, rebuilt ? RB.prims : F.prims, D);
-    tr.lap("shading records");
-    const std::vector<int32_t> ident = identity_table(F);
-    const std::vector<float4> mat_rows = material_shade_rows(D);
-    hipError_t e;
-    if ((e = up(S->d_nodes, S->width == 4 ? swizzled : (rebuilt ? RB.nodes : F.nodes))) != hipSuccess ||
-        (e = up(S->d_prims, rebuilt ? RB.prims : F.prims)) != hipSuccess ||
-        (e = up(S->d_mats, mats)) != hipSuccess ||
-        (e = up(S->d_chain, rebuilt ? RB.chain : std::vector<float4>())) != hipSuccess ||
-        (e = up(S->d_shade, shade)) != hipSuccess ||
-        (e = up(S->d_mat_rows, mat_rows)) != hipSuccess ||
-        (e = S->d_ident.alloc(ident.size() / 4)) != hipSuccess ||   // four words per rank
-        (!ident.empty() && (e = hipMemcpy(S->d_ident.get(), ident.data(), ident.size() * sizeof(int32_t),
-                                          hipMemcpyHostToDevice)) != hipSuccess)) {
-        crt_scene_destroy(S);
-        return set_error(CRT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
-    }
-    tr.lap("uploads");
-    // the uploads above are null-stream copies: wait for them here, once per handle, so that a caller may trace or
-    // render over the scene on any stream (a non-blocking one too) as soon as it holds the handle
-    if ((e = hipStreamSynchronize(0)) != hipSuccess) {
-        crt_scene_destroy(S);
-        return set_error(CRT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
-    }
-    *out = S;
-    return CRT_OK;
-}
-
-int crt_scene_get_stats(const crt_scene* S, crt_scene_stats* out) {
-    if (!S || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    out->device_nodes = (int64_t)S->n_nodes * S->layouts;
-    out->width = S->width;
-    out->stack_bound = S->stack_cap;
-    out->spatial_splits = S->spatial_splits;
-    out->references = S->references;
-    out->device_prims = S->n_prims;
-    out->device_bytes = (int64_t)S->n_nodes * S->layouts * (S->width == 4 ? 128 : 32) + (int64_t)S->n_prims * 48 + (int64_t)S->n_mats * 48 +
-                        (int64_t)S->n_ranks * 48;
-    out->max_depth = S->max_depth;
-    out->n_materials = S->n_mats;
-    out->bvh = S->bvh;
-    out->layouts = S->layouts;
-    out->excluded_prims = S->excluded;
-    return CRT_OK;
-}
-
-void crt_scene_destroy(crt_scene* S) {
-    if (!S) return;
-    (void)hipSetDevice(S->device);
-    delete S;
-}
-
-namespace {
-// Mismatches of uv_div(a, b, RN(1 / b)) against a / b over every a next_ray can form for an image dimension b:
-// a = fl(x + U) with x in [0, b - 1] and U = fl(X * 2^-32 + 2^-33) in [2^-33, 1], so a in [2^-33, b].
-constexpr uint32_t UV_A_MIN_BITS = 0x2f000000u;   // 2^-33
-int uv_div_mismatches(int dim, unsigned long long* out) {
-    const float b = (float)dim, r = 1.0f / b;
-    uint32_t hi;
-    std::memcpy(&hi, &b, 4);
-    DevBuf<unsigned long long> d;
-    HIP_TRY(d.alloc(1));
-    HIP_TRY(hipMemset(d.get(), 0, 8));
-    hipLaunchKernelGGL(crt_uv_div_check_kernel, dim3(4096), dim3(256), 0, 0, b, r, UV_A_MIN_BITS, hi, d.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d.get(), 8, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-}  // namespace
-
-int crt_selftest_uv_div(int dim, unsigned long long* mismatches) {
-    if (dim <= 0 || !mismatches) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    return uv_div_mismatches(dim, mismatches);
-}
-
-static hipError_t create_timing_ring(crt_renderer* R) {
-    for (auto& slot : R->ring)
-        for (DevEvent& ev : slot)
-            if (hipError_t e = ev.create(); e != hipSuccess) return e;
-    return hipSuccess;
-}
-
-int crt_renderer_create(int width, int height, int device, crt_renderer** out) {
-    if (!out || width <= 0 || height <= 0 || (long long)width * height > (1LL << 31) / 6)
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad renderer size");
-    *out = nullptr;
-    if (int rc = use_device(device)) return rc;
-    crt_renderer* R = new (std::nothrow) crt_renderer;
-    if (!R) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-    R->device = device; R->width = width; R->height = height;
-    const size_t n = (size_t)width * height;
-    const auto& tab = seq_tables();
-    hipError_t e;
-    if ((e = R->d_rng.alloc(n * 6)) != hipSuccess ||
-        (e = R->d_sum_own.alloc(n * 3)) != hipSuccess ||
-        (e = R->d_rgba.alloc(n * 4)) != hipSuccess ||
-        (e = R->d_seq.alloc(tab.size())) != hipSuccess ||
-        (e = R->d_counters.alloc(16)) != hipSuccess ||
-        (e = hipMemcpy(R->d_seq.get(), tab.data(), tab.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemset(R->d_sum_own.get(), 0, n * 3 * 4)) != hipSuccess ||
-        (e = hipMemset(R->d_rgba.get(), 0, n * 4)) != hipSuccess ||
-        (e = hipMemset(R->d_counters.get(), 0, 16 * sizeof(unsigned long long))) != hipSuccess ||
-        (e = create_timing_ring(R)) != hipSuccess) {
-        crt_renderer_destroy(R);
-        return set_error(e == hipErrorOutOfMemory ? CRT_ERR_OUT_OF_MEMORY : CRT_ERR_HIP,
-                         std::string("renderer allocation: ") + hipGetErrorString(e));
-    }
-    R->d_sum = R->d_sum_own.get();
-    // next_ray's image-coordinate divisions: uv_div when it equals the IEEE division for every input of this size
-    unsigned long long bad_w = 0, bad_h = 0;
-    int rc = uv_div_mismatches(width, &bad_w);
-    if (rc == CRT_OK) rc = height == width ? CRT_OK : uv_div_mismatches(height, &bad_h);
-    if (rc != CRT_OK) {
-        crt_renderer_destroy(R);
-        return rc;
-    }
-    R->rcp_w = 1.0f / (float)width;
-    R->rcp_h = 1.0f / (float)height;
-    R->fast_uv = bad_w == 0 && bad_h == 0;
-    // the table's copy, the three clears and the division checks ran on the null stream: wait for them here, once per
-    // handle, so that the first call may come on any stream (a non-blocking one too)
-    if ((e = hipStreamSynchronize(0)) != hipSuccess) {
-        crt_renderer_destroy(R);
-        return set_error(CRT_ERR_HIP, std::string("renderer initialisation: ") + hipGetErrorString(e));
-    }
-    *out = R;
-    return CRT_OK;
-}
-
-int crt_renderer_attach_linear(crt_renderer* R, float* ptr) {
-    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "null renderer");
-    if (ptr) {
-        hipPointerAttribute_t attr;
-        HIP_TRY(hipPointerGetAttributes(&attr, ptr));
-        if (attr.type != hipMemoryTypeDevice || attr.device != R->device)
-            return set_error(CRT_ERR_INVALID_ARGUMENT, "attach_linear: not device memory of the renderer's device");
-    }
-    R->d_sum = ptr ? ptr : R->d_sum_own.get();
-    return CRT_OK;
-}
-
-void crt_renderer_destroy(crt_renderer* R) {
-    if (!R) return;
-    (void)hipSetDevice(R->device);
-    delete R;
-}
-
-int crt_renderer_init_rand(crt_renderer* R, unsigned long long seed, unsigned long long subseq_base, void* stream) {
-    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "null renderer");
-    HIP_TRY(hipSetDevice(R->device));
-    const int n = R->width * R->height;
-    hipStream_t st = (hipStream_t)stream;
-    // curand_init is a pure function of (seed, subsequence): keep the initialised array and copy it back for a
-    // repeated (seed, base) — 2.8 ms of GF(2) jumps at 2560x1440 become a 35 us device copy, same bits
-    if (R->rng_cache_valid && R->rng_cache_seed == seed && R->rng_cache_base == subseq_base) {
-        HIP_TRY(hipMemcpyAsync(R->d_rng.get(), R->d_rng_cache.get(), (size_t)n * 24, hipMemcpyDeviceToDevice, st));
-        return CRT_OK;
-    }
-    hipLaunchKernelGGL(crt_init_rand_kernel, dim3((n + 255) / 256), dim3(256), 0, st, R->d_rng.get(),
-                       R->d_seq.get(), n, seed, subseq_base);
-    HIP_TRY(hipGetLastError());
-    R->rng_cache_valid = false;
-    if (!R->d_rng_cache) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (R->d_rng_cache.alloc((size_t)n * 6) != hipSuccess) {   // optional: no cache then
-            (void)hipGetLastError();
-            return CRT_OK;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(R->d_rng_cache.get(), R->d_rng.get(), (size_t)n * 24, hipMemcpyDeviceToDevice, st));
-    R->rng_cache_seed = seed;
-    R->rng_cache_base = subseq_base;
-    R->rng_cache_valid = true;
-    return CRT_OK;
-}
-
-int crt_renderer_set_kernel_variant(crt_renderer* R, int variant) {
-    if (!R || variant < -1 || variant > 10 || variant == 5 || variant == 6 || variant == 9)
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad kernel variant (-1 = automatic, 0-4, 7, 8, 10)");
-    R->variant = variant;
-    return CRT_OK;
-}
-
-int crt_renderer_set_schedule(crt_renderer* R, int probe_spp, int min_spp, int flags) {
-    if (!R || probe_spp < -1 || probe_spp > 64 || min_spp < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad schedule");
-    const int stride = (flags >> 20) & 0xf;   // variant 8's probe subsampling: 0 = automatic, 1 (every pixel), 2, 4
-    if (stride != 0 && stride != 1 && stride != 2 && stride != 4)   // checked before any field changes
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "probe stride (flags >> 20): 0, 1, 2 or 4");
-    R->probe_spp = probe_spp < 0 ? -1 : probe_spp;
-    R->probe_min_spp = min_spp;
-    R->tile_key_mode = (flags >> 16) & 0xf;   // 0 = slowest pixel (callers that pass 0 get the plain key)
-    R->probe_stride = stride;
-    return CRT_OK;
-}
-
-int crt_renderer_set_pixel_shard(crt_renderer* R, int shard, int shards) {
-    if (!R || shards < 1 || shard < 0 || shard >= shards) return set_error(CRT_ERR_INVALID_ARGUMENT, "shard in [0, shards)");
-    const int n_tiles = ((R->width + 7) / 8) * ((R->height + 7) / 8);
-    if (shards > n_tiles) return set_error(CRT_ERR_INVALID_ARGUMENT, "more shards than 8x8 tiles");
-    R->tile_shard = shard;
-    R->tile_shards = shards;
-    return CRT_OK;
-}
-
-int crt_renderer_set_top_levels(crt_renderer* R, int levels) {
-    if (!R || levels < -1 || levels > CRT_TOP_LEVELS)
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "top levels -1 (default) .. " + std::to_string(CRT_TOP_LEVELS));
-    R->top_levels = levels;
-    return CRT_OK;
-}
-
-int crt_renderer_set_critical_tiles(crt_renderer* R, int tiles, int lanes) {
-    if (!R || tiles < -1 || lanes < 1 || lanes > 64) return set_error(CRT_ERR_INVALID_ARGUMENT, "critical tiles >= -1, lanes 1..64");
-    R->crit_tiles = tiles;
-    R->crit_threshold = lanes;
-    return CRT_OK;
-}
-
-int crt_renderer_set_occupancy_target(crt_renderer* R, int waves_per_simd) {
-    if (!R || waves_per_simd < 0 || waves_per_simd > 8) return set_error(CRT_ERR_INVALID_ARGUMENT, "waves per SIMD 0..8");
-    R->min_waves = waves_per_simd;
-    return CRT_OK;
-}
-
-int crt_renderer_set_stack_lds(crt_renderer* R, int entries) {
-    if (!R || entries < 1 || entries > STACK_LDS) return set_error(CRT_ERR_INVALID_ARGUMENT, "stack LDS entries 1..16");
-    R->stack_lds = entries;
-    return CRT_OK;
-}
-
-int crt_renderer_set_regen_threshold(crt_renderer* R, int lanes) {
-    if (!R || lanes < 1 || lanes > 64) return set_error(CRT_ERR_INVALID_ARGUMENT, "threshold must be 1..64");
-    R->regen_threshold = lanes;
-    R->regen_threshold_wide = lanes;
-    return CRT_OK;
-}
-
-int crt_renderer_set_camera(crt_renderer* R, const crt_camera_desc* cam) {
-    if (!R || !cam) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    // primary rays start within lens_radius of the origin (right/up are unit vectors); the 4-wide slab test needs
-    // |o| * 2^64 finite (box_inv), the same 2^60 bound the rebuilt tree's boxes are held to
-    bool ok = std::isfinite(cam->lens_radius) && std::fabs(cam->lens_radius) < 0x1p58f;
-    for (int a = 0; a < 3; ++a) ok = ok && std::isfinite(cam->origin[a]) && std::fabs(cam->origin[a]) < 0x1p59f;
-    if (!ok) return set_error(CRT_ERR_INVALID_ARGUMENT, "camera origin or lens radius non-finite or beyond 2^59");
-    R->cam = *cam;
-    R->has_camera = true;
-    return CRT_OK;
-}
-
-// Cost-probe samples for a render of `spp` samples per pixel (0 = no probe).
-static int probe_spp_for(const crt_renderer* R, int spp) {
-    if (spp < R->probe_min_spp || R->probe_spp == 0) return 0;
-    return R->probe_spp > 0 ? R->probe_spp : (spp >= 1000 ? 4 : 2);
-}
-
-// ---- render dispatch: every instantiation of crt_render_kernel the library launches, one row per (VARIANT, MINW) ----
-using RenderKernel = void (*)(RenderParams);
-struct RenderRow {
-    int variant, w;
-    RenderKernel plain, counting;   // COUNT = false / true; counting is null where that kernel is not built
-    RenderKernel open;              // variant 8: the plain kernel's open twin (crt_render_open_kernel); else null
-};
-#define CRT_ROW(V, W) {V, W, crt_render_kernel<false, V, W>, crt_render_kernel<true, V, W>, nullptr}
-#define CRT_ROW_PLAIN8(W) {8, W, crt_render_kernel<false, 8, W>, nullptr, crt_render_open_kernel<8, W>}
-#define CRT_ROW8(W) {8, W, crt_render_kernel<false, 8, W>, crt_render_kernel<true, 8, W>, crt_render_open_kernel<8, W>}
-static constexpr RenderRow RENDER_ROWS[] = {
-    CRT_ROW(0, 1), CRT_ROW(1, 1),
-    CRT_ROW(2, 1), CRT_ROW(2, 5), CRT_ROW(2, 6), CRT_ROW(2, 8),
-    CRT_ROW(3, 1), CRT_ROW(3, 4), CRT_ROW(3, 5), CRT_ROW(3, 6),
-    CRT_ROW(4, 1), CRT_ROW(4, 4), CRT_ROW(4, 5), CRT_ROW(4, 6), CRT_ROW(4, 7),
-    CRT_ROW(7, 5), CRT_ROW(7, 6), CRT_ROW(7, 7),
-    CRT_ROW_PLAIN8(4),   // the row prefetch (profiles/r06r, r06s); the counting kernel runs at 5
-    CRT_ROW8(5), CRT_ROW8(6), CRT_ROW8(7),
-    CRT_ROW(10, 5), CRT_ROW(10, 6), CRT_ROW(10, 7),
-};
-#undef CRT_ROW
-#undef CRT_ROW_PLAIN8
-#undef CRT_ROW8
-
-// The row of `variant` for an occupancy target of `occ` waves per SIMD: the largest built MINW <= occ, else the
-// smallest built.  Returns an index into RENDER_ROWS.
-static constexpr int render_row(int variant, bool cnt, int occ) {
-    int best = -1, smallest = -1;
-    for (int i = 0; i < (int)(sizeof RENDER_ROWS / sizeof RENDER_ROWS[0]); ++i) {
-        const RenderRow& r = RENDER_ROWS[i];
-        if (r.variant != variant || (cnt && !r.counting)) continue;
-        if (r.w <= occ && (best < 0 || r.w > RENDER_ROWS[best].w)) best = i;
-        if (smallest < 0 || r.w < RENDER_ROWS[smallest].w) smallest = i;
-    }
-    return best >= 0 ? best : smallest;
-}
-// MINW chosen at occ = 1..8, one decimal digit each
-static constexpr int render_row_digits(int variant, bool cnt) {
-    int d = 0;
-    for (int occ = 1; occ <= 8; ++occ) d = d * 10 + RENDER_ROWS[render_row(variant, cnt, occ)].w;
-    return d;
-}
-static_assert(render_row_digits(4, false) == 11145677 && render_row_digits(4, true) == 11145677, "variant 4");
-static_assert(render_row_digits(7, false) == 55555677 && render_row_digits(7, true) == 55555677, "variant 7");
-static_assert(render_row_digits(8, false) == 44445677, "variant 8, plain");
-static_assert(render_row_digits(8, true) == 55555677, "variant 8, counting");
-static_assert(render_row_digits(10, false) == 55555677 && render_row_digits(10, true) == 55555677, "variant 10");
-static_assert(render_row_digits(3, false) == 11145666 && render_row_digits(3, true) == 11145666, "variant 3");
-static_assert(render_row_digits(2, false) == 11115668 && render_row_digits(2, true) == 11115668, "variant 2");
-static_assert(render_row_digits(0, false) == 11111111 && render_row_digits(0, true) == 11111111, "variant 0");
-static_assert(render_row_digits(1, false) == 11111111 && render_row_digits(1, true) == 11111111, "variant 1");
-
-// Whether a launch of `row` with P over scene S may run the frozen twin: the plain variant-8 kernel, and every fact
-// that crt_render_body.inc holds as a constant when FROZEN is true of this launch.  A knob moved by a setter, another
-// per-ray sphere count, spheres in the tree, fewer LDS stack entries than the kernel's or a probe launch runs the open
-// twin, and so does a scene with a stack_cap override (a testing option that must report what it drops).  The stack
-// fact is "an entry below the kernel's LDS entries is kept in LDS": P.stack_lds is all of them, or it is the tree's
-// own bound and that bound lies within them, so no traversal reaches an entry where the twins could differ.
-static bool render_launch_frozen(const RenderRow& row, bool cnt, const RenderParams& P, const crt_scene* S) {
-    if (!row.open || cnt) return false;
-    const int sd = wide_stack_entries(row.w);
-    const bool own_bound = S->stack_cap == S->stack_bound;   // no stack_cap override
-    const bool stack = own_bound && (P.stack_lds == sd || (S->stack_cap < sd && P.stack_lds == S->stack_cap));
-    return stack && P.top_levels == CRT_TOP_LEVELS && P.tree_spheres == 0 && P.n_ray_spheres == 2 && P.n_layouts == 1 &&
-           !P.probe_cost && !P.pix_rays && P.wave_drain == WAVE_DRAIN && P.regen_threshold == REGEN_THRESHOLD_WIDE;
-}
-
-// The main launch of a render: names it (rocprofv3's spelling; both twins of a plain variant-8 kernel carry the frozen
-// one's name, crt_renderer_last_launch_frozen tells them apart), records ev_main immediately before it.  S: the scene,
-// required for the rows that have twins (variant 8), where the choice of the twin reads it.
-static int launch_render(crt_renderer* R, const RenderRow& row, bool cnt, dim3 grid, dim3 block, hipStream_t st,
-                         const RenderParams& P, const crt_scene* S = nullptr) {
-    std::snprintf(R->kernel_name, sizeof R->kernel_name, "crt_render_kernel<%s, %d, %d>", cnt ? "true" : "false",
-                  row.variant, row.w);
-    if (row.open && !S) return set_error(CRT_ERR_INVALID_ARGUMENT, "launch_render: a variant-8 launch needs its scene");
-    R->last_frozen = render_launch_frozen(row, cnt, P, S) ? 1 : 0;
-    HIP_TRY(hipEventRecord(R->ev_main, st));
-    RenderParams Q = P;
-    // frozen: the stack fact as the kernel states it (a smaller own bound: see above)
-    if (R->last_frozen) Q.stack_lds = wide_stack_entries(row.w);
-    const RenderKernel kernel = R->last_frozen ? row.plain : cnt ? row.counting : row.open ? row.open : row.plain;
-    R->last_fill[0] = R->last_fill[1] = 0;
-    if (row.variant != 8 || !P.queue) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, st, Q);
-        return CRT_OK;
-    }
-    // Tail fill (render_tiles set it up; fill_prologue): the grid's blocks are the heads, K tail parts follow them, and
-    // a sweep of tail parts only renders the ranks whose tail part found its head unfinished.  Both launches lie
-    // between ev_main and ev1.
-    const int k = P.drain_threshold, delta = P.probe_stride;
-    HIP_TRY(hipMemsetAsync(R->d_fill.get(), 0, ((size_t)k + 2) * sizeof(uint32_t), st));
-    Q.n_slots = (int)grid.x;
-    hipLaunchKernelGGL(kernel, dim3(grid.x + (unsigned)k), block, 0, st, Q);
-    Q.n_slots = 0;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)k), block, 0, st, Q);
-    HIP_TRY(hipMemcpyAsync(R->h_fill.get(), R->d_fill.get(), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    R->last_fill[0] = k;
-    R->last_fill[1] = delta;
-    R->last_fill_ev = R->ev1;
-    return CRT_OK;
-}
-
-// Order, queue, probe-cost and sort buffers of the tile and pixel-queue schedules, allocated on first use (one stream
-// synchronisation before the first allocation), and the device's CU count.
-static int ensure_order_buffers(crt_renderer* R, hipStream_t st, size_t n_pix, int n_tiles, bool want_tile_key) {
-    if (R->d_order && (R->d_tile_key || !want_tile_key)) return CRT_OK;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (!R->d_order) {
-        HIP_TRY(R->d_order.alloc(std::max(n_pix, (size_t)n_tiles * 64)));
-        HIP_TRY(R->d_queue.alloc(1));
-        HIP_TRY(R->d_tile_cost.alloc(n_pix));
-        HIP_TRY(R->d_order_hist.alloc(ORDER_KEYS));
-        HIP_TRY(R->d_fill.alloc((size_t)n_tiles + 2));
-        HIP_TRY(R->h_fill.alloc(2));
-        HIP_TRY(hipDeviceGetAttribute(&R->n_cus, hipDeviceAttributeMultiprocessorCount, R->device));
-    }
-    if (want_tile_key && !R->d_tile_key) HIP_TRY(R->d_tile_key.alloc((size_t)n_tiles));
-    return CRT_OK;
-}
-
-// out = the indices 0..n-1, largest key first (counting sort over ORDER_KEYS buckets).
-static int sort_descending(crt_renderer* R, hipStream_t st, const uint32_t* keys, int n, uint32_t* out) {
-    const unsigned ob = (unsigned)((n + ORDER_ITEMS - 1) / ORDER_ITEMS);
-    HIP_TRY(hipMemsetAsync(R->d_order_hist.get(), 0, ORDER_KEYS * 4, st));
-    hipLaunchKernelGGL(crt_order_hist_kernel, dim3(ob), dim3(256), 0, st, keys, n, R->d_order_hist.get());
-    hipLaunchKernelGGL(crt_order_scan_kernel, dim3(1), dim3(ORDER_KEYS), 0, st, R->d_order_hist.get());
-    hipLaunchKernelGGL(crt_order_scatter_kernel, dim3(ob), dim3(256), 0, st, keys, n, R->d_order_hist.get(), out, 0u);
-    return CRT_OK;
-}
-
-// After a cost probe wrote per-pixel costs (every stride-th pixel in x and y) to d_tile_cost: per-tile keys, this
-// shard's tiles most expensive first in d_order.  With `stats` the largest tile work and the total work are copied to
-// h_probe_stats on the stream (the caller synchronises).
-static int order_tiles_by_probe(crt_renderer* R, hipStream_t st, int stride, bool stats, int shard, int shards) {
-    const size_t n_pix = (size_t)R->width * R->height;
-    const int tiles_x = (R->width + 7) / 8, n_tiles = tiles_x * ((R->height + 7) / 8);
-    const dim3 tgrid((n_tiles + 255) / 256), tblock(256);
-    if (stats) {
-        if (!R->d_probe_stats) {
-            HIP_TRY(R->d_probe_stats.alloc(2));
-            HIP_TRY(R->h_probe_stats.alloc(2));
-        }
-        HIP_TRY(hipMemsetAsync(R->d_probe_stats.get(), 0, 2 * sizeof(unsigned long long), st));
-    }
-    hipLaunchKernelGGL(crt_tile_cost_kernel, tgrid, tblock, 0, st, R->d_tile_cost.get(), R->width, R->height, tiles_x, n_tiles,
-                       R->d_tile_key.get(), R->tile_key_mode, stride, stats ? R->d_probe_stats.get() : nullptr);
-    if (stats) HIP_TRY(hipMemcpyAsync(R->h_probe_stats.get(), R->d_probe_stats.get(), 2 * sizeof(unsigned long long),
-                                      hipMemcpyDeviceToHost, st));
-    if (R->tile_key_mode == 2) {   // per-pixel costs are no longer needed: reuse them for the smoothed keys
-        hipLaunchKernelGGL(crt_tile_neighbour_kernel, tgrid, tblock, 0, st, R->d_tile_key.get(), tiles_x, n_tiles, R->d_tile_cost.get());
-        HIP_TRY(hipMemcpyAsync(R->d_tile_key.get(), R->d_tile_cost.get(), (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, st));
-    }
-    if (shards > 1)
-        hipLaunchKernelGGL(crt_tile_shard_mask_kernel, tgrid, tblock, 0, st, R->d_tile_key.get(), n_tiles, shard, shards);
-    if (int rc = sort_descending(R, st, R->d_tile_key.get(), n_tiles, R->d_order.get())) return rc;
-    // XCD regions: the per-pixel costs are dead by now, so they hold the strips' lists and the pool (9 n_tiles)
-    if (R->xcd_regions && shards == 1 && tiles_x <= 2048 && n_pix >= (size_t)9 * n_tiles)
-        hipLaunchKernelGGL(crt_xcd_order_kernel, dim3(1), dim3(1024), 0, st, R->d_order.get(), R->d_tile_key.get(), n_tiles, tiles_x,
-                           R->d_tile_cost.get(), R->d_tile_cost.get() + (size_t)8 * n_tiles);
-    return CRT_OK;
-}
-
-// Pixel sharding without the probe: d_order[k] = this shard's k-th tile in row order.
-static void shard_tiles_in_row_order(crt_renderer* R, hipStream_t st, int n_tiles, int shard, int shards) {
-    hipLaunchKernelGGL(crt_shard_tiles_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_order.get(), n_tiles,
-                       shard, shards);
-}
-
-static RenderParams render_params(const crt_renderer* R, const crt_scene* S, int spp, int max_bounces, unsigned flags) {
-    RenderParams P{};   // no order, queue, probe costs, overflow stack or ray counts: the schedules set what they use
-    P.nodes = S->d_nodes.get(); P.prims = S->d_prims.get(); P.mats = S->d_mats.get(); P.shade = S->d_shade.get();
-    P.n_nodes = S->n_nodes; P.n_mats = S->n_mats; P.n_prims = S->n_prims; P.n_layouts = S->layouts;
-    P.err = reinterpret_cast<unsigned*>(R->d_counters.get() + ERR_WORD);
-    set_camera_frame(P, R);
-    P.spp = spp; P.max_bounces = max_bounces;
-    P.accumulate = (flags & CRT_RENDER_ACCUMULATE) ? 1 : 0;
-    P.rng = R->d_rng.get(); P.sum = R->d_sum; P.counters = R->d_counters.get();
-    P.probe_stride = 1;
-    P.crit_threshold = 64;
-    P.top_levels = R->top_levels < 0 ? CRT_TOP_LEVELS : R->top_levels;
-    P.stack_cap = S->stack_cap;
-    P.sphere_first = S->sphere_first;
-    P.n_ray_spheres = S->n_ray_spheres;
-    P.sphere_chain = S->d_chain.get();
-    P.n_chain = S->n_chain;
-    P.tree_spheres = S->tree_spheres;
-    std::memcpy(P.sph2, S->sph2, sizeof P.sph2);
-    P.regen_threshold = S->width == 4 ? R->regen_threshold_wide : R->regen_threshold;
-    P.drain_threshold = R->drain_threshold > 0 ? R->drain_threshold : P.regen_threshold;
-    P.wave_drain = R->wave_drain;
-    return P;
-}
-
-// 4-wide scenes: variant 4 / 7 / 8 when selected explicitly; otherwise the measured best (profiles/r01w): 8
-// (probe-ordered tiles, one wave per workgroup) when the render runs the cost probe, 7 (lanes refill from a pixel
-// queue) for short renders such as the 1-spp interactive frames.  Pixel sharding is variant 8.
-// Threaded scenes (the bit-exact reference BVH, rebuilt width 2): variants 0-3 and 10 when selected explicitly;
-// otherwise 10 (variant 3 over probe-ordered 8x8 tiles, one wave per workgroup; -17 %, profiles/r03s) when the render
-// runs the cost probe, else 3.
-static int choose_variant(const crt_renderer* R, const crt_scene* S, int spp) {
-    const int v = R->variant;
-    const bool probe = probe_spp_for(R, spp) > 0;
-    if (R->tile_shards > 1) return 8;
-    if (S->width == 4) return v == 4 || v == 7 || v == 8 ? v : probe ? 8 : 7;
-    return (v >= 0 && v <= 3) || v == 10 ? v : probe ? 10 : 3;
-}
-
-// Per-lane stack entries in LDS at an occupancy target.  A stack_cap override below the LDS entries must still report
-// the entries it drops (crt_scene_options.stack_cap).
-static int stack_lds_for(const crt_renderer* R, const crt_scene* S, int occ) {
-    const int lds = std::min(R->stack_lds, occ >= 7 ? CRT_STACK7 : occ >= 6 ? CRT_STACK6 : STACK_LDS);
-    return S->width == 4 && S->stack_cap > 0 ? std::min(lds, S->stack_cap) : lds;
-}
-
-// Occupancy target (waves per SIMD): variant 8 runs at 7 (72 VGPRs, 8 LDS stack entries so that 28 one-wave
-// workgroups fit a CU's LDS; -2.4 % on config C, profiles/r03aj) when its frame has at least 4 tiles per wave slot,
-// else at 6, or at 4 with the row prefetch when the cost probe shows a chain-bound frame: a frame with few tiles per
-// slot can end with its most expensive tiles' sequential sample chains (config B, 2 tiles per slot: +3.3 % at 7,
-// profiles/r03ak), and the prefetch takes the node rows' wait off every iteration of a chain (B -8 % against
-// occupancy 6, profiles/r06r-r06u; where the frame is not chain-bound the lost waves cost more: the plain Cornell box
-// at 1280x720 +15 %, 1600x900 +17 %, C +24 %; profiles/r06y).  The other 4-wide variants run at 6, threaded scenes
-// at 5.
-// Variants 10 and 3 (threaded, bit-exact) run at 6 (80 VGPRs; -8.0 % and -4.8 % against 5, profiles/r03am, r03as).
-// *auto_small: variant 8, automatic occupancy, few tiles per slot: render_tiles picks 4 or 6 from the probe's statistics.
-static int choose_occupancy(const crt_renderer* R, const crt_scene* S, int variant, bool cnt, int spp, bool* auto_small) {
-    *auto_small = false;
-    if (R->min_waves) return R->min_waves;
-    if (variant != 8) return S->width == 4 || variant == 10 || variant == 3 ? 6 : 5;
-    const size_t n_tiles = (size_t)((R->width + 7) / 8) * ((R->height + 7) / 8) / (size_t)R->tile_shards;
-    // at least 4 tiles per wave slot: occupancy 7 (throughput).  Fewer: 6, or 4 when the cost probe's tile works
-    // show a chain-bound frame (decided after the sort, in render_tiles; without the probe there is nothing to
-    // decide on, and the tile count alone cannot tell: at 1280x720 the bunny gains 8 % at 4 and the plain Cornell
-    // box loses 16 %, profiles/r06x).  (The counting kernel keeps 6: its counts do not depend on the schedule.)
-    const int occ = n_tiles >= (size_t)4 * R->n_cus * 4 * 7 ? 7 : 6;   // n_cus: ensure_order_buffers
-    *auto_small = occ < 7 && !cnt && probe_spp_for(R, spp) > 0;
-    return occ;
-}
-
-// 4-wide scenes whose stack_cap exceeds the LDS entries: the region of the deeper entries, grown when needed.
-static int ensure_overflow_stack(crt_renderer* R, const crt_scene* S, hipStream_t st, RenderParams& P) {
-    if (S->width != 4 || S->stack_cap <= P.stack_lds) return CRT_OK;
-    const size_t need = (size_t)(S->stack_cap - P.stack_lds);
-    if (need * R->width * R->height * 4 >= ((size_t)1 << 32))
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "traversal-stack overflow region would exceed 4 GiB");
-    if (need * R->width * R->height > R->d_ovf.size()) {   // grow the overflow stack region (rarely needed)
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(R->d_ovf.grow(need * R->width * R->height));
-    }
-    P.ovf = R->d_ovf.get();
-    return CRT_OK;
-}
-
-// Variants 0-4: one 16x16 block of four waves per workgroup over the whole frame.
-static int render_grid(crt_renderer* R, hipStream_t st, const RenderParams& P, bool cnt, int variant, int occ) {
-    const dim3 grid((R->width + 15) / 16, (R->height + 15) / 16);
-    return launch_render(R, RENDER_ROWS[render_row(variant, cnt, occ)], cnt, grid, dim3(256), st, P);
-}
-
-// Variants 8 and 10: one 8x8 tile per one-wave workgroup, most expensive first by a cost probe (variant 4's counting
-// kernel for 8, variant 3's for 10, read-only); without the probe, tiles in row order.
-static int render_tiles(crt_renderer* R, const crt_scene* S, hipStream_t st, RenderParams& P, bool cnt, int spp,
-                        int variant, int occ, bool auto_small) {
-    const int tiles_x = (R->width + 7) / 8, n_tiles = tiles_x * ((R->height + 7) / 8);
-    const int shard = R->tile_shard, shards = R->tile_shards;   // one shard for threaded scenes (rejected otherwise)
-    P.tiles_x = tiles_x;
-    if (probe_spp_for(R, spp) > 0) {
-        RenderParams Q = P;
-        Q.spp = probe_spp_for(R, spp);
-        Q.accumulate = 0;
-        Q.probe_cost = R->d_tile_cost.get();
-        if (variant == 8) {
-            // every stride-th pixel in x and y; automatic: 2 below 1000 spp, where the probe is a larger share of the
-            // frame (a 250-spp rank share: probe 3.2 -> 1.2 ms, render -0.9 %; at 2000 spp the render is unchanged,
-            // profiles/r04f)
-            Q.probe_stride = R->probe_stride ? R->probe_stride : (spp >= 1000 ? 1 : 2);
-            const int ps = 16 * Q.probe_stride;
-            const dim3 pgrid((R->width + ps - 1) / ps, (R->height + ps - 1) / ps);
-            if (occ >= 6) hipLaunchKernelGGL((crt_render_kernel<true, 4, 6>), pgrid, dim3(256), 0, st, Q);
-            else hipLaunchKernelGGL((crt_render_kernel<true, 4, 5>), pgrid, dim3(256), 0, st, Q);
-        } else {
-            const dim3 grid((R->width + 15) / 16, (R->height + 15) / 16);
-            hipLaunchKernelGGL((crt_render_kernel<true, 3, 5>), grid, dim3(256), 0, st, Q);
-        }
-        if (int rc = order_tiles_by_probe(R, st, Q.probe_stride, auto_small, shard, shards)) return rc;
-        P.order = R->d_order.get();
-        if (variant == 8) {
-            P.crit_tiles = R->crit_tiles < 0 ? 4 * R->n_cus : R->crit_tiles;
-            P.crit_threshold = R->crit_threshold;
-        }
-        if (auto_small) {
-            // Chain-bound or not, from the probe's tile works: rho = the largest tile's work over the mean work per
-            // wave slot at occupancy 6 (this rank's share of the tiles when pixel-sharded).  rho > 1 means the most
-            // expensive tile alone outlasts an even spread of the frame over the slots; above CRT_CHAIN_RHO the frame
-            // runs at occupancy 4 with the row prefetch, which shortens every chain iteration (-9 %) and gives up a
-            // third of the wave slots (profiles/r06x, r06y: config B rho 2.0, -7.6 %; the plain Cornell box at the
-            // same size rho 0.8, +15 % at 4).  One host synchronisation after the sort.
-            HIP_TRY(hipStreamSynchronize(st));
-            const double mx = (double)R->h_probe_stats.get()[0];
-            const double mine = (double)R->h_probe_stats.get()[1] / shards;
-            const double rho = mine > 0 ? mx * (4.0 * R->n_cus * 6) / mine : 0.0;
-            if (rho > CRT_CHAIN_RHO) {
-                occ = 4;
-                P.stack_lds = stack_lds_for(R, S, occ);
-            }
-            R->last_schedule[0] = (float)rho;
-            R->last_schedule[2] = (float)mx;
-            R->last_schedule[3] = (float)(mine / std::max(1, n_tiles / shards));
-        }
-    } else if (shards > 1) {   // pixel shard without the probe: this shard's tiles in row order
-        shard_tiles_in_row_order(R, st, n_tiles, shard, shards);
-        P.order = R->d_order.get();
-    }
-    if (P.crit_tiles > 0) P.crit_tiles = (P.crit_tiles + shards - 1) / shards;
-    if (variant == 8) R->last_schedule[1] = (float)occ;
-    if (variant == 8 && !cnt && shards == 1 && R->fill_tiles != 0) {
-        // Tail fill (fill_prologue).  Automatic: where the launch is long against its items, i.e. the
-        // probe-ordered launch at the automatic occupancy 7 (at least 4 tiles per wave slot), the first
-        // CRT_FILL_TILES_NUM / CRT_FILL_TILES_DEN of the cost order hold back spp / CRT_FILL_SPP_DEN samples, unless that
-        // is fewer than CRT_FILL_MIN_SPP.  A delta outside 1..spp-1 renders without it.
-        int k = R->fill_tiles, delta = R->fill_spp;
-        if (k < 0) {
-            const bool on = CRT_FILL_AUTO && P.order && probe_spp_for(R, spp) > 0 && !R->min_waves && occ == 7;
-            k = on ? (int)((long long)n_tiles * CRT_FILL_TILES_NUM / CRT_FILL_TILES_DEN) : 0;
-            delta = spp / CRT_FILL_SPP_DEN;
-            if (delta < CRT_FILL_MIN_SPP) k = 0;
-        }
-        k = std::min(k, n_tiles);
-        if (k > 0 && delta >= 1 && delta <= spp - 1) {
-            P.queue = R->d_fill.get();     // the tail fill's arguments (see RenderParams)
-            P.drain_threshold = k;
-            P.probe_stride = delta;
-        }
-    }
-    const dim3 tgrid((unsigned)((n_tiles - shard + shards - 1) / shards));
-    return launch_render(R, RENDER_ROWS[render_row(variant, cnt, occ)], cnt, tgrid, dim3(64), st, P, S);
-}
-
-// Variant 7 without the probe: d_order = the n_tiles * 64 pixel slots of the 8x8 tiles, the tiles most expensive first
-// by d_pix_rays (temporal order, once a frame has written it) or in row order.  Allocates the temporal buffers on
-// first use (one stream synchronisation).
-static int order_tile_slots(crt_renderer* R, hipStream_t st) {
-    const size_t n_pix = (size_t)R->width * R->height;
-    const int tiles_x = (R->width + 7) / 8, n_tiles = tiles_x * ((R->height + 7) / 8);
-    const size_t n_tile_slots = (size_t)n_tiles * 64;
-    if (R->temporal && !R->d_pix_rays) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(R->d_pix_rays.alloc(n_pix));
-        HIP_TRY(R->d_tile_order.alloc((size_t)n_tiles));
-        if (!R->d_tile_key) HIP_TRY(R->d_tile_key.alloc((size_t)n_tiles));
-        R->pix_rays_valid = false;
-    }
-    const dim3 sgrid((unsigned)((n_tile_slots + 255) / 256));
-    if (R->temporal && R->pix_rays_valid) {
-        // the interactive loop's frames repeat the last frame's cost map: its rays per pixel -> tile keys (the
-        // slowest pixel, raised to 3/4 of the neighbours', as variant 8's probe keys) -> tiles most expensive
-        // first, so the long paths start early and the launch does not end with them (profiles/r04i: a 1-spp
-        // frame in row order spends its last 31 % draining)
-        hipLaunchKernelGGL(crt_tile_cost_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, R->d_pix_rays.get(),
-                           R->width, R->height, tiles_x, n_tiles, R->d_tile_order.get(), 0, 1, nullptr);
-        hipLaunchKernelGGL(crt_tile_neighbour_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st,
-                           R->d_tile_order.get(), tiles_x, n_tiles, R->d_tile_key.get());
-        if (int rc = sort_descending(R, st, R->d_tile_key.get(), n_tiles, R->d_tile_order.get())) return rc;
-        hipLaunchKernelGGL(crt_expand_tile_order_kernel, sgrid, dim3(256), 0, st, R->d_tile_order.get(), R->d_order.get(),
-                           R->width, R->height, (int)n_tile_slots);
-    } else {
-        hipLaunchKernelGGL(crt_order_tiles_kernel, sgrid, dim3(256), 0, st, R->d_order.get(), R->width, R->height,
-                           (int)n_tile_slots);
-    }
-    return CRT_OK;
-}
-
-// Variant 7: persistent workgroups whose lanes refill from a queue of pixel slots, ordered by a per-pixel cost probe,
-// by the previous frame's rays per pixel (temporal), or in 8x8-tile order.
-static int render_pixel_queue(crt_renderer* R, hipStream_t st, RenderParams& P, bool cnt, int spp, int occ) {
-    const size_t n_pix = (size_t)R->width * R->height;
-    const size_t n_tile_slots = (size_t)((R->width + 7) / 8) * ((R->height + 7) / 8) * 64;
-    if (probe_spp_for(R, spp) > 0) {
-        // cost probe: variant 4 at probe_spp samples over the same RNG state, read-only: rays per pixel
-        RenderParams Q = P;
-        Q.spp = probe_spp_for(R, spp);
-        Q.accumulate = 0;
-        Q.probe_cost = R->d_tile_cost.get();
-        const dim3 grid((R->width + 15) / 16, (R->height + 15) / 16);
-        if (occ >= 6) hipLaunchKernelGGL((crt_render_kernel<false, 4, 6>), grid, dim3(256), 0, st, Q);
-        else hipLaunchKernelGGL((crt_render_kernel<false, 4, 5>), grid, dim3(256), 0, st, Q);
-        if (int rc = sort_descending(R, st, R->d_tile_cost.get(), (int)n_pix, R->d_order.get())) return rc;
-        P.n_slots = (int)n_pix;
-    } else {
-        if (int rc = order_tile_slots(R, st)) return rc;
-        P.n_slots = (int)n_tile_slots;
-        if (R->temporal) {
-            P.pix_rays = R->d_pix_rays.get();
-            R->pix_rays_valid = true;
-        }
-    }
-    HIP_TRY(hipMemsetAsync(R->d_queue.get(), 0, 4, st));
-    P.order = R->d_order.get();
-    P.queue = R->d_queue.get();
-    P.probe_cost = nullptr;
-    const RenderRow& row = RENDER_ROWS[render_row(7, cnt, occ)];
-    const int per_cu = row.w;        // workgroups of 4 waves resident per CU
-    const int n_wg = std::max(1, std::min(R->n_cus * per_cu, (int)((n_pix + 255) / 256)));
-    return launch_render(R, row, cnt, dim3(n_wg), dim3(256), st, P);
-}
-
-int crt_renderer_render(crt_renderer* R, const crt_scene* S, int spp, int max_bounces, unsigned flags, void* stream) {
-    if (!R || !S) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, "camera not set");
-    if (spp < 0 || max_bounces < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "negative spp / bounces");
-    if (S->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, "scene and renderer on different devices");
-    HIP_TRY(hipSetDevice(R->device));
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(R->d_counters.get(), 0, ERR_WORD * sizeof(unsigned long long), st));   // the error word stays
-    RenderParams P = render_params(R, S, spp, max_bounces, flags);
-    const bool cnt = (flags & CRT_RENDER_COUNT_WORK) != 0;
-    if (R->tile_shards > 1) {
-        // pixel sharding: variant 8 renders this shard's tiles; every other pixel of the framebuffer is 0, so the sum
-        // of the shards' framebuffers (one collective) is the unsharded frame exactly (x + 0 = x).  Checked and
-        // cleared before ev0, so a rejected call leaves the previous frame's timings intact and the clear is not
-        // counted as probe/sort time.
-        if (S->width != 4) return set_error(CRT_ERR_UNSUPPORTED, "pixel sharding needs a 4-wide rebuilt scene (variant 8)");
-        if (P.accumulate) return set_error(CRT_ERR_INVALID_ARGUMENT, "pixel sharding does not accumulate");
-        HIP_TRY(hipMemsetAsync(R->d_sum, 0, (size_t)R->width * R->height * 3 * sizeof(float), st));
-    }
-    {   // this render's slot of the timing ring: the spare slot, which no readable frame occupies (crt_renderer)
-        const DevEvent* slot = R->ring[R->n_timed % (CRT_TIMING_RING + 1)];
-        R->ev0 = slot[0].get(); R->ev_main = slot[1].get(); R->ev1 = slot[2].get();
-    }
-    HIP_TRY(hipEventRecord(R->ev0, st));
-    const int variant = choose_variant(R, S, spp);
-    const bool tiles = variant == 8 || variant == 10, queue = variant == 7;
-    if (tiles || queue) {
-        const size_t n_pix = (size_t)R->width * R->height;
-        const int n_tiles = ((R->width + 7) / 8) * ((R->height + 7) / 8);
-        if (int rc = ensure_order_buffers(R, st, n_pix, n_tiles, tiles)) return rc;
-    }
-    bool auto_small = false;
-    const int occ = choose_occupancy(R, S, variant, cnt, spp, &auto_small);
-    R->last_schedule[0] = R->last_schedule[1] = R->last_schedule[2] = R->last_schedule[3] = 0.f;
-    P.stack_lds = stack_lds_for(R, S, occ);
-    if (int rc = ensure_overflow_stack(R, S, st, P)) return rc;
-    int rc;
-    if (tiles) rc = render_tiles(R, S, st, P, cnt, spp, variant, occ, auto_small);
-    else if (queue) rc = render_pixel_queue(R, st, P, cnt, spp, occ);
-    else rc = render_grid(R, st, P, cnt, variant, occ);
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(R->ev1, st));
-    ++R->n_timed;
-    return CRT_OK;
-}
-
-int crt_scene_compare_dump(crt_renderer* R, const crt_scene* A, const crt_scene* B, int spp, int max_bounces,
-                           uint64_t out[5], float* dump, int max_dump);
-int crt_scene_compare(crt_renderer* R, const crt_scene* A, const crt_scene* B, int spp, int max_bounces,
-                      uint64_t out[5]) {
-    return crt_scene_compare_dump(R, A, B, spp, max_bounces, out, nullptr, 0);
-}
-
-int crt_scene_compare_dump(crt_renderer* R, const crt_scene* A, const crt_scene* B, int spp, int max_bounces,
-                           uint64_t out[5], float* dump, int max_dump) {
-    if (!R || !A || !B || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, "camera not set");
-    if (A->device != R->device || B->device != R->device)
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "scenes and renderer on different devices");
-    if (A->n_ranks != B->n_ranks) return set_error(CRT_ERR_INVALID_ARGUMENT, "scenes hold different primitive sets");
-    if (spp < 0 || max_bounces < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "negative spp / bounces");
-    HIP_TRY(hipSetDevice(R->device));
-    HIP_TRY(hipMemset(R->d_counters.get(), 0, ERR_WORD * sizeof(unsigned long long)));
-    CompareParams Q{};
-    RenderParams& P = Q.A;
-    P.nodes = A->d_nodes.get(); P.prims = A->d_prims.get(); P.mats = A->d_mats.get(); P.shade = A->d_shade.get();
-    P.n_nodes = A->n_nodes; P.n_mats = A->n_mats; P.n_prims = A->n_prims; P.n_layouts = A->layouts;
-    P.err = reinterpret_cast<unsigned*>(R->d_counters.get() + ERR_WORD);
-    P.width = R->width; P.height = R->height; P.spp = spp; P.max_bounces = max_bounces;
-    P.accumulate = 0; P.regen_threshold = 64; P.drain_threshold = 64; P.wave_drain = 64;
-    P.rng = R->d_rng.get(); P.sum = R->d_sum; P.counters = R->d_counters.get(); P.cam = R->cam;
-    P.rcp_w = R->rcp_w; P.rcp_h = R->rcp_h; P.fast_uv = R->fast_uv;
-    P.probe_stride = 1;
-    P.pix_rays = nullptr;
-    Q.nodes_b = B->d_nodes.get(); Q.prims_b = B->d_prims.get(); Q.n_nodes_b = B->n_nodes; Q.n_layouts_b = B->layouts;
-    Q.width_a = A->width; Q.width_b = B->width;
-    Q.dump = nullptr;
-    Q.max_dump = 0;
-    DevBuf<float> d_dump;
-    if (dump && max_dump > 0) {
-        HIP_TRY(d_dump.alloc((size_t)max_dump * 10));
-        Q.dump = d_dump.get();
-        Q.max_dump = max_dump;
-    }
-    P.sphere_first = A->sphere_first; P.n_ray_spheres = A->n_ray_spheres; P.sphere_chain = A->d_chain.get();
-    P.n_chain = A->n_chain;
-    std::memcpy(P.sph2, A->sph2, sizeof P.sph2);
-    Q.sphere_first_b = B->sphere_first; Q.n_spheres_b = B->n_ray_spheres; Q.chain_b = B->d_chain.get();
-    Q.n_chain_b = B->n_chain;
-    dim3 grid((R->width + 15) / 16, (R->height + 15) / 16), block(256);
-    hipLaunchKernelGGL(crt_compare_kernel, grid, block, 0, 0, Q);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    unsigned long long h[8];
-    HIP_TRY(hipMemcpy(h, R->d_counters.get(), sizeof h, hipMemcpyDeviceToHost));
-    for (int i = 0; i < 5; ++i) out[i] = h[i];
-    if (d_dump) {
-        const size_t n = std::min<size_t>((size_t)max_dump, (size_t)(h[6] & 0xffffffffu));
-        if (n) HIP_TRY(hipMemcpy(dump, d_dump.get(), n * 10 * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return CRT_OK;
-}
-
-int crt_renderer_resolve(crt_renderer* R, float scale, void* stream) {
-    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "null renderer");
-    HIP_TRY(hipSetDevice(R->device));
-    const int n = R->width * R->height;
-    hipLaunchKernelGGL(crt_resolve_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, R->d_sum,
-                       R->d_rgba.get(), n, scale);
-    HIP_TRY(hipGetLastError());
-    return CRT_OK;
-}
-
-int crt_renderer_render_frame(crt_renderer* R, const crt_scene* S, void* stream) {
-    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "null renderer");
-    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, "camera not set");
-    if (int rc = crt_renderer_render(R, S, R->cam.samples_per_pixel, 20, 0u, stream)) return rc;
-    if (int rc = crt_renderer_resolve(R, R->cam.pixel_sample_scale, stream)) return rc;
-    return crt_renderer_synchronize(R, stream);
-}
-
-// The device error word (sticky across renders until read here): a render that dropped a traversal-stack entry
-// or met an out-of-range primitive index produced a wrong frame.  Reported where the reference reports a kernel
-// fault, at the synchronisation after the launch (CUDARenderer.cuh:59, CUDA_CHECK(cudaDeviceSynchronize())).
-static int take_device_error(crt_renderer* R, unsigned long long word) {
-    if (!word) return CRT_OK;
-    // the callers waited for the stream before they read the word; the clear is a null-stream operation and is waited
-    // for, so that a render the caller enqueues next on any stream cannot have its report cleared
-    HIP_TRY(hipMemset(R->d_counters.get() + ERR_WORD, 0, sizeof(unsigned long long)));
-    HIP_TRY(hipStreamSynchronize(0));
-    std::string m = "render kernel reported an internal error:";
-    if (word & 1u) m += " primitive index out of range;";
-    if (word & 2u) m += " traversal stack deeper than the scene's stack bound (entries dropped);";
-    if (word & 4u) m += " leaf-round pair outside its owner's span (checked build);";
-    return set_error(CRT_ERR_HIP, m + " the frame is invalid");
-}
-
-int crt_renderer_synchronize(crt_renderer* R, void* stream) {
-    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "null renderer");
-    HIP_TRY(hipSetDevice(R->device));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    unsigned long long word = 0;
-    HIP_TRY(hipMemcpy(&word, R->d_counters.get() + ERR_WORD, sizeof word, hipMemcpyDeviceToHost));
-    return take_device_error(R, word);
-}
-
-static int read_dev(crt_renderer* R, void* dst, const void* src, size_t bytes) {
-    if (!R || !dst) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    HIP_TRY(hipSetDevice(R->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-int crt_renderer_read_linear(crt_renderer* R, float* out) {
-    return R ? read_dev(R, out, R->d_sum, (size_t)R->width * R->height * 12) : set_error(CRT_ERR_INVALID_ARGUMENT, "null");
-}
-int crt_renderer_read_rgba8(crt_renderer* R, uint8_t* out) {
-    return R ? read_dev(R, out, R->d_rgba.get(), (size_t)R->width * R->height * 4) : set_error(CRT_ERR_INVALID_ARGUMENT, "null");
-}
-int crt_renderer_read_rng(crt_renderer* R, uint32_t* out) {
-    return R ? read_dev(R, out, R->d_rng.get(), (size_t)R->width * R->height * 24) : set_error(CRT_ERR_INVALID_ARGUMENT, "null");
-}
-int crt_renderer_write_linear(crt_renderer* R, const float* in) {
-    if (!R || !in) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    HIP_TRY(hipSetDevice(R->device));
-    HIP_TRY(hipMemcpy(R->d_sum, in, (size_t)R->width * R->height * 12, hipMemcpyHostToDevice));
-    return CRT_OK;
-}
-int crt_renderer_get_counters(crt_renderer* R, crt_work_counters* out) {
-    if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    unsigned long long c[16];
-    if (int rc = read_dev(R, c, R->d_counters.get(), sizeof c)) return rc;
-    R->diag[0] = c[5]; R->diag[1] = c[6] & ((1ull << 40) - 1); R->diag[2] = c[6] >> 40;
-    for (int i = 0; i < 7; ++i) R->prof[i] = c[8 + i];
-    R->prof[7] = c[7];
-    out->rays = c[0]; out->box_tests = c[1]; out->tri_tests = c[2]; out->sphere_tests = c[3]; out->paths = c[4];
-    return take_device_error(R, c[ERR_WORD]);
-}
-int crt_renderer_get_section_profile(crt_renderer* R, unsigned long long* out7) {
-    if (!R || !out7) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    for (int i = 0; i < 7; ++i) out7[i] = R->prof[i];
-    return CRT_OK;
-}
-int crt_renderer_get_section_profile_ex(crt_renderer* R, unsigned long long* out, int n) {
-    if (!R || !out || n < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    for (int i = 0; i < n && i < 8; ++i) out[i] = R->prof[i];
-    return CRT_OK;
-}
-int crt_renderer_get_schedule_stats(crt_renderer* R, unsigned long long* out3) {
-    if (!R || !out3) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    out3[0] = R->diag[0]; out3[1] = R->diag[1]; out3[2] = R->diag[2];
-    return CRT_OK;
-}
-
-float* crt_renderer_linear_device_ptr(crt_renderer* R) { return R ? R->d_sum : nullptr; }
-uint8_t* crt_renderer_rgba_device_ptr(crt_renderer* R) { return R ? R->d_rgba.get() : nullptr; }
-uint32_t* crt_renderer_rng_device_ptr(crt_renderer* R) { return R ? R->d_rng.get() : nullptr; }
-
-const char* crt_renderer_last_kernel_name(const crt_renderer* R) { return R ? R->kernel_name : ""; }
-int crt_renderer_last_launch_frozen(const crt_renderer* R) { return R ? R->last_frozen : 0; }
-
-int crt_renderer_set_tail_fill(crt_renderer* R, int tiles, int spp) {
-    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "null renderer");
-    R->fill_tiles = tiles < 0 ? -1 : tiles;
-    R->fill_spp = tiles > 0 ? spp : 0;
-    return CRT_OK;
-}
-
-int crt_renderer_last_tail_fill(crt_renderer* R, int out[4]) {
-    if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    out[0] = R->last_fill[0]; out[1] = R->last_fill[1]; out[2] = out[3] = 0;
-    if (out[0] == 0) return CRT_OK;
-    HIP_TRY(hipSetDevice(R->device));
-    HIP_TRY(hipEventSynchronize(R->last_fill_ev));   // the render's ev1: its copy of the two counts is done
-    out[2] = (int)R->h_fill.get()[0];
-    out[3] = (int)R->h_fill.get()[1];
-    return CRT_OK;
-}
-
-#ifdef CRT_PROFILE_PAIRS
-extern "C" int crt_profile_pair_hist(unsigned long long* out32, int reset) {
-    if (!out32) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_pair_hist), 32 * 8, 0, hipMemcpyDeviceToHost));
-    if (reset) {
-        static const unsigned long long zero[32] = {};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_pair_hist), zero, sizeof zero, 0, hipMemcpyHostToDevice));
-    }
-    return CRT_OK;
-}
-#endif
-#ifdef CRT_PROFILE_LIVE
-extern "C" int crt_profile_live_hist(unsigned long long* out16, int reset) {
-    if (!out16) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_live_hist), 16 * 8, 0, hipMemcpyDeviceToHost));
-    if (reset) {
-        static const unsigned long long zero[16] = {};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_live_hist), zero, sizeof zero, 0, hipMemcpyHostToDevice));
-    }
-    return CRT_OK;
-}
-#endif
-#ifdef CRT_PROFILE_PASS
-extern "C" int crt_profile_pass_sections(unsigned long long* out20, int reset) {
-    if (!out20) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out20, HIP_SYMBOL(g_pass_prof), 20 * 8, 0, hipMemcpyDeviceToHost));
-    if (reset) {
-        static const unsigned long long zero[20] = {};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_pass_prof), zero, sizeof zero, 0, hipMemcpyHostToDevice));
-    }
-    return CRT_OK;
-}
-#endif
-#ifdef CRT_PROFILE_LOOPS
-extern "C" int crt_profile_loop_counts(unsigned long long* out8, int reset) {
-    if (!out8) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_loop_prof), 8 * 8, 0, hipMemcpyDeviceToHost));
-    if (reset) {
-        static const unsigned long long zero[8] = {};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_loop_prof), zero, sizeof zero, 0, hipMemcpyHostToDevice));
-    }
-    return CRT_OK;
-}
-#endif
-#ifdef CRT_PROFILE_SITES
-extern "C" int crt_profile_site_counts(unsigned long long* out12, int reset) {
-    if (!out12) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out12, HIP_SYMBOL(g_site_prof), 12 * 8, 0, hipMemcpyDeviceToHost));
-    if (reset) {
-        static const unsigned long long zero[12] = {};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_site_prof), zero, sizeof zero, 0, hipMemcpyHostToDevice));
-    }
-    return CRT_OK;
-}
-#endif
-#ifdef CRT_PROFILE_CRIT_TRACE
-// out: 2 x 16384 trace words, then 2 x n_waves HW words
-extern "C" int crt_profile_crit_trace(unsigned long long* trace, unsigned* hw, int n_waves) {
-    if (!trace || !hw || n_waves <= 0 || n_waves > 4 * 65536) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(trace, HIP_SYMBOL(g_crit_trace), sizeof(unsigned long long) * 2 * 16384, 0,
-                                hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpyFromSymbol(hw, HIP_SYMBOL(g_wave_hw), (size_t)n_waves * 8, 0, hipMemcpyDeviceToHost));
-    static const unsigned long long zero[2 * 16384] = {};
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_crit_trace), zero, sizeof zero, 0, hipMemcpyHostToDevice));
-    return CRT_OK;
-}
-#endif
-#ifdef CRT_PROFILE_WAVE_TIMES
-extern "C" int crt_profile_wave_times(unsigned long long* out, int n_waves) {
-    if (!out || n_waves <= 0 || n_waves > 4 * 65536) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_prof), (size_t)n_waves * 16, 0, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-#endif
-
-int crt_renderer_timing_history(crt_renderer* R, int back, float out[3]) {
-    if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    if (back < 0 || back >= CRT_TIMING_RING) return set_error(CRT_ERR_INVALID_ARGUMENT, "back outside [0, CRT_TIMING_RING)");
-    if ((unsigned long long)back >= R->n_timed) return set_error(CRT_ERR_INVALID_ARGUMENT, "fewer renders than back + 1");
-    const DevEvent* slot = R->ring[(R->n_timed - 1 - (unsigned long long)back) % (CRT_TIMING_RING + 1)];
-    HIP_TRY(hipSetDevice(R->device));
-    HIP_TRY(hipEventSynchronize(slot[2].get()));
-    HIP_TRY(hipEventElapsedTime(&out[0], slot[0].get(), slot[2].get()));
-    HIP_TRY(hipEventElapsedTime(&out[1], slot[0].get(), slot[1].get()));
-    HIP_TRY(hipEventElapsedTime(&out[2], slot[1].get(), slot[2].get()));
-    return CRT_OK;
-}
-
-int crt_renderer_set_temporal_order(crt_renderer* R, int on) {
-    if (!R || on < 0 || on > 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "temporal order: 0 or 1");
-    R->temporal = on;
-    R->pix_rays_valid = false;
-    return CRT_OK;
-}
-
-int crt_renderer_set_drain_threshold(crt_renderer* R, int lanes) {
-    if (!R || lanes < 0 || lanes > 64) return set_error(CRT_ERR_INVALID_ARGUMENT, "drain threshold 0..64");
-    R->drain_threshold = lanes;
-    return CRT_OK;
-}
-
-int crt_renderer_set_wave_drain(crt_renderer* R, int sixty_fourths) {
-    if (!R || sixty_fourths < 1 || sixty_fourths > 64) return set_error(CRT_ERR_INVALID_ARGUMENT, "wave drain 1..64");
-    R->wave_drain = sixty_fourths;
-    return CRT_OK;
-}
-
-int crt_renderer_set_xcd_regions(crt_renderer* R, int on) {
-    if (!R || on < 0 || on > 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "xcd regions: 0 or 1");
-    R->xcd_regions = on;
-    return CRT_OK;
-}
-
-// The round-4 leaf-pair carry was measured and not kept (+1.8 % / +15 %); its kernels live on as
-// profiles/r04c/leaf_carry.patch.  The entry point stays in the ABI and reports that this build has no carry.
-int crt_renderer_set_leaf_carry(crt_renderer* R, int lanes, int max_pairs) {
-    if (!R) return set_error(CRT_ERR_INVALID_ARGUMENT, "null renderer");
-    (void)lanes;
-    (void)max_pairs;
-    return set_error(CRT_ERR_UNSUPPORTED, "leaf-pair carry: not in this build (measured and removed, DESIGN.md §8; "
-                                          "profiles/r04c/leaf_carry.patch)");
-}
-
-int crt_renderer_last_schedule(crt_renderer* R, float out[4]) {
-    if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    for (int k = 0; k < 4; ++k) out[k] = R->last_schedule[k];
-    return CRT_OK;
-}
-
-int crt_renderer_last_timings(crt_renderer* R, float out[3]) {
-    if (!R || !out) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    if (!R->n_timed) return set_error(CRT_ERR_INVALID_ARGUMENT, "no render yet");
-    return crt_renderer_timing_history(R, 0, out);
-}
-
-float crt_renderer_last_kernel_ms(crt_renderer* R) {
-    float t[3];
-    if (!R || !R->n_timed || crt_renderer_timing_history(R, 0, t) != CRT_OK) return -1.f;
-    return t[0];
-}
-
-int crt_debug_live_allocations(int64_t* buffers, int64_t* bytes) {
-    if (!buffers || !bytes) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    *buffers = g_live_buffers.load();
-    *bytes = g_live_bytes.load();
-    return CRT_OK;
-}
-
-int crt_selftest_math(const float* a, const float* b, int n, float* out, double* out64) {
-    if (!a || !b || !out || !out64 || n <= 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    DevBuf<float> da, db, dout;
-    DevBuf<double> d64;
-    HIP_TRY(da.alloc(n));
-    HIP_TRY(db.alloc(n));
-    HIP_TRY(dout.alloc(n * 4));
-    HIP_TRY(d64.alloc(n * 2));
-    HIP_TRY(hipMemcpy(da.get(), a, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(db.get(), b, n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(crt_selftest_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, da.get(), db.get(), n, dout.get(),
-                       d64.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout.get(), n * 16, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out64, d64.get(), n * 16, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-
-// crt_selftest_rcp / crt_selftest_sqrt: `kernel` over the f32 bit patterns [lo_bits, hi_bits].
-static int selftest_bit_range(void (*kernel)(uint32_t, uint32_t, unsigned long long*, uint32_t*), uint32_t lo_bits,
-                              uint32_t hi_bits, unsigned long long* mismatches, uint32_t* first_bad) {
-    if (!mismatches || !first_bad) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    DevBuf<unsigned long long> dbad;
-    DevBuf<uint32_t> dfirst;
-    HIP_TRY(dbad.alloc(1));
-    HIP_TRY(dfirst.alloc(1));
-    HIP_TRY(hipMemset(dbad.get(), 0, 8));
-    HIP_TRY(hipMemset(dfirst.get(), 0xff, 4));
-    hipLaunchKernelGGL(kernel, dim3(8192), dim3(256), 0, 0, lo_bits, hi_bits, dbad.get(), dfirst.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(mismatches, dbad.get(), 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(first_bad, dfirst.get(), 4, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-int crt_selftest_rcp(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* mismatches, uint32_t* first_bad) {
-    return selftest_bit_range(crt_selftest_rcp_kernel, lo_bits, hi_bits, mismatches, first_bad);
-}
-int crt_selftest_sqrt(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* mismatches, uint32_t* first_bad) {
-    return selftest_bit_range(crt_selftest_sqrt_kernel, lo_bits, hi_bits, mismatches, first_bad);
-}
-
-int crt_selftest_unit(const float* in, int n, float* out) {
-    if (!in || !out || n <= 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    DevBuf<float> din, dout;
-    HIP_TRY(din.alloc((size_t)n * 3));
-    HIP_TRY(dout.alloc((size_t)n * 3));
-    HIP_TRY(hipMemcpy(din.get(), in, (size_t)n * 12, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(crt_selftest_unit_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, din.get(), n, dout.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout.get(), (size_t)n * 12, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-
-int crt_selftest_scan(const int* in, int n_waves, int* out) {
-    if (!in || !out || n_waves <= 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    DevBuf<int> din, dout;
-    HIP_TRY(din.alloc((size_t)n_waves * 64));
-    HIP_TRY(dout.alloc((size_t)n_waves * 64 * 3));
-    HIP_TRY(hipMemcpy(din.get(), in, (size_t)n_waves * 64 * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(crt_selftest_scan_kernel, dim3(n_waves), dim3(64), 0, 0, din.get(), dout.get(), n_waves);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout.get(), (size_t)n_waves * 64 * 12, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-
-int crt_selftest_geometry(int kind, const float* in, int n, const crt_camera_desc* cam, int width, int height,
-                          uint32_t* rng, float* out) {
-    static const int in_words[5] = {17, 14, 12, 2, 12}, out_words[5] = {1, 1, 1, 6, 1};
-    if (kind < 0 || kind > 4 || !in || !out || n <= 0 || (kind == 3 && (!cam || !rng || width <= 0 || height <= 0)))
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    DevBuf<float> din, dout;
-    DevBuf<uint32_t> drng;
-    HIP_TRY(din.alloc((size_t)n * in_words[kind]));
-    HIP_TRY(dout.alloc((size_t)n * out_words[kind]));
-    if (kind == 3) HIP_TRY(drng.alloc((size_t)n * 6));
-    HIP_TRY(hipMemcpy(din.get(), in, (size_t)n * in_words[kind] * 4, hipMemcpyHostToDevice));
-    unsigned long long bad_w = 0, bad_h = 0;   // the renderer's choice for this size (crt_renderer_create)
-    if (kind == 3) {
-        HIP_TRY(hipMemcpy(drng.get(), rng, (size_t)n * 24, hipMemcpyHostToDevice));
-        if (int rc = uv_div_mismatches(width, &bad_w)) return rc;
-        if (int rc = uv_div_mismatches(height, &bad_h)) return rc;
-    }
-    hipLaunchKernelGGL(crt_selftest_geometry_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, kind, din.get(), n, dout.get(),
-                       drng.get(), cam ? *cam : crt_camera_desc{}, width, height, kind == 3 ? 1.0f / (float)width : 1.f,
-                       kind == 3 ? 1.0f / (float)height : 1.f, (int)(kind == 3 && bad_w == 0 && bad_h == 0));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout.get(), (size_t)n * out_words[kind] * 4, hipMemcpyDeviceToHost));
-    if (kind == 3) HIP_TRY(hipMemcpy(rng, drng.get(), (size_t)n * 24, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-
-int crt_selftest_shade(const float* in, int n, float* out) {
-    if (!in || !out || n <= 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    DevBuf<float> din, dout;
-    HIP_TRY(din.alloc((size_t)n * 32));
-    HIP_TRY(dout.alloc((size_t)n * 20));
-    HIP_TRY(hipMemcpy(din.get(), in, (size_t)n * 32 * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(crt_selftest_shade_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, din.get(), n, dout.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout.get(), (size_t)n * 20 * 4, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-
-int crt_selftest_rng(unsigned long long seed, const unsigned long long* subseq, int n, int n_draw,
-                     uint32_t* state_out, float* uniforms_out) {
-    if (!subseq || !state_out || !uniforms_out || n <= 0 || n_draw < 0)
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = use_device(0)) return rc;
-    const auto& tab = seq_tables();
-    DevBuf<uint32_t> dseq, dst;
-    DevBuf<float> du;
-    HIP_TRY(dseq.alloc(tab.size()));
-    HIP_TRY(dst.alloc((size_t)n * 6));
-    HIP_TRY(du.alloc((size_t)n * std::max(n_draw, 1)));
-    HIP_TRY(hipMemcpy(dseq.get(), tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-    for (int i = 0; i < n; ++i) {   // one launch per subsequence keeps the kernel identical to the renderer's
-        hipLaunchKernelGGL(crt_init_rand_kernel, dim3(1), dim3(64), 0, 0, dst.get() + 6 * i, dseq.get(), 1, seed, subseq[i]);
-    }
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(crt_selftest_rng_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, dst.get(), n, n_draw, du.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(state_out, dst.get(), (size_t)n * 24, hipMemcpyDeviceToHost));
-    if (n_draw) HIP_TRY(hipMemcpy(uniforms_out, du.get(), (size_t)n * n_draw * 4, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
-
-// The schedule stages on caller-supplied costs: the renderer's own buffers and the host functions the renders call
-// (order_tiles_by_probe, sort_descending, order_tile_slots, shard_tiles_in_row_order), on the null stream.
-int crt_selftest_tile_schedule(crt_renderer* R, const uint32_t* pix_cost, int stride, int key_mode, int shard, int shards,
-                               int xcd_regions, unsigned long long* stats_out) {
-    if (!R || !pix_cost) return set_error(CRT_ERR_INVALID_ARGUMENT, "null argument");
-    if ((stride != 1 && stride != 2 && stride != 4) || key_mode < 0 || key_mode > 2 || shards < 1 || shard < 0 ||
-        shard >= shards)
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad stride, key mode or shard");
-    HIP_TRY(hipSetDevice(R->device));
-    const size_t n_pix = (size_t)R->width * R->height;
-    const int n_tiles = ((R->width + 7) / 8) * ((R->height + 7) / 8);
-    if (int rc = ensure_order_buffers(R, 0, n_pix, n_tiles, true)) return rc;
-    HIP_TRY(hipMemset(R->d_order.get(), 0xff, std::max(n_pix, (size_t)n_tiles * 64) * 4));
-    HIP_TRY(hipMemcpy(R->d_tile_cost.get(), pix_cost, n_pix * 4, hipMemcpyHostToDevice));
-    const int mode0 = R->tile_key_mode, xcd0 = R->xcd_regions;
-    R->tile_key_mode = key_mode;
-    R->xcd_regions = xcd_regions ? 1 : 0;
-    const int rc = order_tiles_by_probe(R, 0, stride, stats_out != nullptr, shard, shards);
-    R->tile_key_mode = mode0;
-    R->xcd_regions = xcd0;
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(0));
-    if (stats_out) { stats_out[0] = R->h_probe_stats.get()[0]; stats_out[1] = R->h_probe_stats.get()[1]; }
-    return CRT_OK;
-}
-
-int crt_selftest_pixel_order(crt_renderer* R, int kind, const uint32_t* in, int shard, int shards) {
-    if (!R || kind < 0 || kind > 3 || (kind <= 1 && !in)) return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (kind == 3 && (shards < 1 || shard < 0 || shard >= shards))
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad shard");
-    HIP_TRY(hipSetDevice(R->device));
-    const size_t n_pix = (size_t)R->width * R->height;
-    const int n_tiles = ((R->width + 7) / 8) * ((R->height + 7) / 8);
-    if (int rc = ensure_order_buffers(R, 0, n_pix, n_tiles, kind == 3)) return rc;
-    HIP_TRY(hipMemset(R->d_order.get(), 0xff, std::max(n_pix, (size_t)n_tiles * 64) * 4));
-    int rc = CRT_OK;
-    if (kind == 0) {
-        HIP_TRY(hipMemcpy(R->d_tile_cost.get(), in, n_pix * 4, hipMemcpyHostToDevice));
-        rc = sort_descending(R, 0, R->d_tile_cost.get(), (int)n_pix, R->d_order.get());
-    } else if (kind == 3) {
-        shard_tiles_in_row_order(R, 0, n_tiles, shard, shards);
-    } else {
-        const int temporal0 = R->temporal;
-        const bool valid0 = R->pix_rays_valid;
-        R->temporal = kind == 1;
-        if (kind == 1) {
-            if (!R->d_pix_rays) rc = order_tile_slots(R, 0);   // allocates the temporal buffers (row order this once)
-            if (!rc) {
-                hipError_t e = hipMemcpy(R->d_pix_rays.get(), in, n_pix * 4, hipMemcpyHostToDevice);
-                if (e == hipSuccess) e = hipMemset(R->d_order.get(), 0xff, (size_t)n_tiles * 64 * 4);
-                if (e != hipSuccess) rc = set_error(CRT_ERR_HIP, hipGetErrorString(e));
-            }
-            R->pix_rays_valid = true;
-        }
-        if (!rc) rc = order_tile_slots(R, 0);
-        R->temporal = temporal0;
-        R->pix_rays_valid = kind == 1 ? false : valid0;   // kind 1 replaced the last frame's map
-    }
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(0));
-    return CRT_OK;
-}
-
-int crt_selftest_schedule_buffer(crt_renderer* R, int which, uint32_t* out, int64_t capacity, int64_t* n_out) {
-    if (!R || !n_out || capacity < 0 || (capacity > 0 && !out))
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "bad argument");
-    const size_t n_pix = (size_t)R->width * R->height;
-    const size_t n_tiles = (size_t)((R->width + 7) / 8) * ((R->height + 7) / 8);
-    const uint32_t* src;
-    size_t n;
-    switch (which) {
-        case 0: src = R->d_order.get(); n = std::max(n_pix, n_tiles * 64); break;
-        case 1: src = R->d_tile_key.get(); n = n_tiles; break;
-        case 2: src = R->d_tile_cost.get(); n = n_pix; break;
-        case 3: src = R->d_pix_rays.get(); n = n_pix; break;
-        case 4: src = R->d_tile_order.get(); n = n_tiles; break;
-        default: return set_error(CRT_ERR_INVALID_ARGUMENT, "unknown schedule buffer");
-    }
-    if (!src) n = 0;
-    *n_out = (int64_t)n;
-    n = std::min(n, (size_t)capacity);
-    if (n) {
-        HIP_TRY(hipSetDevice(R->device));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost));
-    }
-    return CRT_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------ ray queries
-// Batch closest-hit / occlusion queries over a device scene: the kernels and their C ABI, in this translation unit
-// because they instantiate the traversal's device functions above (traverse_step4, trace, trace4, ray_spheres).
+// ------------------------------------------------------------------ the host half, then the features
+// Here because they launch or instantiate the device functions above, in order of dependence: the core's host half, one
+// responsibility per header (the core's kernels all stay above), then each feature's kernels and host code.
+#include "crt_handles.h"    // the handles, the per-handle states, the shared host helpers, the entries without a handle
+#include "crt_scene.h"      // scene creation: flattening, the host SAH build, the 4-wide collapse, export
+#include "crt_renderer.h"   // renderer creation, setters, synchronise, reads, getters, compare, resolve
+#include "crt_dispatch.h"   // the render dispatch: the launch table, the schedules, crt_renderer_render
+#include "crt_selftest.h"   // the host side of the self-tests
 #include "crt_trace.h"
 #include "crt_paths.h"
 #include "crt_adaptive.h"

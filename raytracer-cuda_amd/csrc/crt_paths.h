@@ -643,10 +643,7 @@ constexpr int64_t QUEUE_FINISH_BELOW = 921600;
 namespace {
 
 int wavefront_scratch(crt_renderer* R, WavefrontScratch** out) {
-    if (!R->wavefront) {
-        R->wavefront.reset(new (std::nothrow) WavefrontScratch);   // whatever is allocated below is freed with the handle
-        WavefrontScratch* X = R->wavefront.get();
-        if (!X) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+    return first_use(R->wavefront, "the wavefront scratch of this renderer could not be allocated", out, [&](WavefrontScratch* X) -> int {
         const size_t n_pix = (size_t)R->width * R->height;
         for (int k = 0; k < 2; ++k) {
             HIP_TRY(X->rays[k].alloc(n_pix));
@@ -660,23 +657,18 @@ int wavefront_scratch(crt_renderer* R, WavefrontScratch** out) {
         HIP_TRY(X->h_queue.alloc(QUEUE_WORDS));
         HIP_TRY(X->ev0.create());
         HIP_TRY(X->ev1.create());
-        X->ready = true;
-    }
-    if (!R->wavefront->ready)
-        return set_error(CRT_ERR_OUT_OF_MEMORY, "the wavefront scratch of this renderer could not be allocated");
-    *out = R->wavefront.get();
-    return CRT_OK;
+        return CRT_OK;
+    });
 }
 
-}  // namespace
-
-extern "C" {
-
-int crt_renderer_render_wavefront(crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags,
-                                  const crt_trace_options* trace_opts, crt_wavefront_stats* stats_out, void* stream) {
+// What the two wavefront loops check of their arguments, in one order.  queued: the loop of
+// crt_renderer_render_wavefront_queued and _finish, which also checks sync_every, its pixel limit and finish_below.
+int wavefront_check(const crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags, bool queued,
+                    int sync_every, int64_t finish_below) {
     if (!R || !Sc) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: null argument");
     if (spp < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: negative spp");
     if (max_bounces < 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: max_bounces must be >= 1");
+    if (queued && sync_every < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: sync_every must be >= 0");
     if (flags & ~(CRT_RENDER_ACCUMULATE | CRT_RENDER_COUNT_WORK))
         return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: unknown flag");
     if (Sc->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: scene and renderer on different devices");
@@ -686,24 +678,72 @@ int crt_renderer_render_wavefront(crt_renderer* R, const crt_scene* Sc, int spp,
     if (R->tile_shards > 1) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: pixel sharding is crt_renderer_render's");
     const int64_t n_pix = (int64_t)R->width * R->height;
     if (n_pix >= ((int64_t)1 << 31)) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: 2^31 pixels or more");
-    crt_scene* S = const_cast<crt_scene*>(Sc);   // the trace scratch belongs to the handle (handles are not thread-safe)
+    if (!queued) return CRT_OK;
+    if (n_pix > TRACE_LAUNCH_RAYS) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: the queued loop takes at most 2^30 pixels");
+    if (finish_below > 0 && !finish_lane_ok(Sc))
+        return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: finish_below needs a tree whose stack bound fits the "
+                                              "in-lane traversal's 64-entry stack (3 entries per level)");
+    return CRT_OK;
+}
+
+// The start of a frame of either loop, on `stream`: the sums cleared unless the frame accumulates, the handle's scratch,
+// every pixel's remaining samples, the queued loop's device words, ev0 and the camera rays into batch 0.  A frame of no
+// sample or no pixel is done here: the stream is waited for, the stats are zero and *out stays null.
+int wavefront_begin(crt_renderer* R, int spp, unsigned flags, bool queued, crt_wavefront_stats* stats_out, void* stream,
+                    WavefrontScratch** out) {
+    const int64_t n_pix = (int64_t)R->width * R->height;
     HIP_TRY(hipSetDevice(R->device));
     hipStream_t st = (hipStream_t)stream;
-    crt_wavefront_stats stats{};
     if (!(flags & CRT_RENDER_ACCUMULATE))
         HIP_TRY(hipMemsetAsync(R->d_sum, 0, (size_t)n_pix * 3 * sizeof(float), st));
     if (spp == 0 || n_pix == 0) {
         HIP_TRY(hipStreamSynchronize(st));
-        if (stats_out) *stats_out = stats;
+        if (stats_out) *stats_out = crt_wavefront_stats{};
         return CRT_OK;
     }
     WavefrontScratch* X = nullptr;
     if (int rc = wavefront_scratch(R, &X)) return rc;
-    uint32_t* const h_count = X->h_count.get();
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->remaining.get(), spp - 1, (size_t)n_pix, st));
+    if (queued) {   // the error word and the totals are cleared once per call; the first batch is every pixel
+        uint32_t* const d_queue = X->d_queue.get();
+        HIP_TRY(hipMemsetAsync(d_queue, 0, QUEUE_WORDS * 4, st));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_queue, (int)n_pix, 1, st));
+    }
     HIP_TRY(hipEventRecord(X->ev0.get(), st));
     if (int rc = crt_renderer_camera_rays_device(R, nullptr, n_pix, nullptr, X->rays[0].get(), X->paths[0].get(), stream))
         return rc;
+    *out = X;
+    return CRT_OK;
+}
+
+// The end of a frame of either loop: ev1, the elapsed time and the stats.  `word`: the trace error word the loop read; a
+// non-zero one goes into the handle's own word, for trace_take_error's report.
+int wavefront_end(crt_scene* S, WavefrontScratch* X, hipStream_t st, crt_wavefront_stats stats, unsigned long long word,
+                  crt_wavefront_stats* stats_out) {
+    HIP_TRY(hipEventRecord(X->ev1.get(), st));
+    HIP_TRY(hipEventSynchronize(X->ev1.get()));
+    HIP_TRY(hipEventElapsedTime(&stats.ms, X->ev0.get(), X->ev1.get()));
+    if (stats_out) *stats_out = stats;
+    if (word) HIP_TRY(hipMemcpy(S->trace->d_stats.get() + TRACE_ERR_WORD, &word, 8, hipMemcpyHostToDevice));
+    // a frame handed over before its first round ran no query: a scene that was never traced has no scratch to ask
+    return S->trace ? trace_take_error(S->trace.get()) : CRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crt_renderer_render_wavefront(crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags,
+                                  const crt_trace_options* trace_opts, crt_wavefront_stats* stats_out, void* stream) {
+    if (int rc = wavefront_check(R, Sc, spp, max_bounces, flags, false, 0, 0)) return rc;
+    crt_scene* S = const_cast<crt_scene*>(Sc);   // the trace scratch belongs to the handle (handles are not thread-safe)
+    hipStream_t st = (hipStream_t)stream;
+    WavefrontScratch* X = nullptr;
+    if (int rc = wavefront_begin(R, spp, flags, false, stats_out, stream, &X)) return rc;
+    if (!X) return CRT_OK;
+    const int64_t n_pix = (int64_t)R->width * R->height;
+    uint32_t* const h_count = X->h_count.get();
+    crt_wavefront_stats stats{};
     int cur = 0;
     int64_t m = n_pix;
     while (m > 0) {
@@ -721,15 +761,11 @@ int crt_renderer_render_wavefront(crt_renderer* R, const crt_scene* Sc, int spp,
         HIP_TRY(hipStreamSynchronize(st));
         m = std::min<int64_t>(h_count[0], n_pix);
         cur ^= 1;
-        if (h_count[2] | h_count[3]) break;                  // reported below, as trace_take_error words it
+        if (h_count[2] | h_count[3]) break;                  // reported by wavefront_end, as trace_take_error words it
     }
-    HIP_TRY(hipEventRecord(X->ev1.get(), st));
-    HIP_TRY(hipEventSynchronize(X->ev1.get()));
-    HIP_TRY(hipEventElapsedTime(&stats.ms, X->ev0.get(), X->ev1.get()));
-    if (stats_out) *stats_out = stats;
-    if (h_count[2] | h_count[3])
-        HIP_TRY(hipMemcpy(S->trace->d_stats.get() + TRACE_ERR_WORD, h_count + 2, 8, hipMemcpyHostToDevice));
-    return trace_take_error(S->trace.get());
+    unsigned long long word;
+    std::memcpy(&word, h_count + 2, sizeof word);
+    return wavefront_end(S, X, st, stats, word, stats_out);
 }
 
 }  // extern "C"
@@ -742,52 +778,21 @@ namespace {
 int wavefront_queued(crt_renderer* R, const crt_scene* Sc, int spp, int max_bounces, unsigned flags,
                      const crt_trace_options* trace_opts, int sync_every, int64_t finish_below,
                      crt_wavefront_stats* stats_out, void* stream) {
-    if (!R || !Sc) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: null argument");
-    if (spp < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: negative spp");
-    if (max_bounces < 1) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: max_bounces must be >= 1");
-    if (sync_every < 0) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: sync_every must be >= 0");
-    if (flags & ~(CRT_RENDER_ACCUMULATE | CRT_RENDER_COUNT_WORK))
-        return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: unknown flag");
-    if (Sc->device != R->device) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: scene and renderer on different devices");
-    if (!R->has_camera) return set_error(CRT_ERR_INVALID_ARGUMENT, "render wavefront: camera not set");
-    if (flags & CRT_RENDER_COUNT_WORK)
-        return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: work counters are the render kernels' (crt_renderer_render)");
-    if (R->tile_shards > 1) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: pixel sharding is crt_renderer_render's");
-    const int64_t n_pix = (int64_t)R->width * R->height;
-    if (n_pix >= ((int64_t)1 << 31)) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: 2^31 pixels or more");
-    if (n_pix > TRACE_LAUNCH_RAYS) return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: the queued loop takes at most 2^30 pixels");
-    if (finish_below > 0 && !finish_lane_ok(Sc))
-        return set_error(CRT_ERR_UNSUPPORTED, "render wavefront: finish_below needs a tree whose stack bound fits the "
-                                              "in-lane traversal's 64-entry stack (3 entries per level)");
+    if (int rc = wavefront_check(R, Sc, spp, max_bounces, flags, true, sync_every, finish_below)) return rc;
     const int block = sync_every ? sync_every : QUEUE_SYNC_EVERY;
     crt_scene* S = const_cast<crt_scene*>(Sc);   // the trace scratch belongs to the handle (handles are not thread-safe)
-    HIP_TRY(hipSetDevice(R->device));
     hipStream_t st = (hipStream_t)stream;
-    crt_wavefront_stats stats{};
-    if (!(flags & CRT_RENDER_ACCUMULATE))
-        HIP_TRY(hipMemsetAsync(R->d_sum, 0, (size_t)n_pix * 3 * sizeof(float), st));
-    if (spp == 0 || n_pix == 0) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (stats_out) *stats_out = stats;
-        return CRT_OK;
-    }
     WavefrontScratch* X = nullptr;
-    if (int rc = wavefront_scratch(R, &X)) return rc;
+    if (int rc = wavefront_begin(R, spp, flags, true, stats_out, stream, &X)) return rc;
+    if (!X) return CRT_OK;
     uint32_t *const d_queue = X->d_queue.get(), *const h_queue = X->h_queue.get();
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X->remaining.get(), spp - 1, (size_t)n_pix, st));
-    // the error word and the totals are cleared once per call; the first batch is every pixel
-    HIP_TRY(hipMemsetAsync(d_queue, 0, QUEUE_WORDS * 4, st));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_queue, (int)n_pix, 1, st));
-    HIP_TRY(hipEventRecord(X->ev0.get(), st));
-    if (int rc = crt_renderer_camera_rays_device(R, nullptr, n_pix, nullptr, X->rays[0].get(), X->paths[0].get(), stream))
-        return rc;
     unsigned* d_err = d_queue + QUEUE_ERR;
     uint64_t* d_totals = reinterpret_cast<uint64_t*>(d_queue + QUEUE_TOTALS);
     int cur = 0;
     // A batch is never larger than the one before it (an input entry appends at most one output entry), so the last
     // count the host read bounds every later one: it is the capacity of the whole block.  Iterations enqueued after the
     // count reached 0 trace nothing and append nothing.
-    int64_t m = n_pix;
+    int64_t m = (int64_t)R->width * R->height;
     while (m > 0) {
         if (m <= finish_below) {                             // the hand-off: the lanes run their pixels to the end
             if (int rc = crt_scene_path_finish_device(S, R, X->rays[cur].get(), X->paths[cur].get(), d_queue + cur, m,
@@ -813,22 +818,14 @@ int wavefront_queued(crt_renderer* R, const crt_scene* Sc, int spp, int max_boun
         HIP_TRY(hipMemcpyAsync(h_queue, d_queue, QUEUE_WORDS * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         m = std::min<int64_t>(h_queue[cur], m);
-        if (h_queue[QUEUE_ERR]) break;                          // reported below, as trace_take_error words it
+        if (h_queue[QUEUE_ERR]) break;                          // reported by wavefront_end, as trace_take_error words it
     }
-    HIP_TRY(hipEventRecord(X->ev1.get(), st));
-    HIP_TRY(hipEventSynchronize(X->ev1.get()));
-    HIP_TRY(hipEventElapsedTime(&stats.ms, X->ev0.get(), X->ev1.get()));
     uint64_t totals[2];
     std::memcpy(totals, h_queue + QUEUE_TOTALS, sizeof totals);
+    crt_wavefront_stats stats{};
     stats.rays = totals[0];
     stats.iterations = (uint32_t)totals[1];
-    if (stats_out) *stats_out = stats;
-    if (h_queue[QUEUE_ERR]) {                                   // into the handle's own word, for trace_take_error's report
-        const unsigned long long word = h_queue[QUEUE_ERR];
-        HIP_TRY(hipMemcpy(S->trace->d_stats.get() + TRACE_ERR_WORD, &word, 8, hipMemcpyHostToDevice));
-    }
-    // a frame handed over before its first round ran no query: a scene that was never traced has no scratch to ask
-    return S->trace ? trace_take_error(S->trace.get()) : CRT_OK;
+    return wavefront_end(S, X, st, stats, h_queue[QUEUE_ERR], stats_out);
 }
 
 }  // namespace

@@ -164,10 +164,7 @@ int reproject_waves(const crt_renderer* R) { return ((R->width + REPROJECT_BX - 
 // The handle's denoiser state must exist (the guides live there).
 int reproject_state(crt_renderer* R, ReprojectState** out) {
     DenoiseState* N = R->denoise.get();
-    if (!R->reproject) {
-        R->reproject.reset(new (std::nothrow) ReprojectState);   // whatever is allocated below is freed with the handle
-        ReprojectState* P = R->reproject.get();
-        if (!P) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+    return first_use(R->reproject, "the reprojection state of this renderer could not be allocated", out, [&](ReprojectState* P) -> int {
         const size_t n_pix = (size_t)R->width * R->height;
         HIP_TRY(P->hist[0].alloc(n_pix));
         HIP_TRY(P->hist[1].alloc(n_pix));
@@ -175,12 +172,8 @@ int reproject_state(crt_renderer* R, ReprojectState** out) {
         if (!N->guides[1]) HIP_TRY(N->guides[1].alloc(n_pix * 2));
         HIP_TRY(P->e0.create());
         HIP_TRY(P->e1.create());
-        P->ready = true;
-    }
-    if (!R->reproject->ready)
-        return set_error(CRT_ERR_OUT_OF_MEMORY, "the reprojection state of this renderer could not be allocated");
-    *out = R->reproject.get();
-    return CRT_OK;
+        return CRT_OK;
+    });
 }
 
 // The checks of the options alone (no handle, no device).
@@ -201,10 +194,8 @@ int reproject_check_options(const crt_reproject_options* o, const char* who) {
 
 // The variance state (crt_variance.h) with its moment buffers, for a reprojection that carries the moments.
 int reproject_moments_state(crt_renderer* R, VarianceState** out) {
-    if (!R->variance) {
-        R->variance.reset(new (std::nothrow) VarianceState);     // whatever it comes to hold is freed with the handle
-        if (!R->variance) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-    }
+    if (!R->variance)
+        if (int rc = new_state(R->variance)) return rc;
     for (DevBuf<float2>& b : R->variance->mom)
         if (!b) HIP_TRY(b.alloc((size_t)R->width * R->height));
     *out = R->variance.get();

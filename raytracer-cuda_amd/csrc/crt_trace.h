@@ -126,10 +126,7 @@ namespace {
 
 // The scratch is allocated on first use and initialised on `st`, the stream its first user goes on to enqueue on.
 int trace_scratch(crt_scene* S, hipStream_t st, TraceScratch** out) {
-    if (!S->trace) {
-        S->trace.reset(new (std::nothrow) TraceScratch);   // whatever is allocated below is freed with the handle
-        TraceScratch* X = S->trace.get();
-        if (!X) return set_error(CRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+    return first_use(S->trace, "the trace scratch of this scene could not be allocated", out, [&](TraceScratch* X) -> int {
         HIP_TRY(X->d_next.alloc(1));
         HIP_TRY(X->d_stats.alloc(TRACE_STAT_WORDS));
         HIP_TRY(hipMemsetAsync(X->d_stats.get(), 0, TRACE_STAT_WORDS * sizeof(unsigned long long), st));
@@ -141,12 +138,8 @@ int trace_scratch(crt_scene* S, hipStream_t st, TraceScratch** out) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, crt_trace_kernel<false, false>, 64, 0) != hipSuccess || nb <= 0)
             nb = 4 * 6;
         X->wg_per_cu = nb;
-        X->ready = true;
-    }
-    if (!S->trace->ready)
-        return set_error(CRT_ERR_OUT_OF_MEMORY, "the trace scratch of this scene could not be allocated");
-    *out = S->trace.get();
-    return CRT_OK;
+        return CRT_OK;
+    });
 }
 
 // One query over device pointers, enqueued on st.  d_n null: rays [0, n).  Otherwise the indirect query: n is the

@@ -14,7 +14,7 @@
 #include "ParallelFor.h"
 
 namespace {
-// CRT_SETUP_TRACE=1: the host loader's stages on stderr (tools/setup_breakdown.py; crt_hip.hip times the rest)
+// CRT_SETUP_TRACE=1: the host loader's stages on stderr (tools/setup_breakdown.py; crt_scene.h times the rest)
 struct LoadTrace {
     bool on = std::getenv("CRT_SETUP_TRACE") != nullptr;
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();

@@ -108,7 +108,7 @@ ONE = 0xffffffff                                        # uniform 1.0
 
 # ------------------------------------------------------------------------------------------ the material rows
 def shade_rows_of(mats):
-    """material_shade_row of crt_hip.hip in float32: (code, 0, 0, 0) (payload) per row of the table."""
+    """material_shade_row of crt_scene.h in float32: (code, 0, 0, 0) (payload) per row of the table."""
     mats = np.asarray(mats, F32).reshape(-1, 9)
     rows = np.zeros((len(mats), 2, 4), F32)
     for k, m in enumerate(mats):

@@ -8,7 +8,8 @@ Every comparison is bit for bit, on uint32 views; frames are 64x36 unless stated
    workgroup and a workgroup's whole reservation; remaining all 0 / all positive / alternating / None; entries that come
    in ENDED or name no pixel; n = 0; a permuted batch; a caller's own output pair.
 2. paths.render(compact="device") == Renderer.render (sums, RGBA8, RNG state, rays) and == compact="torch" (iterations).
-3. Renderer.render_wavefront == the same, accumulation, refusals, a second frame on the same handle.
+3. Renderer.render_wavefront == the same, accumulation, refusals, a second frame on the same handle; the plain, the
+   queued and the finish loop refuse alike, word for word.
 4. on_bounce under device compaction.
 5. a side stream without synchronisation == the default stream.
 6. the checked build in a fresh child process gives the same bits.
@@ -315,6 +316,82 @@ def test_render_wavefront_accumulates_refuses_and_reuses_its_scratch(frames):
     # no sample: the sums are cleared, nothing is traced
     assert b.render_wavefront(scene, 0, 20) == {"rays": 0, "iterations": 0, "ms": 0.0}
     assert not b.linear().any()
+
+
+INVALID = -1                          # CRT_ERR_INVALID_ARGUMENT
+RENDER_ACCUMULATE = 1                 # CRT_RENDER_ACCUMULATE
+# What the three loops answer to a call they refuse, word for word from the library's source (crt_paths.h), in the order
+# the library checks: (status, crt_last_error()).  The camera is looked at before the work-counter flag.
+REFUSALS = {
+    "negative spp": (INVALID, "render wavefront: negative spp"),
+    "no bounce": (INVALID, "render wavefront: max_bounces must be >= 1"),
+    "sync_every": (INVALID, "render wavefront: sync_every must be >= 0"),                 # the two queued entries only
+    "unknown flag": (INVALID, "render wavefront: unknown flag"),
+    "no camera": (INVALID, "render wavefront: camera not set"),
+    "count work": (UNSUPPORTED, "render wavefront: work counters are the render kernels' (crt_renderer_render)"),
+    "pixel shard": (UNSUPPORTED, "render wavefront: pixel sharding is crt_renderer_render's"),
+}
+FINISH_BELOW = (INVALID, "render wavefront: finish_below must be >= 0, or -1 for the default")   # the finish entry only
+
+
+def test_the_three_loops_refuse_alike():
+    """crt_renderer_render_wavefront, _queued and _finish through the library's own entries (the Python front-end
+    refuses some of these calls itself): the same status and the same text for the same bad input, the library's own
+    order of the checks, and the same answer to a frame of no samples.  No frame is rendered."""
+    import synth_scenes as synth
+    L = _lib.hip()
+    scene = custom_scene.CustomScene([], synth.SPHERES_ONLY["only3"], synth.SPHERE_MATS).upload(0)
+    r = crt_amd.Renderer(16, 8)
+    st = _lib.WavefrontStats()
+
+    def loop(entry, spp=1, bounces=20, flags=0, sync_every=0, finish_below=0):
+        """(status, crt_last_error()) of one of the three entries."""
+        if entry == "plain":
+            rc = L.crt_renderer_render_wavefront(r.h, scene.h, spp, bounces, flags, None, C.byref(st), None)
+        elif entry == "queued":
+            rc = L.crt_renderer_render_wavefront_queued(r.h, scene.h, spp, bounces, flags, None, sync_every, C.byref(st), None)
+        else:
+            rc = L.crt_renderer_render_wavefront_finish(r.h, scene.h, spp, bounces, flags, None, sync_every, finish_below,
+                                                        C.byref(st), None)
+        return rc, L.crt_last_error().decode() if rc else ""
+
+    def refused(what, want, only=("plain", "queued", "finish"), **kw):
+        got = {entry: loop(entry, **kw) for entry in only}
+        assert all(g == want for g in got.values()), (what, want, got)
+
+    bad = {"negative spp": dict(spp=-1), "no bounce": dict(bounces=0), "unknown flag": dict(flags=4),
+           "count work": dict(flags=RENDER_COUNT_WORK)}
+    # the renderer has no camera yet: every input that the library looks at before the camera is still named first
+    refused("no camera", REFUSALS["no camera"])
+    for what in ("negative spp", "no bounce", "unknown flag"):
+        refused(what + ", no camera", REFUSALS[what], **bad[what])
+    refused("no camera, count work", REFUSALS["no camera"], **bad["count work"])
+    r.set_camera(crt_amd.camera(1))
+    r.init_rand(41)
+    # each input alone
+    for what, kw in bad.items():
+        refused(what, REFUSALS[what], **kw)
+    refused("sync_every", REFUSALS["sync_every"], only=("queued", "finish"), sync_every=-1)
+    refused("finish_below", FINISH_BELOW, only=("finish",), finish_below=-2)
+    r.set_pixel_shard(0, 2)
+    refused("pixel shard", REFUSALS["pixel shard"])
+    # together: the first of the checks wins, in all three alike
+    refused("all at once", REFUSALS["negative spp"], spp=-1, bounces=0, flags=4 | RENDER_COUNT_WORK, sync_every=-1)
+    refused("no bounce first", REFUSALS["no bounce"], bounces=0, flags=4 | RENDER_COUNT_WORK, sync_every=-1)
+    refused("sync_every before the flags", REFUSALS["sync_every"], only=("queued", "finish"), flags=4 | RENDER_COUNT_WORK,
+            sync_every=-1)
+    refused("unknown flag first", REFUSALS["unknown flag"], flags=4 | RENDER_COUNT_WORK)
+    refused("count work before the shard", REFUSALS["count work"], flags=RENDER_COUNT_WORK)
+    refused("finish_below before everything", FINISH_BELOW, only=("finish",), spp=-1, bounces=0, finish_below=-2)
+    r.set_pixel_shard(0, 1)
+    # no sample: the sums are cleared unless the call accumulates, nothing is traced
+    pattern = (np.arange(8 * 16 * 3, dtype=F32).reshape(8, 16, 3) + F32(0.5))
+    for flags in (0, RENDER_ACCUMULATE):
+        for entry in ("plain", "queued", "finish"):
+            r.write_linear(pattern)
+            st.rays, st.iterations = 7, 7
+            assert loop(entry, spp=0, flags=flags) == (0, "") and (st.rays, st.iterations) == (0, 0), (entry, flags)
+            assert same(r.linear(), pattern if flags else np.zeros_like(pattern)), (entry, flags)
 
 
 # ------------------------------------------------------------------------------------------ 4. on_bounce
